@@ -18,8 +18,14 @@ edges, 256 features); it fits one GPU (~60 GB).  At N > 1 the same graph is shar
 
 Besides the contract fields the JSON line carries
   roofline     for the dominant kernel (forward SpMM): algorithmic bytes B_gather / HIP-event time
-  cpu_baseline the CPU oracle (the port of the reference arithmetic) timed on this box's host cores on a
-               bounded sample (rank 0, N = 1 only)
+and, with --full only (a plain run sets up, warms up, times the steps and prints the line):
+  ceilings     the in-run copy / gather ceilings beside the roofline (N = 1)
+  vertex_order_control, cpp_api   the as-generated vertex order and the C++ call-site leg (N = 1)
+  cpu_baseline, cpu_reference     the CPU oracle (the port of the reference arithmetic) timed on this box's host cores on a
+               bounded sample, and the compiled reference at Cora size (rank 0, N = 1 only)
+
+--dump-outputs DIR writes what the last timed step computed (N = 1): out, dX, dW, dbias of the layer -- out and dX on a fixed,
+seeded sample of rows -- or, for --train-layers, every layer's parameters after the last SGD step; float32 .npy files.
 """
 import argparse
 import ctypes as C
@@ -216,6 +222,11 @@ def main():
     ap.add_argument("--workload", default="rmat10m_100m_f256", choices=sorted(WORKLOADS))
     ap.add_argument("--chunk", type=int, default=1024,
                     help="plan: rows longer than this go to the sequential hub kernel (one accumulator per feature, the reference's order; 0 = no plan)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: in-run ceilings, vertex-order control, C++ call-site "
+                         "leg, CPU baseline and the reference's timing (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N=1: write the outputs of the last timed step to DIR/<name>.npy (float32; a fixed sample of rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train-layers", type=int, default=0,
                     help="N=1 only: time a whole training step of an L-layer GCN instead (forward, softmax-CE, backward, SGD); "
@@ -276,6 +287,8 @@ def main():
                          "device -- on all host threads (about 35 s at 10 M / 100 M / 256 on 128 threads); > 0: a sample of that many "
                          "nodes from the same generator (same average degree).  The single-thread leg always runs on 1/40 of the nodes")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded):
+        sys.exit("--dump-outputs is implemented for the single-GPU runs only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -385,11 +398,13 @@ def main():
 
     ms_per_step = dt / args.steps * 1e3
     nnz_total = runner.nnz_total * max(1, args.train_layers)
+    if args.dump_outputs:   # before anything below runs the step again (the vertex-order control reuses the output buffers)
+        runner.dump_outputs(args.dump_outputs)
     if graph is not None:  # per-kernel HIP events are not recorded inside a replayed graph: time the kernels once eagerly
         runner.step(timed=True)
         torch.cuda.synchronize()
     ceilings = None
-    if world == 1 and not args.force_sharded and not args.no_ceilings and rank == 0:
+    if args.full and world == 1 and not args.force_sharded and not args.no_ceilings and rank == 0:
         ceilings = measure_ceilings(capi, dev)   # outside the timed region: two small kernels, a few ms each
     if isinstance(runner, SingleGpu):
         roof = runner.roofline(ceilings)
@@ -407,8 +422,8 @@ def main():
     runner_chunks = getattr(getattr(runner, "plan", None), "n_chunks", 1)
     # control for the vertex order (informational, outside the timed region above): the same runner on the as-generated labels
     order_control = None
-    if (world == 1 and not args.force_sharded and not args.train_layers and relabel and graph is None and not args.no_order_control
-            and isinstance(runner, SingleGpu)):
+    if (args.full and world == 1 and not args.force_sharded and not args.train_layers and relabel and graph is None
+            and not args.no_order_control and isinstance(runner, SingleGpu)):
         order_control = runner.as_generated_control(pkg, n, e, abc, seed, args.chunk)
 
     if order_control and roof.get("avg_launch_ms") and order_control.get("spmm_fwd_ms"):
@@ -416,11 +431,11 @@ def main():
         order_control["hbm_spec_frac_as_generated"] = (roof["algorithmic_bytes_per_launch"] / (order_control["spmm_fwd_ms"] * 1e-3) / 1e9
                                                        / HBM_PEAK_GBS)
     cpu = cpu_ref = cpp = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(pkg, args, F, abc, seed, runner=runner)
         cpu_ref = cpu_reference(pkg)
-    if (rank == 0 and world == 1 and not args.force_sharded and not args.train_layers and not args.no_cpp_api and abc is not None
-            and abc == (0.57, 0.19, 0.19)):
+    if (args.full and rank == 0 and world == 1 and not args.force_sharded and not args.train_layers and not args.no_cpp_api
+            and abc is not None and abc == (0.57, 0.19, 0.19)):
         # free this process's device memory first: the child builds the same graph and tensors through the C++ API
         del runner
         ops._ws_cache.clear()
@@ -648,6 +663,17 @@ class SingleGpu:
         torch.cuda.empty_cache()
         return out
 
+    DUMP_ROWS = 16384   # rows of out and dX in the --dump-outputs sample: 2 x 16 MB at F = 256
+
+    def dump_outputs(self, path):
+        """--dump-outputs: what the caller of the layer step receives -- out and dX on a fixed, seeded sample of rows (row numbers in
+        the bench's row order, rows.npy), dW and dbias whole."""
+        k = min(self.n, self.DUMP_ROWS)
+        rows = np.sort(np.random.default_rng(20240611).choice(self.n, size=k, replace=False))
+        idx = torch.from_numpy(rows).to(self.out.device)
+        write_outputs(path, {"rows": rows.astype(np.float64), "out": self.out[idx], "dX": self.dX[idx], "dW": self.dW,
+                             "dbias": self.dbias})
+
     def kernel_times(self):
         out = {}
         for i, nm in enumerate(self.names):
@@ -769,6 +795,27 @@ class TrainStep(SingleGpu):
     def roofline(self, ceilings=None):
         return {"bound": "hbm", "kernel": "n/a for --train-layers (see the default run)", "achieved": None, "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": None, "traffic": None, "ceilings": ceilings}
+
+    def dump_outputs(self, path):
+        """--dump-outputs: every layer's weight and bias after the last SGD step."""
+        arrays = {}
+        for l, (W, b) in enumerate(zip(self.net.W, self.net.b)):
+            arrays[f"W{l}"], arrays[f"b{l}"] = W, b
+        write_outputs(path, arrays)
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy for every array: device tensors copied to the host as float32, numpy arrays as given (float64 row numbers)."""
+    arrays = {k: v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpp_api_bench(n, e, F, seed, both_orders=True, steps=5):

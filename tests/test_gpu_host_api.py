@@ -210,9 +210,9 @@ def _run_bench(args, timeout=600):
 
 def test_bench_contract_single_gpu_and_sharded_rehearsal():
     """bench.py's JSON line (the driver's contract): metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling /
-    dtype / data / config.workload, a roofline object for the dominant kernel and the cpu_baseline object at N = 1; and the
+    dtype / data / config.workload, a roofline object for the dominant kernel and, with --full, the cpu_baseline object at N = 1; and the
     N > 1 code path (partition, halo plan, overlap schedule, all-reduce) rehearsed on one rank."""
-    d = _run_bench(["--workload", "tiny", "--steps", "3", "--warmup", "1"])
+    d = _run_bench(["--workload", "tiny", "--steps", "3", "--warmup", "1", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -230,7 +230,7 @@ def test_bench_contract_single_gpu_and_sharded_rehearsal():
     assert ro["peak"] == 8000.0 and 3000.0 < ro["ceilings"]["fabric_gather_GBps"] < 12000.0
     assert abs(ro["frac_algorithmic_vs_hbm_spec"] - ro["effective_GBps"] / 8000.0) < 1e-9 and "traffic_from_committed_profile" in ro
     assert 2500.0 < ro["ceilings"]["hbm_copy_GBps"] < 8000.0 and ro["effective_GBps"] > 0 and ro["avg_launch_ms"] > 0
-    nc = _run_bench(["--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-ceilings", "--no-cpp-api"])
+    nc = _run_bench(["--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ceilings", "--no-cpp-api"])
     assert nc["roofline"]["peak"] == 8000.0 and nc["roofline"]["ceilings"] is None and nc["cpp_api"] is None
     cp = d["cpp_api"]   # the C++ call-site leg ran as a child process on the same workload
     assert cp and "error" not in cp and cp["hot_path_ms"] > 0 and cp["full_layer_ms"] > cp["hot_path_ms"] * 0.9, cp
@@ -245,6 +245,35 @@ def test_bench_contract_single_gpu_and_sharded_rehearsal():
     t = _run_bench(["--workload", "tiny", "--steps", "2", "--warmup", "1", "--force-sharded", "--no-cpu-baseline", "--train-layers", "2"])
     assert t["n_gpus"] == 1 and "training step" in t["config"]["step"] and t["roofline"]["frac"] is None
     assert abs(t["value"] - 2 * t["config"]["nnz"] / (t["ms_per_step"] * 1e-3)) <= 1e-6 * t["value"]
+
+
+def test_bench_plain_run_dumps_its_outputs():
+    """A plain run (no --full) measures nothing beside the steps; --dump-outputs writes what the last timed step computed, as float
+    .npy files within 64 MB, and two runs with the same arguments write the same bits.  With --train-layers: the parameters."""
+    with tempfile.TemporaryDirectory() as td:
+        dirs = [os.path.join(td, "a"), os.path.join(td, "b")]
+        lines = [_run_bench(["--workload", "tiny", "--steps", str(k), "--warmup", "1", "--dump-outputs", p]) for k, p in zip((2, 3), dirs)]
+        for d, k in zip(lines, (2, 3)):
+            assert d["steps"] == k and d["ms_per_step"] > 0 and d["roofline"]["avg_launch_ms"] > 0
+            assert d["roofline"]["ceilings"] is None and d["cpp_api"] is None and d["cpu_baseline"] is None
+            assert d["cpu_reference"] is None and d["vertex_order_control"] is None
+        got = []
+        for p in dirs:
+            arrays = {f[:-4]: np.load(os.path.join(p, f)) for f in sorted(os.listdir(p))}
+            assert set(arrays) == {"rows", "out", "dX", "dW", "dbias"}
+            assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+            assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+            F = lines[0]["config"]["features"]
+            k = min(lines[0]["config"]["n_nodes"], 16384)
+            assert arrays["out"].shape == (k, F) and arrays["dX"].shape == (k, F) and arrays["dW"].shape == (F, F)
+            assert arrays["dbias"].shape == (F,) and np.all(np.diff(arrays["rows"]) > 0)
+            assert all(np.isfinite(a).all() for a in arrays.values()) and np.abs(arrays["out"]).max() > 0
+            got.append(arrays)
+        for name in got[0]:
+            assert np.array_equal(got[0][name], got[1][name]), name
+        tr = os.path.join(td, "train")
+        _run_bench(["--workload", "tiny", "--steps", "2", "--warmup", "1", "--train-layers", "2", "--dump-outputs", tr])
+        assert sorted(os.listdir(tr)) == ["W0.npy", "W1.npy", "b0.npy", "b1.npy"]
 
 
 def test_multi_process_job_rehearsal_on_one_gpu():
