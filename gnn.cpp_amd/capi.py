@@ -138,6 +138,15 @@ _SIGS = {
     "gnnx_softmax_ce_colsum_f32": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_softmax_ce_partial_f32": [_vp, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_sgd_step_f32": [_vp, _vp, _i64, _f32, _f32, _vp],
+    "gnnx_mask_to_rows_workspace": [_i64, C.POINTER(_sz)],
+    "gnnx_mask_to_rows": [_vp, _i64, _vp, C.POINTER(_i32), _vp, _sz, _vp],
+    "gnnx_csr_restrict_workspace": [_i32, _i64, C.POINTER(_sz)],
+    "gnnx_csr_restrict": [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _sz, _vp],
+    "gnnx_softmax_ce_rows_workspace": [_i64, _i32, C.POINTER(_sz)],
+    "gnnx_softmax_ce_rows_f32": [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
+    "gnnx_argmax_rows_workspace": [C.POINTER(_sz)],
+    "gnnx_argmax_rows_f32": [_vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp],
+    "gnnx_accuracy_rows_f32": [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, C.POINTER(_i64), _vp, _sz, _vp],
     "gnnx_comm_unique_id": [_vp],
     "gnnx_comm_init": [C.POINTER(_vp), C.c_int, C.c_int, _vp],
     "gnnx_comm_init_local": [C.POINTER(_vp), C.c_int],

@@ -57,8 +57,16 @@ public:
     size_t num_edges() const { return _num_edges; }
     cyg::tptr<float> x() const { return _x; }
     cyg::tptr<float> edge_attr() const { return _edge_attr; }
+    // the train / validation / test vertex sets of semi-supervised node classification (reference graph.h:86-94, graph.cpp:130-151):
+    // one bool per vertex; a mask of another size throws.  Not owned (the reference deletes the previous mask; callers own theirs
+    // here, as with set_edge_index).  nn::cross_entropy_loss(logits, target, mask) / nn::accuracy take them.
+    void set_mask(cyg::tensor<bool> &mask, DataType type = DataType::TRAIN);
+    cyg::tensor<bool> *train_mask() const { return _train_mask; }
+    cyg::tensor<bool> *val_mask() const { return _val_mask; }
+    cyg::tensor<bool> *test_mask() const { return _test_mask; }
 
 protected:
+    cyg::tensor<bool> *_train_mask = nullptr, *_val_mask = nullptr, *_test_mask = nullptr;
     size_t _num_nodes = 0, _num_node_features = 0, _num_edges = 0, _num_edge_features = 0;
     cyg::tensor<int> *_edge_index = nullptr;
     cyg::tensor<float> *_y = nullptr;

@@ -110,6 +110,14 @@ cyg::tptr<float> cross_entropy_loss(const cyg::tptr<float> logits, const cyg::tp
 // (addition) a shard's share of the loss over a batch of n_total rows (1-D vertex partition): the value is this rank's term of the
 // mean -- sum the ranks' values for the loss -- and the gradient carries 1 / n_total, as the unsharded call on all rows would
 cyg::tptr<float> cross_entropy_loss(const cyg::tptr<float> logits, const cyg::tptr<int> target, size_t n_total);
+// (addition) semi-supervised node classification: the loss over the rows whose mask entry is true (graph::Data's train mask),
+// divided by their number; target is read at those rows only.  Backward: (softmax - onehot) / n_masked on the masked rows, zero rows
+// elsewhere.  A mask without a true entry throws (the mean over no rows is undefined).  gnnx_softmax_ce_rows_f32.
+cyg::tptr<float> cross_entropy_loss(const cyg::tptr<float> logits, const cyg::tptr<int> target, cyg::tensor<bool> &mask);
+// (addition) how many masked rows have argmax(logits row) == target -- the FIRST index of the maximum, as the reference's
+// tensor::argmax (functional.h:59-61) -- and that count over the number of masked rows.  gnnx_accuracy_rows_f32.
+size_t count_correct(const cyg::tptr<float> logits, const cyg::tptr<int> target, cyg::tensor<bool> &mask);
+float accuracy(const cyg::tptr<float> logits, const cyg::tptr<int> target, cyg::tensor<bool> &mask);
 
 // Optimisers over device-resident parameters (reference nn.h:156-191).  SGD is the textbook update
 // p -= lr * (g + weight_decay * p) (+ momentum buffers); the reference's step() reads an empty velocity vector

@@ -634,6 +634,118 @@ tptr<float> cross_entropy_loss(const tptr<float> logits, const tptr<int> target)
     return out;
 }
 
+namespace {
+// ascending device row list of a host bool mask over the n rows of the logits (gnnx_mask_to_rows)
+tptr<int> rows_of_mask(tensor<bool> &mask, size_t n)
+{
+    if (mask.numel() != n) throw std::runtime_error(ERROR_SIZE_MISMATCH);
+    const std::valarray<bool> &h = *mask.data();
+    std::vector<uint8_t> bytes(n);
+    for (size_t i = 0; i < n; i++) bytes[i] = h[i] ? 1 : 0;
+    void *st = detail::current_stream();
+    void *d_mask = detail::dev_alloc(n ? n : 1);
+    auto all = std::make_shared<tensor<int>>(tensor<int>::device_tag{}, std::vector<size_t>{n ? n : 1}, false);
+    int32_t count = 0;
+    try {
+        if (n) detail::gx(gnnx_memcpy_h2d(d_mask, bytes.data(), n, st), "mask");
+        size_t wsb = 0;
+        detail::gx(gnnx_mask_to_rows_workspace((int64_t)n, &wsb), "mask");
+        detail::gx(gnnx_mask_to_rows(static_cast<const uint8_t *>(d_mask), (int64_t)n, all->device_out(), &count, detail::workspace(wsb), wsb, st),
+                   "mask");   // synchronises: `bytes` and d_mask are done with
+    } catch (...) {
+        detail::dev_free(d_mask, n ? n : 1);
+        throw;
+    }
+    detail::dev_free(d_mask, n ? n : 1);
+    if (count == 0) throw std::runtime_error("invalid input, mask selects no row");
+    auto rows = std::make_shared<tensor<int>>(tensor<int>::device_tag{}, std::vector<size_t>{(size_t)count}, false);
+    detail::gx(gnnx_memcpy_d2d(rows->device_out(), all->device_data(), (size_t)count * sizeof(int), st), "mask");
+    return rows;
+}
+
+class MaskedCrossEntropyOp : public cyg::Operation<tensor<float>> {
+public:
+    tptr<int> target, rows;
+    MaskedCrossEntropyOp() { name = "MaskedCrossEntropy"; }
+    void run(const tptr<float> &logits, float *d_loss, float *d_dlogits)
+    {
+        const auto shp = logits->shape();
+        const int64_t nl = (int64_t)rows->numel();
+        size_t wsb = 0;
+        detail::gx(gnnx_softmax_ce_rows_workspace(nl, (int32_t)shp[1], &wsb), "cross_entropy");
+        detail::gx(gnnx_softmax_ce_rows_f32(logits->device_data(), (int64_t)shp[1], target->device_data(), rows->device_data(), nl, (int64_t)shp[0],
+                                            (int32_t)shp[1], nl, d_loss, d_dlogits, (int64_t)shp[1], nullptr, detail::workspace(wsb), wsb,
+                                            detail::current_stream()),
+                   "cross_entropy");
+    }
+    tptr<float> forward(const tptr<float> &logits, const tptr<int> &tgt, tensor<bool> &mask)
+    {
+        if (logits->rank() != 2 || tgt->rank() != 1)
+            throw std::runtime_error("invalid input, logits must be of rank 2 and targets must be 1D tensor");
+        const auto shp = logits->shape();
+        if (tgt->numel() != shp[0]) throw std::runtime_error(ERROR_SIZE_MISMATCH);
+        target = tgt;
+        rows = rows_of_mask(mask, shp[0]);
+        auto out = std::make_shared<tensor<float>>(tensor<float>::device_tag{}, std::vector<size_t>{1}, logits->requires_grad());
+        run(logits, out->device_out(), nullptr);
+        if (out->requires_grad()) context->save_for_backward({logits});
+        return out;
+    }
+    void _backward(std::shared_ptr<tensor<float>> g) override
+    {
+        auto var = context->get_variables();
+        CHECK_BACKWARD<tensor<float>>(var, 1);
+        auto logits = var[0];
+        if (!logits->requires_grad()) return;
+        void *st = detail::current_stream();
+        auto d = std::make_shared<tensor<float>>(tensor<float>::device_tag{}, logits->shape(), false);
+        float *dd = d->device_out();
+        detail::gx(gnnx_fill_f32(dd, (int64_t)d->numel(), 0.0f, st), "cross_entropy");   // rows outside the mask: zero
+        run(logits, nullptr, dd);
+        const float up = g->item();  // upstream scalar (1 for loss->backward())
+        if (up != 1.0f) {
+            auto scaled = std::make_shared<tensor<float>>(tensor<float>::device_tag{}, logits->shape(), false);
+            detail::gx(gnnx_fill_f32(scaled->device_out(), (int64_t)scaled->numel(), 0.0f, st), "cross_entropy");
+            detail::gx(gnnx_axpy_f32((int64_t)scaled->numel(), up, d->device_data(), scaled->device_inplace(), st), "cross_entropy");
+            d = scaled;
+        }
+        logits->backward(d);
+    }
+};
+}  // namespace
+
+tptr<float> cross_entropy_loss(const tptr<float> logits, const tptr<int> target, tensor<bool> &mask)
+{
+    auto op = std::make_unique<MaskedCrossEntropyOp>();
+    auto out = op->forward(logits, target, mask);
+    if (out->requires_grad()) out->grad_fn = std::move(op);
+    return out;
+}
+
+size_t count_correct(const tptr<float> logits, const tptr<int> target, tensor<bool> &mask)
+{
+    if (logits->rank() != 2 || target->rank() != 1)
+        throw std::runtime_error("invalid input, logits must be of rank 2 and targets must be 1D tensor");
+    const auto shp = logits->shape();
+    if (target->numel() != shp[0]) throw std::runtime_error(ERROR_SIZE_MISMATCH);
+    auto rows = rows_of_mask(mask, shp[0]);
+    size_t wsb = 0;
+    detail::gx(gnnx_argmax_rows_workspace(&wsb), "accuracy");
+    int64_t correct = 0;
+    detail::gx(gnnx_accuracy_rows_f32(logits->device_data(), (int64_t)shp[1], target->device_data(), rows->device_data(), (int64_t)rows->numel(),
+                                      (int64_t)shp[0], (int32_t)shp[1], nullptr, &correct, detail::workspace(wsb), wsb, detail::current_stream()),
+               "accuracy");
+    return (size_t)correct;
+}
+
+float accuracy(const tptr<float> logits, const tptr<int> target, tensor<bool> &mask)
+{
+    size_t n_masked = 0;
+    const std::valarray<bool> &h = *mask.data();
+    for (size_t i = 0; i < h.size(); i++) n_masked += h[i] ? 1 : 0;
+    return (float)count_correct(logits, target, mask) / (float)n_masked;   // (an empty mask has thrown in count_correct)
+}
+
 void Optimizer::zero_grad()
 {
     for (auto &p : _parameters) p->zero_grad();
@@ -752,6 +864,14 @@ Data::Data(const tptr<float> &x, tensor<int> *edge_index, tptr<float> edge_attr,
             _num_edge_features = edge_attr->shape()[1];
         }
     }
+}
+void Data::set_mask(tensor<bool> &mask, DataType type)
+{
+    if (mask.numel() != _num_nodes)
+        throw std::runtime_error("invalid input, mask must be 1D and of same size with num of nodes in graph");
+    if (type == DataType::TRAIN) _train_mask = &mask;
+    else if (type == DataType::VAL) _val_mask = &mask;
+    else if (type == DataType::TEST) _test_mask = &mask;
 }
 tensor<int> *Data::edge_index()
 {

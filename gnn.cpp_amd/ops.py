@@ -184,6 +184,7 @@ class CsrGraph:
     def make_plans(self, chunk, max_feat, big_rows=None):
         """Load-balancing plans for power-law rows (forward CSR and transposed CSR).  big_rows: the threshold above which a hub row
         takes the producer / consumer kernel (SpmmPlan.set_big_row_threshold; None = the library's default)."""
+        self._plan_args = (int(chunk), int(max_feat), big_rows)   # CsrGraph.labelled builds its plans the same way
         self.plan = SpmmPlan(self.rowptr, chunk, max_feat)
         if self.rowptr_t is not None:
             self.plan_t = SpmmPlan(self.rowptr_t, chunk, max_feat)
@@ -192,6 +193,94 @@ class CsrGraph:
                 if pl is not None:
                     pl.set_big_row_threshold(big_rows)
         return self.plan, self.plan_t
+
+
+    def mask_in_row_order(self, mask):
+        """A vertex-order mask ([n] bool / uint8, vertex v at position v) as uint8 in this graph's row order (vertex v at nid[v])."""
+        if int(mask.numel()) != self.n:
+            raise ValueError(f"mask has {int(mask.numel())} entries, the graph has {self.n} vertices")
+        m = mask.reshape(-1).to(torch.uint8)
+        return self.to_new_order(m).contiguous()
+
+    def rows_of(self, mask):
+        """The rows of this graph (ascending int32) that hold the vertices of a vertex-order mask."""
+        return rows_from_mask(self.mask_in_row_order(mask))
+
+    def labelled(self, mask):
+        """The labelled vertex set of semi-supervised training (reference graph.cpp:130-151 set_mask) prepared for the pruned last
+        layer: a LabelledSet in this graph's row order.  mask: [n] bool / uint8 in VERTEX order (as X before to_new_order)."""
+        return LabelledSet(self, mask)
+
+
+class LabelledSet:
+    """rows / n_labelled of a train mask, the row-restricted CSR(A) (entries whose row is labelled) and the column-restricted
+    CSR(A^T) (entries whose column is labelled, with norm_per_nz_t restricted by the same call), and an SpmmPlan for each when the
+    graph has plans (same chunk).  Both CSRs hold the same edge set.  The last layer's aggregations on them have the bits of the
+    full ones wherever the loss looks (a dropped term is norm * 0)."""
+
+    def __init__(self, g, mask):
+        if g.rowptr_t is None or g.norm is None:
+            raise ValueError("labelled() needs the transposed CSR and the norm (from_coo(transpose=True, norm=True))")
+        m = g.mask_in_row_order(mask)
+        self.mask = m
+        self.rows = rows_from_mask(m)
+        self.n_labelled = int(self.rows.numel())
+        self.rowptr, self.colidx, _ = csr_restrict(g.rowptr, g.colidx, row_keep=m, n_cols=g.n)
+        if getattr(g, "norm_per_nz_t", None) is None:
+            g.norm_per_nz_t = gather_rows(g.norm.reshape(-1, 1), g.colidx_t).reshape(-1)
+        self.rowptr_t, self.colidx_t, self.norm_per_nz_t = csr_restrict(g.rowptr_t, g.colidx_t, vals=g.norm_per_nz_t, col_keep=m, n_cols=g.n)
+        self.nnz = int(self.colidx.numel())
+        self.plan = self.plan_t = None
+        if g.plan is not None:
+            chunk, max_feat, big_rows = g._plan_args
+            self.plan = SpmmPlan(self.rowptr, chunk, max_feat)
+            self.plan_t = SpmmPlan(self.rowptr_t, chunk, max_feat) if g.plan_t is not None else None
+            if big_rows is not None:
+                for pl in (self.plan, self.plan_t):
+                    if pl is not None:
+                        pl.set_big_row_threshold(big_rows)
+
+
+def rows_from_mask(mask):
+    """gnnx_mask_to_rows: ascending int32 positions of the non-zero entries of a [n] bool / uint8 device tensor."""
+    m = mask.reshape(-1)
+    m = (m if m.dtype == torch.uint8 else m.to(torch.uint8)).contiguous()
+    n = int(m.numel())
+    rows = torch.empty(max(n, 1), dtype=torch.int32, device=m.device)
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_mask_to_rows_workspace", n, C.byref(wsb))
+    ws = _workspace(wsb.value, m.device, "mask")
+    cnt = C.c_int32(0)
+    capi.call("gnnx_mask_to_rows", _ptr(m), n, _ptr(rows), C.byref(cnt), _ptr(ws), ws.numel(), _stream())
+    return rows[: cnt.value].clone()
+
+
+def csr_restrict(rowptr, colidx, vals=None, row_keep=None, col_keep=None, n_cols=None):
+    """gnnx_csr_restrict: the CSR with the same rows keeping entry (r, c) iff row_keep[r] (when given) and col_keep[c] (when given);
+    stored order inside a row is kept.  Masks: [n_rows] / [n_cols] bool or uint8.  -> (rowptr', colidx', vals' or None)."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    dev = rowptr.device
+    u8 = lambda t: None if t is None else (t if t.dtype == torch.uint8 else t.to(torch.uint8)).reshape(-1).contiguous()  # noqa: E731
+    rk, ck = u8(row_keep), u8(col_keep)
+    if rk is not None and int(rk.numel()) != n_rows:
+        raise ValueError("row_keep must have one entry per row")
+    if n_cols is None:
+        n_cols = int(ck.numel()) if ck is not None else n_rows
+    if ck is not None and int(ck.numel()) != n_cols:
+        raise ValueError("col_keep must have one entry per column")
+    rowptr_o = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
+    colidx_o = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    vals_o = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev) if vals is not None else None
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_csr_restrict_workspace", n_rows, nnz, C.byref(wsb))
+    ws = _workspace(wsb.value, dev, "mask")
+    out_nnz = C.c_int64(0)
+    capi.call("gnnx_csr_restrict", n_rows, int(n_cols), nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(vals), _ptr(rk), _ptr(ck),
+              _ptr(rowptr_o), _ptr(colidx_o), _ptr(vals_o), C.byref(out_nnz), _ptr(ws), ws.numel(), _stream())
+    k = out_nnz.value
+    # (an empty result stays a view of its 1-element buffer: the aggregation wants a device pointer even for no entries)
+    shrink = lambda t: None if t is None else (t[:k].clone() if k else t[:0])  # noqa: E731
+    return rowptr_o, shrink(colidx_o), shrink(vals_o)
 
 
 def to_bf16(X, out=None):
@@ -544,18 +633,26 @@ def linear_fwd(X, W, out=None):
     return gemm(X, W, transB=True, out=out)
 
 
-def aggregate_fwd(g, H, bias=None, out=None, use_plan=True, bn=None, relu_in=False, relu_out=False):
+def aggregate_fwd(g, H, bias=None, out=None, use_plan=True, bn=None, relu_in=False, relu_out=False, labelled=None):
     """out = norm (.) (A . H) (+ bias)  (graph.cpp:204-212, :188).  bn / relu_in: GCNConv's BatchNorm + ReLU between transform
-    and aggregation (graph.cpp:174-175) folded into the gather; relu_out: the ReLU in front of the next layer."""
-    return spmm(g.rowptr, g.colidx, H, out=out, rowscale=g.norm, bias=bias, plan=g.plan if use_plan else None, bn=bn,
+    and aggregation (graph.cpp:174-175) folded into the gather; relu_out: the ReLU in front of the next layer.
+    labelled (CsrGraph.labelled): the same call on the row-restricted CSR -- labelled rows have the full aggregation's bits, every
+    other row holds `bias` (not computed)."""
+    c = g if labelled is None else labelled
+    return spmm(c.rowptr, c.colidx, H, out=out, rowscale=g.norm, bias=bias, plan=c.plan if use_plan else None, bn=bn,
                 relu_in=relu_in, relu_out=relu_out)
 
 
-def aggregate_bwd(g, G, out=None, beta=0.0, use_plan=True):
+def aggregate_bwd(g, G, out=None, beta=0.0, use_plan=True, labelled=None):
     """dH = A^T . (norm (.) G)  (operation.h:144-167 then :524-531).
     The per-source scale norm[i] is handed to the kernel per non-zero (vals_t[p] = norm[colidx_t[p]], gathered once per
     graph): a coalesced 4 B/edge stream instead of a random 4-byte gather per edge; the arithmetic (one rounded multiply
-    per term) is identical."""
+    per term) is identical.
+    labelled (CsrGraph.labelled): G is zero outside the labelled rows; the same call on the column-restricted CSR(A^T) -- the
+    dropped terms are norm * 0, the result has the full product's bits."""
+    if labelled is not None:
+        return spmm(labelled.rowptr_t, labelled.colidx_t, G, out=out, vals=labelled.norm_per_nz_t, beta=beta,
+                    plan=labelled.plan_t if use_plan else None)
     if getattr(g, "norm_per_nz_t", None) is None:
         g.norm_per_nz_t = gather_rows(g.norm.reshape(-1, 1), g.colidx_t).reshape(-1)
     return spmm(g.rowptr_t, g.colidx_t, G, out=out, vals=g.norm_per_nz_t, beta=beta, plan=g.plan_t if use_plan else None)
@@ -643,6 +740,46 @@ def softmax_ce(logits, target, want_grad=True, colsum_out=None, n_total=None, gr
     return loss, d
 
 
+def softmax_ce_rows(logits, target, rows, colsum_out=None, grad_out=None, n_total=None, want_grad=True):
+    """gnnx_softmax_ce_rows_f32: (loss over the listed rows / n_total as a 1-element device tensor, dlogits or None).  Only the listed
+    rows of the gradient buffer are written: pass a zeroed grad_out (without one a zero-filled buffer is made).  target is read at
+    listed rows only.  colsum_out [C]: the column sums of the listed gradient rows.  n_total: the divisor (default: len(rows))."""
+    N, Cn = logits.shape
+    nl = int(rows.numel())
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    d = (torch.zeros_like(logits) if grad_out is None else grad_out) if want_grad else None
+    if colsum_out is not None:
+        assert want_grad and colsum_out.numel() == Cn and colsum_out.is_contiguous()
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_softmax_ce_rows_workspace", nl, Cn, C.byref(wsb))
+    ws = _workspace(wsb.value, logits.device, "ce")
+    capi.call("gnnx_softmax_ce_rows_f32", _ptr(logits), _ld(logits), _ptr(target), _ptr(rows) if nl else None, nl, N, Cn,
+              int(nl if n_total is None else n_total), _ptr(loss), _ptr(d), _ld(d) if want_grad else 0, _ptr(colsum_out), _ptr(ws),
+              ws.numel(), _stream())
+    return loss, d
+
+
+def argmax_rows(logits):
+    """gnnx_argmax_rows_f32: int32 [N], the first index of each row's maximum (reference functional.h:59-61)."""
+    N, Cn = logits.shape
+    pred = torch.empty(max(N, 1), dtype=torch.int32, device=logits.device)
+    ws = _workspace(512, logits.device, "argmax")
+    capi.call("gnnx_argmax_rows_f32", _ptr(logits), _ld(logits), N, Cn, _ptr(pred), _ptr(ws), ws.numel(), _stream())
+    return pred[:N]
+
+
+def accuracy(logits, target, rows=None):
+    """gnnx_accuracy_rows_f32: (number of listed rows -- all rows without a list -- whose argmax equals the target, number of rows
+    counted) as Python ints."""
+    N, Cn = logits.shape
+    nl = N if rows is None else int(rows.numel())
+    ws = _workspace(512, logits.device, "argmax")
+    correct = C.c_int64(0)
+    capi.call("gnnx_accuracy_rows_f32", _ptr(logits), _ld(logits), _ptr(target), _ptr(rows) if (rows is not None and nl) else None, nl, N, Cn,
+              None, C.byref(correct), _ptr(ws), ws.numel(), _stream())
+    return correct.value, nl
+
+
 def sgd_step(param, grad, lr, weight_decay=0.0):
     capi.call("gnnx_sgd_step_f32", _ptr(param), _ptr(grad), param.numel(), float(lr), float(weight_decay), _stream())
     return param
@@ -711,14 +848,16 @@ class GcnStack:
         Xp[:, :self.dims[0]] = X
         return Xp[:, :self.dims[0]]
 
-    def forward(self, X):
+    def forward(self, X, labelled=None):
+        """labelled (CsrGraph.labelled): the LAST layer aggregates on the row-restricted CSR -- logits rows of labelled vertices have
+        the bits of the full forward, every other logits row holds the last bias (not computed).  Layers below are not pruned."""
         L = len(self.W)
         if not self.padded:
             saved, h = [], X
             for l in range(L):
                 H = linear_fwd(h, self.W[l], out=self._gathered(("H", l), X.shape[0], self.dims[l + 1], X.device))
                 # the ReLU between layers rides in the aggregation's epilogue: only relu(Z) is stored (its sign is the mask)
-                Y = aggregate_fwd(self.g, H, self.b[l], relu_out=l + 1 < L)
+                Y = aggregate_fwd(self.g, H, self.b[l], relu_out=l + 1 < L, labelled=labelled if l + 1 == L else None)
                 saved.append((h, Y))
                 h = Y
             self._saved = saved
@@ -738,18 +877,20 @@ class GcnStack:
         for l in range(L):
             H = linear_fwd(hp, self.Wp[l][:d[l + 1]])                 # K = P[l] (zero pads), N = d[l+1]: gathered, own width
             Yp = self._zeros(("Y", l), (n, P[l + 1]), X.device)
-            aggregate_fwd(self.g, H, self.b[l], out=Yp[:, :d[l + 1]], relu_out=l + 1 < L)
+            aggregate_fwd(self.g, H, self.b[l], out=Yp[:, :d[l + 1]], relu_out=l + 1 < L, labelled=labelled if l + 1 == L else None)
             saved.append((hp, Yp))
             hp = Yp
         self._saved = saved
         return hp[:, :d[L]]
 
-    def backward(self, dOut, fused=True, input_grad=True, have_last_bias_grad=False):
+    def backward(self, dOut, fused=True, input_grad=True, have_last_bias_grad=False, labelled=None):
         """fused: the ReLU mask of the layer below and its bias gradient ride in the epilogue of dH . W
         (gnnx_gemm_relu_colsum_f32); fused=False runs them as their own passes (same G bits, db within rounding).
         input_grad=False: the stack's input is data (no requires_grad, as the reference's DataBatch features): dH . W of the
         first layer is not computed and None is returned.  have_last_bias_grad: db[L-1] was already written by the loss kernel
-        (softmax_ce(..., colsum_out=net.db[-1]))."""
+        (softmax_ce(..., colsum_out=net.db[-1])).  labelled (CsrGraph.labelled): dOut is zero outside the labelled rows
+        (softmax_ce_rows into a zeroed buffer); the LAST layer's backward aggregation runs on the column-restricted CSR(A^T) -- same
+        bits; the dense products and the layers below are not pruned."""
         G = dOut
         L = len(self.W)
         d, P = self.dims, self.P
@@ -762,11 +903,11 @@ class GcnStack:
                 # layers whose widths differ but round to the same 128-float bucket must not share pad columns (a narrower layer
                 # would inherit the wider one's values there, and dW / W pads would stop being zero)
                 dH = self._zeros(("dH", P[l + 1], d[l + 1]), (G.shape[0], P[l + 1]), G.device)
-                aggregate_bwd(self.g, G, out=dH[:, :d[l + 1]])
+                aggregate_bwd(self.g, G, out=dH[:, :d[l + 1]], labelled=labelled if l + 1 == L else None)
                 Wl, hl = self.Wp[l][:, :d[l]], h[:, :d[l]]            # [P_out, d_in] (ld P_in); the layer input, logical width
                 gemm(dH, h, transA=True, out=self.dWp[l])             # dW_l = dH^T . h on the padded widths
             else:
-                dH = aggregate_bwd(self.g, G)
+                dH = aggregate_bwd(self.g, G, labelled=labelled if l + 1 == L else None)
                 Wl, hl = self.W[l], h
                 gemm(dH, h, transA=True, out=self.dW[l])          # dW_l = dH^T . h
             if l == 0:
@@ -783,3 +924,32 @@ class GcnStack:
     def step(self, lr, weight_decay=0.0):
         for p, gr in zip(self.Wp + self.b, self.dWp + self.db):   # padded storage: pads are 0 - lr * (0 + wd * 0) = 0
             sgd_step(p, gr, lr, weight_decay)
+
+    def masked_grad_buffer(self, labelled):
+        """grad_buffer() zero everywhere outside the rows softmax_ce_rows writes: zeroed when first used and whenever a different
+        labelled set arrives (the rows the previous set wrote must become zero again)."""
+        G = self.grad_buffer()
+        key = (id(labelled), G.data_ptr())
+        if getattr(self, "_grad_zeroed_for", None) != key:
+            G.zero_()
+            self._grad_zeroed_for = key
+            self._grad_set = labelled   # keeps the set alive: id() stays unique
+        return G
+
+    def train_step(self, X, target, labelled, lr, weight_decay=0.0):
+        """One semi-supervised SGD step: forward with the pruned last layer -> softmax_ce_rows over labelled.rows (db[-1] from the loss
+        kernel) -> backward with the pruned last aggregation, no input gradient -> step.  X and target in the graph's ROW order
+        (g.to_new_order of vertex-order data); target is read at labelled rows only.  Returns the loss tensor."""
+        logits = self.forward(X, labelled=labelled)
+        loss, G = softmax_ce_rows(logits, target, labelled.rows, colsum_out=self.db[-1], grad_out=self.masked_grad_buffer(labelled))
+        self.backward(G, input_grad=False, have_last_bias_grad=True, labelled=labelled)
+        self.step(lr, weight_decay)
+        return loss
+
+    def evaluate(self, X, target, rows):
+        """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows)).  rows: ascending
+        int32 rows of the graph (g.rows_of(mask) for a vertex-order validation / test mask)."""
+        logits = self.forward(X)
+        loss, _ = softmax_ce_rows(logits, target, rows, want_grad=False)
+        correct, count = accuracy(logits, target, rows)
+        return loss, correct, count

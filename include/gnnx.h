@@ -458,6 +458,57 @@ int gnnx_softmax_ce_partial_f32(const float *d_logits, int64_t ldx, const int32_
                                 size_t workspace_bytes, void *stream);
 int gnnx_sgd_step_f32(float *d_param, const float *d_grad, int64_t n, float lr, float weight_decay, void *stream);
 
+/* ------------------------------------------------------------------ semi-supervised training: masks ---- */
+/*
+ * Node classification with a label mask (reference include/graph.h:86-94 / src/graph.cpp:130-151: Data::set_mask with a train, a
+ * validation and a test mask over the vertices; functional.h:59-61: argmax).  A mask is one byte per vertex (non-zero = in the set);
+ * the compute calls take the set as an ascending list of row ids.
+ *
+ *   gnnx_mask_to_rows   d_rows[k] = the k-th non-zero position of d_mask[0..n), ascending (capacity n int32); *n_rows_out: HOST, valid
+ *                       on return (synchronises `stream`).
+ *   gnnx_csr_restrict   the CSR with the SAME number of rows that keeps entry (r, c) iff d_row_keep[r] != 0 (when given) and
+ *                       d_col_keep[c] != 0 (when given); rows that lose everything become empty; surviving entries keep their STORED
+ *                       ORDER inside the row -- the summation order of the aggregation, also on a relabelled graph whose rows are
+ *                       sorted by original column id.  nnz = rowptr[n_rows] (checked); d_colidx_out / d_vals_out have capacity nnz;
+ *                       d_vals / d_vals_out both or neither; both masks NULL is a copy; not in place.  *nnz_out: HOST, valid on
+ *                       return (synchronises).  GNNX_ERR_INDEX_RANGE: a column id outside [0, n_cols) met under a column mask.
+ *                       With a train mask the last GCN layer aggregates on the row-restricted CSR(A) forward and on the
+ *                       column-restricted CSR(A^T) backward: every dropped term of a kept accumulator is norm * 0, so the kept rows
+ *                       and the whole backward product have the bits of the full aggregation.
+ *   gnnx_softmax_ce_rows_f32  the loss of gnnx_softmax_ce_f32 (reference forward nn.cpp:442-453) over the listed rows:
+ *                       loss = (sum_{i in rows} -log(exp(x_i[t_i]) / (sum_c exp(x_ic) + 1e-20))) / n_total;
+ *                       dlogits[i,:] = (softmax(x_i) - onehot(t_i)) / n_total for LISTED rows only -- every other row of the buffer
+ *                       is left as it is (the caller zeroes it once); d_colsum [n_classes] (may be NULL) = column sums of those
+ *                       gradient rows, fixed order.  n_total >= n_listed is the divisor (n_listed on one GPU; the labelled count of
+ *                       the whole batch on a shard).  d_rows: ascending, no repeats, each in [0, n_rows).  Targets are read at listed
+ *                       rows only (-1 elsewhere is fine).  Same expression per element and the same row-sum order as
+ *                       gnnx_softmax_ce_f32: listing every row gives its dlogits bits.  Cost O(n_listed), not O(n_rows).
+ *                       Synchronises.  GNNX_ERR_INDEX_RANGE: a target outside [0, n_classes) at a listed row, or a listed row
+ *                       outside [0, n_rows); GNNX_ERR_INVALID_ARG: n_listed == 0 (never a NaN loss).
+ *   gnnx_argmax_rows_f32      d_pred[i] = the FIRST index of the maximum of row i (functional.h:59-61), every row.
+ *   gnnx_accuracy_rows_f32    *correct_out (HOST) = number of listed rows (d_rows NULL: all n_rows rows, n_listed == n_rows) whose
+ *                       argmax equals the target (a target outside the classes never matches); d_pred (may be NULL): the class of
+ *                       the k-th listed row at d_pred[k].  Both synchronise.  A row with a NaN gives some in-range class
+ *                       (unspecified which).
+ */
+int gnnx_mask_to_rows_workspace(int64_t n, size_t *bytes);
+int gnnx_mask_to_rows(const uint8_t *d_mask, int64_t n, int32_t *d_rows, int32_t *n_rows_out, void *d_workspace, size_t workspace_bytes,
+                      void *stream);
+int gnnx_csr_restrict_workspace(int32_t n_rows, int64_t nnz, size_t *bytes);
+int gnnx_csr_restrict(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, const float *d_vals,
+                      const uint8_t *d_row_keep, const uint8_t *d_col_keep, int32_t *d_rowptr_out, int32_t *d_colidx_out,
+                      float *d_vals_out, int64_t *nnz_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_softmax_ce_rows_workspace(int64_t n_listed, int32_t n_classes, size_t *bytes);
+int gnnx_softmax_ce_rows_f32(const float *d_logits, int64_t ldx, const int32_t *d_target, const int32_t *d_rows, int64_t n_listed,
+                             int64_t n_rows, int32_t n_classes, int64_t n_total, float *d_loss, float *d_dlogits, int64_t ldd,
+                             float *d_colsum, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_argmax_rows_workspace(size_t *bytes);
+int gnnx_argmax_rows_f32(const float *d_logits, int64_t ldx, int64_t n_rows, int32_t n_classes, int32_t *d_pred, void *d_workspace,
+                         size_t workspace_bytes, void *stream);
+int gnnx_accuracy_rows_f32(const float *d_logits, int64_t ldx, const int32_t *d_target, const int32_t *d_rows, int64_t n_listed,
+                           int64_t n_rows, int32_t n_classes, int32_t *d_pred, int64_t *correct_out, void *d_workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */
