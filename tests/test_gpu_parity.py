@@ -26,11 +26,9 @@ import pytest
 
 import oracle
 from tests.golden_util import CASES, load_case, same
-from tests.helpers import synth
+from tests.helpers import RTOL, assert_close, synth  # noqa: F401  (assert_close: shared with test_gpu_large_offsets.py)
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-5  # north_star: "within 1e-5 relative fp32"
 
 
 @pytest.fixture(scope="module")
@@ -50,23 +48,6 @@ def dev(env, a):
 
 def host(t):
     return t.detach().cpu().numpy()
-
-
-def assert_close(got, ref, what="", absum=None, exact=None):
-    """|got - ref| <= RTOL * max(1, |ref|[, absum]).  absum = sum_k |term_k| per output element, passed only for
-    node-dimension / hub reductions (module docstring).  exact = float64 result: then also require the GPU to
-    be no further from it than twice the reference's own error (plus 1e-6 of the result scale)."""
-    got64, ref64 = got.astype(np.float64), ref.astype(np.float64)
-    err = np.abs(got64 - ref64)
-    scale = np.maximum(1.0, np.abs(ref64))
-    if absum is not None:
-        scale = np.maximum(scale, absum)
-    worst = float((err / (RTOL * scale)).max()) if err.size else 0.0
-    assert worst <= 1.0, f"{what}: max err/bound = {worst:.3f}"
-    if exact is not None and err.size:
-        e_gpu, e_ref = np.abs(got64 - exact).max(), np.abs(ref64 - exact).max()
-        assert e_gpu <= 2.0 * e_ref + 1e-6 * max(1.0, np.abs(exact).max()), \
-            f"{what}: GPU error vs float64 {e_gpu:.3e} exceeds reference's own {e_ref:.3e}"
 
 
 # ------------------------------------------------------------------ golden vectors (real reference)
@@ -1188,6 +1169,8 @@ def test_headline_config_whole_graph_vs_oracle(env):
         powf is 1 ulp from the correctly rounded value for a few degrees >= 1058) -- so s, norm and, end to end with the ORACLE'S OWN
         norm, both aggregations are BIT-EXACT: nothing tolerance-level is left on the aggregation path;
       * a caller-supplied table (CsrGraph.norm_from_pow_table) gives the same bits."""
+    # (the dense kernels that run at this size -- the three products, their fused epilogues, the row-streaming kernels -- are held to
+    # independent references past 2^31 element offsets in tests/test_gpu_large_offsets.py)
     ops, torch = env["ops"], env["torch"]
     n, e, F, abc, seed = 10_000_000, 100_000_000, 256, (0.57, 0.19, 0.19), 2
     srcd, dstd = ops.rmat_edges(seed, n, e, *abc)
@@ -1784,6 +1767,8 @@ def test_bn_stats_from_the_transform_vs_float64(env, n, offset):
     W = ops.uniform_pm1(2, (F, F), scale=F ** -0.5, device=env["dev"])
     H, m1, v1 = ops.linear_fwd_bn_stats(X, W)
     m2, v2 = ops.bn_stats(H)
+    # (HIP against HIP: H and the plain product at 10 M rows are held to exact and float64 references, and these statistics to the float64
+    # statistics of an EXACT H, in tests/test_gpu_large_offsets.py::test_transform_with_batchnorm_statistics_at_the_headline_size)
     assert torch.equal(H, ops.linear_fwd(X, W)), "the statistics ride along: H itself is the plain product's bits"
     del X
     m64 = torch.zeros(F, dtype=torch.float64, device=env["dev"])
