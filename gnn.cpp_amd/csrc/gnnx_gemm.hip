@@ -5,18 +5,25 @@
 // backward, dH.W and dH^T.X (operation.h:504-534); W^T / X^T / dH^T are never materialised (the reference
 // does: nn.cpp:207, operation.h:518-519,526-527).
 //
-// Tiling: 128 x 128 output tile per 256-thread workgroup (4 wavefronts as 2 x 2, each 64 x 64 = 2 x 2
-// MFMA tiles of 32 x 32, 64 accumulator VGPRs), K step 32.  Both operand tiles live in LDS k-major
-// ([k][m] and [k][n], row stride 130 words) so that an MFMA fragment read is 32 consecutive words per
-// half-wave (conflict-free ds_read_b32); K-contiguous operands (X, W) are transposed on the way in
-// (register staging, 16-byte global loads, b32 LDS writes at worst 2-way conflicted), k-major operands
-// (W in dH.W, both operands of dH^T.X) go in as they are.  Register-staged double buffering: tile t+1 is in
-// flight from HBM while tile t is multiplied.
-// transA = 1 reduces over the node dimension (K = millions, M x N = F_out x F_in tiny): split-K over
-// workgroups into fp32 slabs + an in-order slab reduction (deterministic; no float atomics).
+// Four kernels, and which shapes go where (gnnx_gemm_f32 and the fused entry points at the end of the file):
+//   * gemm_kernel -- generic, register-staged: any shape, any transposition, alpha / beta, ragged edges, split-K.  One output tile per
+//     workgroup (128 x 128, 128 x 256 or 256 x 256: pick_tile), v_mfma_f32_32x32x2_f32.  Both operand tiles live in LDS k-major
+//     ([k][m] and [k][n]) so that an MFMA fragment read is 32 consecutive words per half-wave (conflict-free ds_read_b32);
+//     K-contiguous operands (X, W) are transposed on the way in (16-byte global loads, b32 LDS writes at worst 2-way conflicted),
+//     k-major operands go in as they are.  Tile t+1 is in flight from HBM while tile t is multiplied.  It takes whatever the
+//     kernels below leave: small products, ragged last rows, beta != 0, unaligned operands, and the last K % 64 rows of dH^T.X.
+//   * gemm_stream_kernel -- resident, register-staged: the same tiles, but a workgroup walks the M-tiles of its column and the K-tile
+//     stream runs across them.  Tall row-parallel products of whole tiles that the LDS-DMA kernel does not take (K % 32 == 0 but
+//     K % 64 != 0, X.W^T without a workspace for W^T): launch_stream, which also says why 256-wide X.W^T stays on the generic kernel.
+//   * gemm_dma_kernel -- LDS-DMA, row-parallel (X.W^T, dH.W on >= 2048 rows, K % 64 == 0, N % 4 == 0, N >= 64, 16-byte aligned, beta == 0,
+//     B k-major -- for X.W^T the small W is transposed once into the workspace): operands go HBM -> LDS without passing through
+//     registers, v_mfma_f32_16x16x4_f32, resident workgroups of 256 x 256 (N % 256 == 0) or 256 x 128 (every other N, the last column
+//     tile guarded), the last partly filled round of a plain product on 256 x 128 or 128 x 128 tiles (launch_dma).  Its epilogues
+//     (Epi): plain, ReLU mask + column sums, BatchNorm sums, bf16 output, send slots.
+//   * gemm_dma_tn_kernel -- LDS-DMA, dW = dH^T.X (reduction over the node dimension: K = millions, M x N = F_out x F_in tiny, whole
+//     128 x 128 tiles, K >= 64 Ki): split-K over workgroups into fp32 slabs + an in-order slab reduction (deterministic; no float
+//     atomics), as the generic kernel does for every other transA = 1 shape.
 #include <atomic>
-#include <cstdlib>
-#include <cstring>
 
 #include "gnnx_common.h"
 
@@ -391,7 +398,7 @@ typedef __attribute__((address_space(3))) void gemm_lds_void_t;
 typedef float gemm_f32x4 __attribute__((ext_vector_type(4)));
 typedef float gemm_f32x4acc __attribute__((ext_vector_type(4)));
 
-// The loop carries (almost) NO vector-ALU instruction.  Measured on this chip (mfma_peak_kernel<mode>, 4 wavefronts per SIMD): beside the f32 MFMA every VALU instruction per MFMA
+// The loop carries (almost) NO vector-ALU instruction.  Measured on this chip (a register-only MFMA loop, 4 wavefronts per SIMD: DESIGN_HISTORY.md, "What bounds an f32 MFMA loop on this chip"): beside the f32 MFMA every VALU instruction per MFMA
 // costs 4-7 % of the matrix rate (1 / 2 / 4 per MFMA: 143 / 136 / 125 of 155 TFLOP/s), an LDS read 2-3 %, an s_nop nothing.
 // The register-staged kernels carry 2-3 VALU per MFMA (staging, fragment addresses), and so did two first LDS-DMA versions
 // (ds_read_b128 + element selects on 32x32x2, per-read address arithmetic on 16x16x4: loop-only 84-85 % of peak with loads
@@ -415,17 +422,16 @@ __device__ __forceinline__ void lds_read_b32(float &dst, uint32_t addr)
 // is the bench shape; 4 x 2 (512 threads, 256 x 128) takes 128-wide outputs (BASELINE configs[2]).  A k-major operand row of
 // 256 floats is one wave-instruction; one of 128 floats is half of one, so an instruction carries two rows (k and k + 16): see the
 // operand image below -- conflict-free fragment reads at both widths.
-template <int WM_, int WN_, int BK_ = 32>
+template <int WM_, int WN_>
 struct DmaGeo {
     static constexpr int WM = WM_, WN = WN_, NW = WM * WN, NT = 64 * NW;
-    static constexpr int BM = 64 * WM, BN = 64 * WN, BK = BK_;
-    static_assert(BK == 32 || BK == 16, "K-tile of 32 or 16");
+    static constexpr int BM = 64 * WM, BN = 64 * WN, BK = 32;
     // K-contiguous image: [BM rows][SLOTS slots of 16 B], slot s of row r holding k-group s ^ a_xor(r).  A 16-lane fragment read takes
-    // one word of 16 consecutive rows x 4 q: rows 64 / BK apart share their banks, so the XOR runs over row / (64 / BK).
+    // one word of 16 consecutive rows x 4 q: rows 2 apart share their banks, so the XOR runs over row / 2.
     static constexpr int SLOTS = BK / 4;                              // k-groups (16 B) per row of the image
     static constexpr int A_ROW_BYTES = BK * 4, A_BLOCK_BYTES = 16 * A_ROW_BYTES;   // one row; one MFMA block of 16 rows
-    static constexpr int A_ROWS_PER_INSTR = 1024 / A_ROW_BYTES;       // rows one 1-KiB wave-instruction brings (8 / 16)
-    static constexpr int a_xor(int row) { return (row / (64 / BK)) % SLOTS; }
+    static constexpr int A_ROWS_PER_INSTR = 1024 / A_ROW_BYTES;       // rows one 1-KiB wave-instruction brings (8)
+    static constexpr int a_xor(int row) { return (row / 2) % SLOTS; }
     static constexpr int A_STAGE_BYTES = BM * BK * 4;
     static constexpr int A_PER_WAVE = (BM / A_ROWS_PER_INSTR) / NW;   // 1-KiB wave-instructions per wavefront and K-tile
     // k-major operand image (B here, both operands of the TN kernel): one DMA wave-instruction = 1 KiB = one k row of 256 floats or
@@ -493,13 +499,6 @@ __device__ __forceinline__ void dma2_read_group(float (&a)[4], float (&b)[4], co
     GNNX_DMA2_STEP(ST, 6, 0, 1);                                          \
     GNNX_DMA2_WAIT(0, 1);                                                 \
     GNNX_DMA2_MFMA(1)
-#define GNNX_DMA2_KTILE16(ST)                                             \
-    dma2_read_group<GEO, ST, 0>(a[0], b[0], ak, bk);                     \
-    GNNX_DMA2_STEP(ST, 0, 0, 1);                                          \
-    GNNX_DMA2_STEP(ST, 1, 1, 0);                                          \
-    GNNX_DMA2_STEP(ST, 2, 0, 1);                                          \
-    GNNX_DMA2_WAIT(0, 1);                                                 \
-    GNNX_DMA2_MFMA(1)
 
 // LDS-DMA with a wave-uniform 64-bit base in SGPRs + a per-lane 32-bit BYTE offset (the saddr form: no 64-bit vector address
 // arithmetic, no zero-extended offset pairs to keep alive).  M0 = LDS destination of lane 0; it is compiler-reserved, so it is
@@ -511,48 +510,43 @@ __device__ __forceinline__ void dma_16B(uint32_t voff_bytes, const float *sbase,
                  : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_dst) : "memory");
 }
 
-#ifdef GNNX_EXPERIMENTS
-#define GNNX_ABLATE(bit) ((ablate & (bit)) != 0)  // timing only -- 1: no epilogue, 2: no operand loads after the first, 4: the epilogue's LDS round trip without its stores, 8: stores straight from the accumulators (16 rows x 64 B per instruction), 16: FUSE 4's list walk without its send stores, 32: non-temporal C stores, 64: non-temporal send stores
-#else
-#define GNNX_ABLATE(bit) false
-#endif
-// FUSE: the epilogue of the stacked layers' backward GEMM (SURVEY.md 2b "fused ops"): C = (A . B) masked
-// by the ReLU of the layer below (C[m][n] = 0 where Ymask[m][n] <= 0: Mask::_backward, reference operation.h:557-562) and
-// colsum_partial[blockIdx.y][n] = sum over this workgroup's rows of the masked C -- the bias gradient of the layer below
-// (Add::_backward -> sum_to_size, operation.h:114-128) -- so neither the unmasked gradient nor a separate column-sum pass
-// touches HBM.  The mask values are loaded with the same full-line pattern the stores use, under the LDS round trip.
-// FUSE == 2 (opt-in, gnnx_gemm_bn_stats_f32): the batch statistics of BatchNorm over the columns of C = X . W^T in the same
-// pass -- per-lane sums of d = c - shift[n] and d^2 (shift = row 0 of C: a sample value, so the single-pass variance
-// Q/M - (S/M)^2 cancels mildly), reduced per workgroup into [gridDim.y][2][N] partials and finished in double.  C itself is
-// stored unchanged.  Not the reference's two-pass arithmetic (nn.cpp:303,312): tolerance-level, next to the exact gnnx_bn_stats_f32.
-// FUSE == 4 (gnnx_gemm_nt_rows_to_slots_f32, the sharded step's transform): the halo PACK rides in the epilogue.  slots[row][8] lists
-// the send-buffer rows that row `row` of C goes to (-1 padded, packed at the front: gnnx_rows_to_slots_f32's table); every store
-// instruction of the epilogue (4 rows x 256 B, a quarter-wave per row) is repeated for each listed slot of its rows, from the same
-// registers -- the rows never come back from HBM to be packed.  A lane loads ONE dword of its row's eight (lane & 7) in front of the
-// LDS round trip and the quarter-wave shares them through ds_bpermute.  C itself is stored unchanged.
+// The epilogue of gemm_dma_kernel.
+//   kReluColsum (gnnx_gemm_relu_colsum_f32): the stacked layers' backward GEMM (SURVEY.md 2b "fused ops"): C = (A . B)
+//     masked by the ReLU of the layer below (C[m][n] = 0 where Ymask[m][n] <= 0: Mask::_backward, reference operation.h:557-562) and
+//     colsum_partial[blockIdx.y][n] = sum over this workgroup's rows of the masked C -- the bias gradient of the layer below
+//     (Add::_backward -> sum_to_size, operation.h:114-128) -- so neither the unmasked gradient nor a separate column-sum pass
+//     touches HBM.  The mask values are loaded with the same full-line pattern the stores use, under the LDS round trip.
+//   kBnSums (opt-in, gnnx_gemm_bn_stats_f32): the batch statistics of BatchNorm over the columns of C = X . W^T in the same
+//     pass -- per-lane sums of d = c - shift[n] and d^2 (shift = row 0 of C: a sample value, so the single-pass variance
+//     Q/M - (S/M)^2 cancels mildly), reduced per workgroup into [gridDim.y][2][N] partials and finished in double.  C itself is
+//     stored unchanged.  Not the reference's two-pass arithmetic (nn.cpp:303,312): tolerance-level, next to the exact gnnx_bn_stats_f32.
+//   kBf16 (gnnx_gemm_nt_bf16out_f32): C is stored as bf16, rounded to nearest even (ldc in bf16 elements).
+//   kSendSlots (gnnx_gemm_nt_rows_to_slots_f32, the sharded step's transform): the halo PACK rides in the epilogue.  slots[row][8] lists
+//     the send-buffer rows that row `row` of C goes to (-1 padded, packed at the front: gnnx_rows_to_slots_f32's table); every store
+//     instruction of the epilogue (4 rows x 256 B, a quarter-wave per row) is repeated for each listed slot of its rows, from the same
+//     registers -- the rows never come back from HBM to be packed.  A lane loads ONE dword of its row's eight (lane & 7) in front of the
+//     LDS round trip and the quarter-wave shares them through ds_bpermute.  C itself is stored unchanged.
+enum class Epi { kPlain, kReluColsum, kBnSums, kBf16, kSendSlots };
+
+// Epilogues that store rows and nothing per workgroup: ragged last rows are covered by one more, overlapping tile (gemm_dma_kernel:
+// row0_of) and the last, partly filled round of tiles may go to a launch of its own (launch_dma).  The column-sum epilogues index
+// their partials by workgroup and take whole tiles only; so does the bf16 output (its caller rounds the ragged rows itself).
+constexpr bool epi_covers_rows(Epi e) { return e == Epi::kPlain || e == Epi::kSendSlots; }
+
 struct GemmFuse {
-    const float *ymask;      // FUSE 1: [M][N] forward output of the layer below (ld ldy), mask = ymask > 0; FUSE 2: shift[N]
-    int64_t ldy;             // FUSE 4: ld of `send` (elements)
-    float *colsum_partial;   // FUSE 1: [gridDim.y][N]; FUSE 2: [gridDim.y][2][N]; FUSE 4: the send buffer
-    const int32_t *slots;    // FUSE 4: [M][8]
+    const float *ymask;     // kReluColsum: [M][N] forward output of the layer below (ld ldy), mask = ymask > 0; kBnSums: shift[N]
+    int64_t ldy;             // kSendSlots: ld of `send` (elements)
+    float *colsum_partial;   // kReluColsum: [gridDim.y][N]; kBnSums: [gridDim.y][2][N]; kSendSlots: the send buffer
+    const int32_t *slots;    // kSendSlots: [M][8]
 };
 
 // NG (N guard): the last column tile is narrower than BN (N % 4 == 0): lanes whose 16 bytes lie past column N neither load B
 // (their LDS slots keep whatever they held: the products of those columns are garbage and stay in registers) nor store C nor
 // contribute column sums.
-// BK_ = 16: half the K-tile, so that TWO workgroups are resident per CU (4 wavefronts per SIMD as before): the C-store epilogue and
-// the K-tile barriers of one run under the MFMAs of the other.
-// DEFER (EXPERIMENTS build only; plain products on the 256 x 128 tile, K >= 128): the C tile does not leave through an epilogue.  Eight
-// wavefronts per CU leave every wavefront 256 VGPRs, twice what the tile needs, so the finished accumulators are parked in a second
-// set of 64 registers and stored STRAIGHT from there -- 16 rows x 64 bytes per instruction, one block row in front of each of the next
-// tile's first four K-tiles -- while the matrix pipe works on that tile.  Same bits; measured slower than the LDS-staged epilogue
-// (launch_dma_geo), kept as the record of that experiment.
-template <int WM_, int WN_, int FUSE, bool NG, int BK_ = 32, bool DEFER = false>
-__global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_kernel(GemmArgs g, int64_t m_tiles, int ablate, GemmFuse fu)
+template <int WM_, int WN_, Epi EPI, bool NG>
+__global__ __launch_bounds__(64 * WM_ * WN_, 1) void gemm_dma_kernel(GemmArgs g, GemmFuse fu, int64_t m_tiles)
 {
-    static_assert(!DEFER || (FUSE == 0 && WM_ * WN_ <= 8 && BK_ == 32), "deferred stores: plain product, at most two wavefronts per SIMD");
-    (void)ablate;
-    using GEO = DmaGeo<WM_, WN_, BK_>;
+    using GEO = DmaGeo<WM_, WN_>;
     constexpr int BM = GEO::BM, BN = GEO::BN, BK = GEO::BK, NW = GEO::NW;
     constexpr int APW = GEO::A_PER_WAVE, BPW = GEO::B_PER_WAVE;
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];  // [2][A stage], then [2][B stage]
@@ -626,31 +620,18 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
                            (uint32_t)((q ^ (r16 & 3)) << 4);   // + 64 j
     // reader: lane L reads 16 B at byte L*16 of a piece = row L/16, 16-B column L%16 (stored at column ^ (row & 3))
     const uint32_t ep_rd = (uint32_t)((lane >> 4) * 256) + (uint32_t)(((lane & 15) ^ (lane >> 4)) << 4);
-    constexpr int ES = FUSE == 3 ? 2 : 4;   // bytes per stored element (FUSE 3: C is bf16, ldc in bf16 elements)
+    constexpr int ES = EPI == Epi::kBf16 ? 2 : 4;   // bytes per stored element (bf16: ldc in bf16 elements)
     const uint32_t offc = (uint32_t)((wm * 64 + (lane >> 4)) * g.ldc + wn * 64 + 4 * (lane & 15)) * (uint32_t)ES;  // bytes: row L/16, col 4 (L%16)
 
     gemm_f32x4acc acc[4][4];
-    gemm_f32x4acc pend[DEFER ? 4 : 1][DEFER ? 4 : 1];   // DEFER: the previous tile's accumulators (x alpha), on their way out
-    char *pend_tile = nullptr;                          // ... and where they go (nullptr: nothing pending)
-    const uint32_t offd = (uint32_t)((wm * 64 + r16) * g.ldc + wn * 64 + 4 * q) * 4u;   // direct store: row r16, columns 4 q .. of block (i, j)
-    auto flush_row = [&](int i) {   // block row i of the pending tile: 4 stores of 16 rows x 64 bytes
-        if constexpr (DEFER) {
-            if (pend_tile) {
-                char *crow = pend_tile + (int64_t)(16 * i) * g.ldc * 4;
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (!NG || wn * 64 + 16 * j + 4 * q + 4 <= n_left) *reinterpret_cast<gemm_f32x4acc *>(crow + offd + 64 * j) = pend[i][j];
-            }
-        }
-    };
     float a[2][4], b[2][4];
-    gemm_f32x4acc csum = {0.f, 0.f, 0.f, 0.f};   // FUSE: column sums of this lane's 4 columns over every row it stores
-    gemm_f32x4acc csq = {0.f, 0.f, 0.f, 0.f};    // FUSE 2: sums of squares (of the shifted values)
+    gemm_f32x4acc csum = {0.f, 0.f, 0.f, 0.f};   // kReluColsum, kBnSums: column sums of this lane's 4 columns over every row it stores
+    gemm_f32x4acc csq = {0.f, 0.f, 0.f, 0.f};    // kBnSums: sums of squares (of the shifted values)
     gemm_f32x4acc shift4 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (FUSE == 2)
+    if constexpr (EPI == Epi::kBnSums)
         if (okc) shift4 = *reinterpret_cast<const gemm_f32x4acc *>(fu.ymask + n0 + wn * 64 + 4 * (lane & 15));
-    const uint32_t offy = FUSE == 1 ? (uint32_t)((wm * 64 + (lane >> 4)) * fu.ldy + wn * 64 + 4 * (lane & 15)) * 4u : 0u;
-    // FUSE 4: the tile's slot lists (BM rows x 32 B) come into LDS by DMA with the tile's first K-tile -- two buffers behind the
+    const uint32_t offy = EPI == Epi::kReluColsum ? (uint32_t)((wm * 64 + (lane >> 4)) * fu.ldy + wn * 64 + 4 * (lane & 15)) * 4u : 0u;
+    // kSendSlots: the tile's slot lists (BM rows x 32 B) come into LDS by DMA with the tile's first K-tile -- two buffers behind the
     // operand stages, alternating per tile: a wavefront that is already in the next tile must not overwrite lists its neighbours
     // still read (they are at most one barrier apart).  The epilogue must not LOAD from global memory: vmcnt counts loads and stores
     // in order, so waiting for a load issued behind the stores of the rows before it is waiting for those stores to be acknowledged
@@ -658,7 +639,7 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
     constexpr uint32_t SLOT_BUF = (uint32_t)BM * 32u;
     const uint32_t slot_lds = lds0 + (uint32_t)GEO::LDS_BYTES;
     const uint32_t offs = (uint32_t)((wm * 64 + (lane >> 4)) * 8 + (lane & 7)) * 4u;   // bytes into the tile's slot lists
-    char *send_col = FUSE == 4 ? reinterpret_cast<char *>(fu.colsum_partial + n0 + wn * 64 + 4 * (lane & 15)) : nullptr;
+    char *send_col = EPI == Epi::kSendSlots ? reinterpret_cast<char *>(fu.colsum_partial + n0 + wn * 64 + 4 * (lane & 15)) : nullptr;
     uint32_t sbuf = 0;
     int64_t mt = blockIdx.y;
     if (mt < m_tiles) issue(0, mt, 0);
@@ -672,64 +653,25 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
             for (int j = 0; j < 4; j++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) acc[i][j][r] = 0.f;
-        if constexpr (FUSE == 4) {   // one 1-KiB wave-instruction per 32 rows; lands before the barrier of the first K-tile
+        if constexpr (EPI == Epi::kSendSlots) {   // one 1-KiB wave-instruction per 32 rows; lands before the barrier of the first K-tile
             sbuf ^= SLOT_BUF;
             if (wave < BM / 32)
                 dma_16B((uint32_t)lane * 16u, reinterpret_cast<const float *>(fu.slots + row0_of(mt) * 8 + wave * 256), slot_lds + sbuf + (uint32_t)wave * 1024u);
         }
         for (int64_t k0 = 0; k0 < g.K; k0 += 2 * BK) {
             const bool last = k0 + 2 * BK >= g.K;
-            if (!GNNX_ABLATE(2)) issue(1, mt, k0 + BK);   // K % 64 == 0: the odd K-tile of this trip always exists
-            if constexpr (DEFER) {   // the pending tile's block rows 0 / 2 (first two trips: K >= 128) leave under this K-tile's MFMAs
-                if (k0 == 0) flush_row(0);
-                else if (k0 == 2 * BK) flush_row(2);
-            }
-            if constexpr (BK == 32) { GNNX_DMA2_KTILE(0); } else { GNNX_DMA2_KTILE16(0); }
+            issue(1, mt, k0 + BK);   // K % 64 == 0: the odd K-tile of this trip always exists
+            GNNX_DMA2_KTILE(0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if ((!last || mt_next < m_tiles) && !GNNX_ABLATE(2)) issue(0, last ? mt_next : mt, last ? 0 : k0 + 2 * BK);
-            if constexpr (DEFER) {
-                if (k0 == 0) flush_row(1);
-                else if (k0 == 2 * BK) flush_row(3);
-            }
-            if constexpr (BK == 32) { GNNX_DMA2_KTILE(1); } else { GNNX_DMA2_KTILE16(1); }
+            if (!last || mt_next < m_tiles) issue(0, last ? mt_next : mt, last ? 0 : k0 + 2 * BK);
+            GNNX_DMA2_KTILE(1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-        }
-        if (GNNX_ABLATE(1)) {
-            float s_ = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) s_ += acc[i][j][r];
-            if (s_ == 1.2345e30f) g.C[0] = s_;
-            continue;
         }
         const float alpha = g.alpha;
         char *ctile = reinterpret_cast<char *>(g.C) + (row0_of(mt) * g.ldc + n0) * ES;
-        if constexpr (DEFER) {   // park the tile (every block row of the tile before it left during this tile's first four K-tiles)
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) pend[i][j] = alpha != 1.0f ? acc[i][j] * alpha : acc[i][j];
-            pend_tile = ctile;
-            continue;
-        }
-        if constexpr (FUSE == 0 && !NG) {
-            if (GNNX_ABLATE(8)) {   // A/B: straight from the accumulators, 16 rows x 64 B per store instruction, no LDS
-                const uint32_t offd = (uint32_t)((wm * 64 + r16) * g.ldc + wn * 64 + 4 * q) * 4u;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    char *crow = ctile + (int64_t)(16 * i) * g.ldc * 4;
-#pragma unroll
-                    for (int j = 0; j < 4; j++) *reinterpret_cast<gemm_f32x4acc *>(crow + offd + 64 * j) = acc[i][j] * alpha;
-                }
-                continue;
-            }
-        }
-        const char *ytile = FUSE == 1 ? reinterpret_cast<const char *>(fu.ymask + row0_of(mt) * fu.ldy + n0) : nullptr;
+        const char *ytile = EPI == Epi::kReluColsum ? reinterpret_cast<const char *>(fu.ymask + row0_of(mt) * fu.ldy + n0) : nullptr;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
 #pragma unroll
@@ -739,7 +681,7 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
                 asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(ep_wr), "v"(v), "i"(64 * j) : "memory");
             }
             gemm_f32x4acc ym[4] = {};
-            if constexpr (FUSE == 1) {   // issued behind the LDS writes (block row i's accumulators are dead by now: their registers
+            if constexpr (EPI == Epi::kReluColsum) {   // issued behind the LDS writes (block row i's accumulators are dead by now: their registers
                                     // take the mask values) and in flight during the LDS round trip below
                 const char *yrow = ytile + (int64_t)(16 * i) * fu.ldy * 4;
 #pragma unroll
@@ -747,12 +689,12 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
                     if (okc) ym[p] = *reinterpret_cast<const gemm_f32x4acc *>(yrow + (int64_t)(4 * p) * fu.ldy * 4 + offy);
             }
             int32_t sl[4] = {-1, -1, -1, -1};
-            if constexpr (FUSE == 4) {   // dword (lane & 7) of the slot list of row 16 i + 4 p + lane / 16, from the tile's lists in LDS
+            if constexpr (EPI == Epi::kSendSlots) {   // dword (lane & 7) of the slot list of row 16 i + 4 p + lane / 16, from the tile's lists in LDS
 #pragma unroll
                 for (int p = 0; p < 4; p++)
                     asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(sl[p]) : "v"(slot_lds + sbuf + offs), "i"((16 * i + 4 * p) * 32) : "memory");
             }
-            if constexpr (FUSE == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sl[0]), "+v"(sl[1]), "+v"(sl[2]), "+v"(sl[3])::"memory");
+            if constexpr (EPI == Epi::kSendSlots) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sl[0]), "+v"(sl[1]), "+v"(sl[2]), "+v"(sl[3])::"memory");
             else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             gemm_f32x4acc o[4];
 #pragma unroll
@@ -761,31 +703,25 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
             char *crow = ctile + (int64_t)(16 * i) * g.ldc * ES;   // wave-uniform
 #pragma unroll
             for (int p = 0; p < 4; p++) {
-                if constexpr (FUSE == 1) {
+                if constexpr (EPI == Epi::kReluColsum) {
 #pragma unroll
                     for (int c = 0; c < 4; c++) o[p][c] = ym[p][c] > 0.f ? o[p][c] : 0.f;
                     csum += o[p];
                 }
-                if constexpr (FUSE == 2) {
+                if constexpr (EPI == Epi::kBnSums) {
                     const gemm_f32x4acc d = o[p] - shift4;
                     csum += d;
                     csq += d * d;
                 }
-                if constexpr (FUSE == 3) {   // round to nearest even, as gnnx_f32_to_bf16: 8 bytes per lane, 128-byte row segments
+                if constexpr (EPI == Epi::kBf16) {   // round to nearest even, as gnnx_f32_to_bf16: 8 bytes per lane, 128-byte row segments
                     union { __bf16 h[4]; uint2 u; } ob;
                     ob.h[0] = (__bf16)o[p][0];
                     ob.h[1] = (__bf16)o[p][1];
                     ob.h[2] = (__bf16)o[p][2];
                     ob.h[3] = (__bf16)o[p][3];
                     if (okc) *reinterpret_cast<uint2 *>(crow + (int64_t)(4 * p) * g.ldc * ES + offc) = ob.u;
-                } else {
-                    if (GNNX_ABLATE(4)) {   // A/B: the LDS round trip without the stores
-                        asm volatile("" ::"v"(o[p]));
-                    } else if (GNNX_ABLATE(32)) {   // A/B: C leaves with the non-temporal policy
-                        if (okc) __builtin_nontemporal_store(o[p], reinterpret_cast<gemm_f32x4acc *>(crow + (int64_t)(4 * p) * g.ldc * ES + offc));
-                    } else if (okc) *reinterpret_cast<gemm_f32x4acc *>(crow + (int64_t)(4 * p) * g.ldc * ES + offc) = o[p];
-                }
-                if constexpr (FUSE == 4) {
+                } else if (okc) *reinterpret_cast<gemm_f32x4acc *>(crow + (int64_t)(4 * p) * g.ldc * ES + offc) = o[p];
+                if constexpr (EPI == Epi::kSendSlots) {
                     // the same 4 rows x 256 B once more per listed slot.  Lists are packed at the front, so the number of rounds the
                     // wavefront needs is the longest list of its four rows: one ballot, no data-dependent exit
                     const uint64_t has = __ballot(sl[p] >= 0);
@@ -794,15 +730,6 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
                     for (int k = 0; k < rounds; k += 2) {   // two lists entries per trip: the second bpermute is in flight under the first store
                         const int32_t s0 = __builtin_amdgcn_ds_bpermute(((lane & 48) + k) << 2, sl[p]);
                         const int32_t s1 = __builtin_amdgcn_ds_bpermute(((lane & 48) + k + 1) << 2, sl[p]);   // k + 1 <= 7
-                        if (GNNX_ABLATE(16)) {   // A/B: the list walk without its stores
-                            asm volatile("" ::"v"(s0), "v"(s1));
-                            continue;
-                        }
-                        if (GNNX_ABLATE(64)) {   // A/B: the send rows leave with the non-temporal policy (nothing on this GPU reads them again)
-                            if (s0 >= 0 && okc) __builtin_nontemporal_store(o[p], reinterpret_cast<gemm_f32x4acc *>(send_col + (int64_t)s0 * fu.ldy * 4));
-                            if (s1 >= 0 && okc) __builtin_nontemporal_store(o[p], reinterpret_cast<gemm_f32x4acc *>(send_col + (int64_t)s1 * fu.ldy * 4));
-                            continue;
-                        }
                         if (s0 >= 0 && okc) *reinterpret_cast<gemm_f32x4acc *>(send_col + (int64_t)s0 * fu.ldy * 4) = o[p];
                         if (s1 >= 0 && okc) *reinterpret_cast<gemm_f32x4acc *>(send_col + (int64_t)s1 * fu.ldy * 4) = o[p];
                     }
@@ -810,13 +737,7 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
             }
         }
     }
-    if constexpr (DEFER) {   // the last tile of this workgroup
-        flush_row(0);
-        flush_row(1);
-        flush_row(2);
-        flush_row(3);
-    }
-    if constexpr (FUSE == 1 || FUSE == 2) {
+    if constexpr (EPI == Epi::kReluColsum || EPI == Epi::kBnSums) {
         // column sums of the workgroup: lanes with equal (lane & 15) in the WM wavefronts of a column group wn hold the same 4
         // columns.  Everything is parked in LDS (the operand stages are dead: every DMA was waited for, the last K-tile
         // ended with a barrier) and added in a fixed order: wm 0..WM-1, lane group 0..3.
@@ -829,10 +750,10 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
             gemm_f32x4acc sum = {0.f, 0.f, 0.f, 0.f};
             for (int w = 0; w < GEO::WM; w++)
                 for (int lg = 0; lg < 4; lg++) sum += red[(w * GEO::WN + cg) * 64 + lg * 16 + c16];
-            float *prow = fu.colsum_partial + (int64_t)blockIdx.y * (FUSE == 2 ? 2 : 1) * g.N;
+            float *prow = fu.colsum_partial + (int64_t)blockIdx.y * (EPI == Epi::kBnSums ? 2 : 1) * g.N;
             *reinterpret_cast<gemm_f32x4acc *>(prow + n0 + 4 * tid) = sum;
         }
-        if constexpr (FUSE == 2) {   // the same for the squares
+        if constexpr (EPI == Epi::kBnSums) {   // the same for the squares
             __syncthreads();
             red[wave * 64 + lane] = csq;
             __syncthreads();
@@ -846,204 +767,6 @@ __global__ __launch_bounds__(64 * WM_ * WN_, BK_ == 16 ? 4 : 1) void gemm_dma_ke
         }
     }
 }
-
-#ifdef GNNX_EXPERIMENTS
-// (EXPERIMENTS build only, GNNX_GEMM_W128=1: a record of what does NOT lift the 128-wide products -- DESIGN.md section 4.2.  Same bits
-// as gemm_dma_kernel<4, 2>; 10 M x 128 x 128: 2.83 ms against 2.82.  With its stores aimed at L2-resident rows 2.54, with its loads
-// 2.52, with both 2.45 = 0.85 of the matrix peak: the loop's nine LDS reads per eight MFMAs cost what the barriers cost the
-// 256 x 128 tile.  A first version -- strips of 32 rows, ten reads per sixteen MFMAs, two stages -- ran 2.70 against 2.76.)
-// ---- 128-wide products without a barrier: C[M][128] = A[M][128] . B[128][128] (K = N = 128: BASELINE configs[2]) ----------------------
-// At this width bytes and flops are nearly balanced and a K-tile of gemm_dma_kernel<4, 2> lasts only 3.4 us: its one-K-tile prefetch
-// distance no longer covers an HBM round trip once the C stores share the memory pipeline (loop alone 0.90 of the matrix peak, with
-// loads 0.89, with loads AND stores 0.74), and `s_waitcnt vmcnt(0)` behind a tile's first K-tile waits for the previous tile's stores
-// to be acknowledged, because vmcnt counts loads and stores in one order.  Here
-//   * W (64 KB) is loaded into LDS once and stays (k-major operand image, 68 KB); a wavefront owns a STRIP of 16 rows x all 128
-//     columns and brings its own operand rows into its own ring of four 2-KB stages: after the barrier behind the load of W no
-//     wavefront waits for another, and the two wavefronts of a SIMD drift apart (one's epilogue under the other's MFMAs);
-//   * the ring is THREE K-tiles ahead of the multiply (stage = K-tile index: a strip is four K-tiles), and every wait is counted:
-//     `vmcnt(12)` / `vmcnt(4)` leave the two younger K-tiles (2 DMA instructions each) AND the last strip's 8 stores in flight -- no
-//     wait ever waits for a store (first strip of a wavefront: no stores yet, vmcnt(4));
-//   * same MFMA chain per output element as gemm_dma_kernel (D = mfma(b, a) over k = 0 .. 127 in steps of 4): same bits;
-//   * per k-group 1 a-fragment + 8 b-fragments (one ds_read_b32 each, precomputed addresses + immediates) feed 8 MFMAs;
-//   * C leaves through a 2-KB staging area of the wavefront's own, 16 rows x 32 columns at a time: a store instruction covers
-//     8 rows x 128 B (whole lines);
-//   * loads are never predicated: past the last strip the ring re-reads the last strip (so that the counts above stay exact), and
-//     the last strip starts at M - 16, overlapping its neighbour (same values stored twice).
-struct W128 {
-    static constexpr int NW = 8, NT = 64 * NW, ROWS = 16;                    // wavefronts per workgroup, rows per strip
-    using G = DmaGeo<4, 2, 32>;                                              // (the operand images of the 256 x 128 tile: BK = 32, BN = 128)
-    static constexpr int B_TILE_BYTES = G::B_STAGE_BYTES;                    // one K-tile of W: 16 pieces of 272 words
-    static constexpr int B_BYTES = 4 * B_TILE_BYTES;                         // K = 128
-    static constexpr int A_STAGE_BYTES = ROWS * 32 * 4;                      // 2 KB
-    static constexpr int WAVE_BYTES = 4 * A_STAGE_BYTES + 2048;              // ring of four stages + C staging
-    static constexpr int LDS_BYTES = B_BYTES + NW * WAVE_BYTES;              // 68 KB + 80 KB
-};
-
-template <int KT, int KG>
-__device__ __forceinline__ void w128_read_group(float &a, float (&b)[8], const uint32_t (&ak)[8], uint32_t bk_lo, uint32_t bk_hi)
-{
-    lds_read_b32<KT * W128::A_STAGE_BYTES>(a, ak[KG]);
-    // K-tiles 0, 1 through bk_lo, 2, 3 through bk_hi (= bk_lo + 2 K-tiles): the ds_read offset is a 16-bit immediate
-    constexpr int SB = (KT & 1) * W128::B_TILE_BYTES + W128::G::kgroup_off(128, KG);
-    const uint32_t bk = KT < 2 ? bk_lo : bk_hi;
-    lds_read_b32<SB + 0 * 64>(b[0], bk);
-    lds_read_b32<SB + 1 * 64>(b[1], bk);
-    lds_read_b32<SB + 2 * 64>(b[2], bk);
-    lds_read_b32<SB + 3 * 64>(b[3], bk);
-    lds_read_b32<SB + 4 * 64>(b[4], bk);
-    lds_read_b32<SB + 5 * 64>(b[5], bk);
-    lds_read_b32<SB + 6 * 64>(b[6], bk);
-    lds_read_b32<SB + 7 * 64>(b[7], bk);
-}
-
-#define GNNX_W128_WAIT(N, set)                                                                                                      \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(a[set]), "+v"(b[set][0]), "+v"(b[set][1]), "+v"(b[set][2]), "+v"(b[set][3]),      \
-                 "+v"(b[set][4]), "+v"(b[set][5]), "+v"(b[set][6]), "+v"(b[set][7])::"memory")
-#define GNNX_W128_MFMA(set) \
-    _Pragma("unroll") for (int j_ = 0; j_ < 8; j_++) acc[j_] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[set][j_], a[set], acc[j_], 0, 0, 0)
-#define GNNX_W128_STEP(KT, KG, cur, nxt)                                           \
-    w128_read_group<KT, KG + 1>(a[nxt], b[nxt], ak, bk_lo, bk_hi);                 \
-    GNNX_W128_WAIT(9, cur);                                                        \
-    GNNX_W128_MFMA(cur)
-#define GNNX_W128_KTILE(KT)                                                        \
-    w128_read_group<KT, 0>(a[0], b[0], ak, bk_lo, bk_hi);                          \
-    GNNX_W128_STEP(KT, 0, 0, 1);                                                   \
-    GNNX_W128_STEP(KT, 1, 1, 0);                                                   \
-    GNNX_W128_STEP(KT, 2, 0, 1);                                                   \
-    GNNX_W128_STEP(KT, 3, 1, 0);                                                   \
-    GNNX_W128_STEP(KT, 4, 0, 1);                                                   \
-    GNNX_W128_STEP(KT, 5, 1, 0);                                                   \
-    GNNX_W128_STEP(KT, 6, 0, 1);                                                   \
-    GNNX_W128_WAIT(0, 1);                                                          \
-    GNNX_W128_MFMA(1)
-
-__global__ __launch_bounds__(W128::NT, 1) void gemm_w128_kernel(GemmArgs g, int64_t n_strips, int ablate)
-{
-    (void)ablate;
-    using G = W128::G;
-    extern __shared__ __attribute__((aligned(16))) float lds_raw[];   // [W: 4 K-tiles][per wavefront: ring of 4 stages, C staging]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int q = lane >> 4, r16 = lane & 15;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(gemm_lds_void_t *)lds_raw;
-    const uint32_t a0 = lds0 + (uint32_t)W128::B_BYTES + (uint32_t)wave * (uint32_t)W128::WAVE_BYTES;   // this wavefront's stage 0
-
-    // ---- W into LDS, once: K-tile t = 16 wave-instructions (two k rows of 128 floats each: rows I and I + 16 of the K-tile)
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-        const int inst = wave + W128::NW * u;   // 0 .. 63: K-tile inst / 16, instruction inst % 16
-        const int t = inst >> 4, I = inst & 15;
-        const int krow = 32 * t + G::krow_of(128, I, lane);
-        dma_16B((uint32_t)(krow * g.ldb + 4 * (lane % 32)) * 4u, g.B, lds0 + (uint32_t)(t * W128::B_TILE_BYTES + I * G::B_PIECE_BYTES));
-    }
-    // ---- this wavefront's operand DMA: instruction u of a K-tile brings rows 8 u .. 8 u + 7 (128 bytes each) of the strip
-    uint32_t offa[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int row = 8 * u + lane / 8;
-        const int kg = (lane % 8) ^ G::a_xor(row);
-        offa[u] = (uint32_t)(row * g.lda + 4 * kg) * 4u;
-    }
-    const int64_t last_row0 = g.M - W128::ROWS;
-    const int64_t last_strip = n_strips - 1;
-    auto row0_of = [&](int64_t s) { return s * W128::ROWS <= last_row0 ? s * W128::ROWS : last_row0; };
-    auto issue = [&](int kt, int64_t strip) {   // K-tile kt of `strip` (clamped to the last strip: never predicated) into stage kt
-        const float *abase = g.A + row0_of(GNNX_ABLATE(2) ? 0 : (strip < last_strip ? strip : last_strip)) * g.lda + 32 * kt;   // A/B 2: every strip re-reads strip 0 (L2 hits)
-        if (GNNX_ABLATE(4)) {   // A/B 4 (timing only, wrong products): the same bytes as ONE contiguous 2-KB run per K-tile instead of 16 row slices of 128 B
-            const float *cbase = g.A + row0_of(strip < last_strip ? strip : last_strip) * g.lda + 512 * kt;
-            dma_16B((uint32_t)lane * 16u, cbase, a0 + (uint32_t)(kt * W128::A_STAGE_BYTES));
-            dma_16B((uint32_t)lane * 16u + 1024u, cbase, a0 + (uint32_t)(kt * W128::A_STAGE_BYTES + 1024));
-            return;
-        }
-        dma_16B(offa[0], abase, a0 + (uint32_t)(kt * W128::A_STAGE_BYTES));
-        dma_16B(offa[1], abase, a0 + (uint32_t)(kt * W128::A_STAGE_BYTES + 1024));
-    };
-    // ---- fragment addresses
-    uint32_t ak[8];
-    {
-        const uint32_t xa = (uint32_t)(G::a_xor(r16) << 4);
-#pragma unroll
-        for (int kg = 0; kg < 8; kg++) ak[kg] = a0 + (uint32_t)(r16 * G::A_ROW_BYTES + 4 * q) + (((uint32_t)kg << 4) ^ xa);
-    }
-    const uint32_t bk_lo = lds0 + (uint32_t)(q * G::KPIECE_BYTES + r16 * 4);
-    const uint32_t bk_hi = bk_lo + 2u * W128::B_TILE_BYTES;
-    // ---- C staging: 16 rows x 32 columns (128 B per row); 16-byte column c of row r is stored at c ^ ((r >> 1) & 7): conflict-free
-    // for the writers (16 rows of one 16-byte column) and the readers (8 columns of two rows)
-    const uint32_t ep = a0 + 4u * W128::A_STAGE_BYTES;
-    const uint32_t ep_wr0 = ep + (uint32_t)(r16 * 128) + (uint32_t)(((uint32_t)q ^ (((uint32_t)r16 >> 1) & 7u)) << 4);         // block j even
-    const uint32_t ep_wr1 = ep + (uint32_t)(r16 * 128) + (uint32_t)(((uint32_t)(4 + q) ^ (((uint32_t)r16 >> 1) & 7u)) << 4);   // block j odd
-    const int rr = lane >> 3, rc = lane & 7;   // reader: row rr (+ 8 p), 16-byte column rc
-    const uint32_t ep_rd0 = ep + (uint32_t)(rr * 128) + (uint32_t)(((uint32_t)rc ^ (((uint32_t)rr >> 1) & 7u)) << 4);
-    const uint32_t ep_rd1 = ep + (uint32_t)((rr + 8) * 128) + (uint32_t)(((uint32_t)rc ^ (((uint32_t)(rr + 8) >> 1) & 7u)) << 4);
-    const uint32_t offc = (uint32_t)(rr * g.ldc + 4 * rc) * 4u;   // row rr, columns 4 rc .. of a 32-column group
-
-    const int64_t stride = (int64_t)gridDim.x * W128::NW;
-    int64_t strip = (int64_t)blockIdx.x * W128::NW + wave;
-    issue(0, strip);
-    issue(1, strip);
-    issue(2, strip);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // W and K-tile 0 have landed (K-tiles 1, 2 may be on their way)
-    __syncthreads();   // W is complete in LDS (the only barrier of the kernel)
-    gemm_f32x4acc acc[8];
-    float a[2], b[2][8];
-    const float alpha = g.alpha;
-    // one strip: K-tile kt is multiplied while K-tiles kt + 1 .. kt + 3 (the last ones: the NEXT strip's first) are in flight or landed.
-    // STORES = the number of store instructions of the previous strip's epilogue that may still be in flight (0 on a wavefront's
-    // first strip, else 8): the waits count them so that they are never waited for.
-    auto strip_body = [&](auto stores_tag, int64_t cur, int64_t next) {
-        constexpr int STORES = decltype(stores_tag)::value;
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) acc[j][r] = 0.f;
-        issue(3, cur);
-        GNNX_W128_KTILE(0);
-        // K-tile 1 must have landed; younger: K-tiles 2, 3 (4 instructions) and, issued between K-tile 1's and 2's DMA, the last strip's stores
-        if constexpr (STORES == 8) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        issue(0, next);
-        GNNX_W128_KTILE(1);
-        if constexpr (STORES == 8) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");   // K-tile 2; younger: 3, next 0, and the stores (behind K-tile 2's DMA)
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        issue(1, next);
-        GNNX_W128_KTILE(2);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // K-tile 3; younger: next 0, next 1 (the last strip's stores are older than K-tile 3's DMA)
-        issue(2, next);
-        GNNX_W128_KTILE(3);
-        // ---- epilogue: four groups of 32 columns through the staging area
-        char *ctile = reinterpret_cast<char *>(g.C + row0_of(cur) * g.ldc);
-#pragma unroll
-        for (int c4 = 0; c4 < 4; c4++) {
-            gemm_f32x4acc v0 = acc[2 * c4], v1 = acc[2 * c4 + 1];
-            if (alpha != 1.0f) {
-                v0 = v0 * alpha;
-                v1 = v1 * alpha;
-            }
-            asm volatile("ds_write_b128 %0, %1" ::"v"(ep_wr0), "v"(v0) : "memory");
-            asm volatile("ds_write_b128 %0, %1" ::"v"(ep_wr1), "v"(v1) : "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            gemm_f32x4acc o0, o1;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(o0) : "v"(ep_rd0) : "memory");
-            asm volatile("ds_read_b128 %0, %1" : "=v"(o1) : "v"(ep_rd1) : "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(o0), "+v"(o1)::"memory");
-            char *cg = (GNNX_ABLATE(1) ? reinterpret_cast<char *>(g.C + (int64_t)wave * 16 * g.ldc) : ctile) + 128 * c4;   // wave-uniform: columns 32 c4 .. (A/B 1: every strip stores over the same rows: L2 absorbs them)
-            *reinterpret_cast<gemm_f32x4acc *>(cg + offc) = o0;
-            *reinterpret_cast<gemm_f32x4acc *>(cg + (int64_t)8 * g.ldc * 4 + offc) = o1;
-        }
-        // the next strip's K-tile 0 must have landed; younger: its K-tiles 1, 2 (4 instructions) and the 8 stores above
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    };
-    if (strip < n_strips) {
-        strip_body(std::integral_constant<int, 0>{}, strip, strip + stride);
-        for (strip += stride; strip < n_strips; strip += stride) strip_body(std::integral_constant<int, 8>{}, strip, strip + stride);
-    }
-}
-#undef GNNX_W128_KTILE
-#undef GNNX_W128_STEP
-#undef GNNX_W128_MFMA
-#undef GNNX_W128_WAIT
-#endif  // GNNX_EXPERIMENTS
 
 // Split-K partials -> C in a FIXED order (deterministic, no float atomics): 8 lane groups each sum a contiguous eighth of the
 // slabs for 32 consecutive elements (128-byte coalesced reads), then the eight partial sums are combined left to right.
@@ -1074,90 +797,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *slab, i
     }
 }
 
-#ifdef GNNX_EXPERIMENTS
-// Calibration: register-only MFMA loop (4 independent accumulators per wavefront, no memory traffic) -- what the
-// fp32 matrix pipe sustains on THIS chip at the clock it holds under load; the GEMM's fraction of that is the honest
-// utilisation figure next to the 157.3 TFLOP/s datasheet peak.
-template <int mode>
-__global__ __launch_bounds__(256) void mfma_peak_kernel(int iters, float *sink)
-{
-    __shared__ float lds[4096];
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][r] = (float)(threadIdx.x + r);
-    float a = 1.0f + threadIdx.x * 1e-3f, b = 1.0f - threadIdx.x * 1e-3f;
-    lds[threadIdx.x] = a;
-    __syncthreads();
-    const uint32_t la = (uint32_t)(uintptr_t)(gemm_lds_void_t *)lds + (threadIdx.x & 63) * 16;
-    float d0 = a, d1 = b, d2 = a, d3 = b;
-    gemm_f32x4 w0 = {a, b, a, b}, w1 = w0;
-    uint32_t sc = (uint32_t)iters;
-    // mode (measurement only): what one extra instruction per MFMA costs the matrix pipe
-    //   0 none | 1: 1 VALU | 2: 2 VALU | 4: 4 VALU | 10: 1 ds_read_b32 | 11: 1 ds_read_b128 per 2 MFMA | 12: 1 ds_read_b128 per MFMA
-    for (int it = 0; it < iters; it++) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[i], 0, 0, 0);
-            if (mode == 1 || mode == 2 || mode == 4) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(d0) : "v"(d1));
-            if (mode == 2 || mode == 4) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(d1) : "v"(d0));
-            if (mode == 4) {
-                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(d2) : "v"(d3));
-                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(d3) : "v"(d2));
-            }
-            if (mode == 20) asm volatile("s_nop 0");
-            if (mode == 21) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sc));
-            if (mode == 10) asm volatile("ds_read_b32 %0, %1" : "=v"(d2) : "v"(la) : "memory");
-            if (mode == 11 && (i & 1)) asm volatile("ds_read_b128 %0, %1" : "=v"(w0) : "v"(la) : "memory");
-            if (mode == 12) asm volatile("ds_read_b128 %0, %1" : "=v"(w1) : "v"(la) : "memory");
-        }
-        if (mode >= 10) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d2), "+v"(w0), "+v"(w1)::"memory");
-    }
-    float s = d0 + d1 + d2 + d3 + w0.x + w1.y + (float)sc;
-#pragma unroll
-    for (int i = 0; i < 4; i++) s += acc[i][0] + acc[i][7];
-    if (s == 12345.678f) sink[0] = s;  // keep the loop alive
-}
-#endif  // GNNX_EXPERIMENTS
-
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 using CfgDefault = Cfg<128, 128, 32, 2, 2>;  // 256 threads, 66 KB LDS, 2 workgroups per CU
 using CfgWide = Cfg<128, 256, 16, 2, 4>;     // 512 threads, 49 KB LDS: one pass over A for 256-wide outputs
-using CfgK16 = Cfg<128, 128, 16, 2, 2>;      // 33 KB LDS: 3 workgroups per CU
-using CfgWide32 = Cfg<128, 256, 32, 2, 4>;   // 512 threads, 97 KB LDS: one workgroup per CU, half the barriers
-using CfgTall = Cfg<256, 256, 16, 4, 4>;     // 1024 threads, 66 KB LDS
-using CfgTall32 = Cfg<256, 256, 32, 4, 4>;   // 1024 threads, 132 KB LDS: half the barriers
+using CfgTall32 = Cfg<256, 256, 32, 4, 4>;   // 1024 threads, 132 KB LDS
 
-// Tile choice.  Default ("auto"): 256 x 256 x 32 / 1024 threads (132 KB LDS) when the output is at least that big (A and B are each
-// streamed once for a 256-wide output: 118-121 TFLOP/s at the bench shape vs 111 for 128 x 128), 128 x 256 for wide
-// but short outputs, 128 x 128 otherwise.  GNNX_GEMM_TILE=square|wide|k16|wide32|tall forces one (A/B experiments).
-enum TileId { kSquare = 0, kWide = 1, kK16 = 2, kWide32 = 3, kTall = 4, kTall32 = 5 };
+// Tile choice of the register-staged kernels: 256 x 256 x 32 / 1024 threads (132 KB LDS) when the output is at least that big (A and B
+// are each streamed once for a 256-wide output: 118-121 TFLOP/s at the bench shape vs 111 for 128 x 128), 128 x 256 for wide but
+// short outputs, 128 x 128 otherwise.
+enum TileId { kSquare, kWide, kTall32 };
 
-int forced_tile()
+TileId pick_tile(int64_t M, int64_t N)
 {
-    static const int v = [] {
-        const char *e = experiment_env("GNNX_GEMM_TILE");
-        if (!e) return -1;
-        if (!strcmp(e, "square")) return (int)kSquare;
-        if (!strcmp(e, "wide")) return (int)kWide;
-        if (!strcmp(e, "k16")) return (int)kK16;
-        if (!strcmp(e, "wide32")) return (int)kWide32;
-        if (!strcmp(e, "tall")) return (int)kTall;
-        if (!strcmp(e, "tall32")) return (int)kTall32;
-        return -1;
-    }();
-    return v;
-}
-
-int pick_tile(int64_t M, int64_t N)
-{
-    int f = forced_tile();
-    if (f == kK16 || f == kSquare) return f;
     if (N <= 128) return kSquare;
-    if (f == kWide || f == kWide32) return f;
-    if (f == kTall || f == kTall32) return f;
     return M >= 256 ? kTall32 : kWide;
 }
 
@@ -1166,9 +819,6 @@ TileDims tile_dims(int64_t M, int64_t N)
 {
     switch (pick_tile(M, N)) {
     case kWide: return {CfgWide::BM, CfgWide::BN, CfgWide::BK};
-    case kK16: return {CfgK16::BM, CfgK16::BN, CfgK16::BK};
-    case kWide32: return {CfgWide32::BM, CfgWide32::BN, CfgWide32::BK};
-    case kTall: return {CfgTall::BM, CfgTall::BN, CfgTall::BK};
     case kTall32: return {CfgTall32::BM, CfgTall32::BN, CfgTall32::BK};
     default: return {CfgDefault::BM, CfgDefault::BN, CfgDefault::BK};
     }
@@ -1215,16 +865,10 @@ int launch(const GemmArgs &g, int splits, bool va, bool vb, hipStream_t st)
 {
     switch (pick_tile(g.M, g.N)) {
     case kWide: return launch_cfg<CfgWide, A_KC, B_KC>(g, splits, va, vb, st);
-#ifdef GNNX_EXPERIMENTS
-    case kK16: return launch_cfg<CfgK16, A_KC, B_KC>(g, splits, va, vb, st);
-    case kWide32: return launch_cfg<CfgWide32, A_KC, B_KC>(g, splits, va, vb, st);
-    case kTall: return launch_cfg<CfgTall, A_KC, B_KC>(g, splits, va, vb, st);
-#endif
     case kTall32: return launch_cfg<CfgTall32, A_KC, B_KC>(g, splits, va, vb, st);
     default: return launch_cfg<CfgDefault, A_KC, B_KC>(g, splits, va, vb, st);
     }
 }
-
 
 template <class C, bool B_KC>
 int launch_stream_cfg(const GemmArgs &g, int64_t m_tiles, int64_t gy, hipStream_t st)
@@ -1240,26 +884,26 @@ int launch_stream_cfg(const GemmArgs &g, int64_t m_tiles, int64_t gy, hipStream_
 }
 
 // *rows_done = number of leading rows of C written by the streaming kernel (0: shape not eligible).
-int launch_stream(const GemmArgs &g, bool b_kc, int waves_per_slot, hipStream_t st, int64_t *rows_done)
+int launch_stream(const GemmArgs &g, bool b_kc, hipStream_t st, int64_t *rows_done)
 {
     *rows_done = 0;
-    const int tile = pick_tile(g.M, g.N);
+    const TileId tile = pick_tile(g.M, g.N);
     if (tile != kTall32 && tile != kSquare) return GNNX_OK;
-    // measured at 10M rows (scripts/exp_gemm.py, same box, GNNX_GEMM_STREAM=0/1): dH.W 256-wide 10.69 -> 10.22 ms, 128-wide
+    // measured at 10M rows (scripts/exp_gemm.py, same box, streaming kernel off / on): dH.W 256-wide 10.69 -> 10.22 ms, 128-wide
     // 3.28 -> 3.15 ms; X.W^T 128-wide 3.29 -> 3.17 ms; X.W^T 256-wide 10.51 -> 10.65 ms (no gain: stays on the generic kernel)
-    if (b_kc && tile == kTall32 && waves_per_slot < 3) return GNNX_OK;
+    if (b_kc && tile == kTall32) return GNNX_OK;
     const TileDims t = tile_dims(g.M, g.N);
     if (g.K % t.bk != 0 || g.N % t.bn != 0) return GNNX_OK;
     const int64_t m_tiles = g.M / t.bm, cols = g.N / t.bn;
-    const int64_t slots = (int64_t)kNumCU * (tile == kTall32 ? 1 : 2);
+    const int64_t slots = (int64_t)kNumCU * (tile == kTall32 ? 1 : 2);   // resident workgroups
     if (m_tiles * cols < 4 * slots) return GNNX_OK;  // too few tiles for residency to matter
     // per-lane 32-bit offsets must cover one operand / output tile
     if ((int64_t)t.bm * g.lda >= (1ll << 30) || (int64_t)(b_kc ? t.bn : t.bk) * g.ldb >= (1ll << 30) || (int64_t)t.bm * g.ldc >= (1ll << 30))
         return GNNX_OK;
-    int64_t gy = ceil_div(slots * waves_per_slot, cols);
+    int64_t gy = ceil_div(slots, cols);
     if (gy > m_tiles) gy = m_tiles;
     int rc;
-    if (tile == kTall32) rc = b_kc ? launch_stream_cfg<CfgTall32, true>(g, m_tiles, gy, st) : launch_stream_cfg<CfgTall32, false>(g, m_tiles, gy, st);
+    if (tile == kTall32) rc = launch_stream_cfg<CfgTall32, false>(g, m_tiles, gy, st);
     else rc = b_kc ? launch_stream_cfg<CfgDefault, true>(g, m_tiles, gy, st) : launch_stream_cfg<CfgDefault, false>(g, m_tiles, gy, st);
     if (rc != GNNX_OK) return rc;
     *rows_done = m_tiles * t.bm;
@@ -1391,170 +1035,86 @@ bool dma_shape_ok(int64_t M, int64_t N, int64_t K)
     return K % 64 == 0 && N % 4 == 0 && N >= 64 && M >= 8 * 256;   // N off the 128 grid: guarded last column tile (NG)
 }
 
-template <int WM, int WN, bool NG, int BKT = 32>
-int launch_dma_geo(const GemmArgs &g, hipStream_t st, int64_t *rows_done, const GemmFuse *fuse, int64_t *partial_rows, int fuse_mode)
+// One launch of gemm_dma_kernel<WM, WN, EPI, NG>.  *rows_done = number of leading rows of C it writes; left as it is where the kernel
+// declines the operands.  *partial_rows (column-sum epilogues) = number of per-workgroup partial rows in fu.colsum_partial.
+template <int WM, int WN, Epi EPI, bool NG>
+int launch_dma_geo(const GemmArgs &g, const GemmFuse &fu, hipStream_t st, int64_t *rows_done, int64_t *partial_rows)
 {
-    using GEO = DmaGeo<WM, WN, BKT>;
+    using GEO = DmaGeo<WM, WN>;
     constexpr int BM = GEO::BM, BN = GEO::BN, BK = GEO::BK;
     if ((int64_t)BM * g.lda >= (1ll << 28) || (int64_t)BK * g.ldb >= (1ll << 28) || (int64_t)BM * g.ldc >= (1ll << 28))
         return GNNX_OK;  // per-lane BYTE offsets are 32-bit
-    // plain products (and the send-slot epilogue) cover ragged last rows with one more, overlapping tile (gemm_dma_kernel: row0_of)
-    const bool cover = (!fuse && fuse_mode != 3) || (fuse && fuse_mode == 4);
-    const int64_t m_tiles = cover ? ceil_div(g.M, (int64_t)BM) : g.M / BM, cols = ceil_div(g.N, (int64_t)BN);
+    const int64_t m_tiles = epi_covers_rows(EPI) ? ceil_div(g.M, (int64_t)BM) : g.M / BM, cols = ceil_div(g.N, (int64_t)BN);
     if (g.M < BM) return GNNX_OK;
-    constexpr size_t lds = GEO::LDS_BYTES;   // 4 x 4: 2 x (32 KB + 34 KB) = 132 KB; 4 x 2: 2 x (32 KB + 17 KB) = 98 KB; 2 x 2: 66 KB
-    constexpr int wg_per_cu = 160 * 1024 / lds >= 2 ? 2 : 1;   // resident workgroups: as many as the LDS of a CU holds
-    static const int wgpcu_env = [] { const char *e = experiment_env("GNNX_GEMM_WGPCU"); return e ? atoi(e) : 0; }();   // A/B: resident workgroups per CU
-    int64_t gy = ceil_div((int64_t)kNumCU * (wgpcu_env > 0 ? wgpcu_env : wg_per_cu), cols);
+    if constexpr (EPI == Epi::kReluColsum)
+        if (fu.ldy % 4 || !aligned16(fu.ymask) || (int64_t)BM * fu.ldy >= (1ll << 28)) return GNNX_OK;
+    if constexpr (EPI == Epi::kBnSums)
+        if (!aligned16(fu.ymask)) return GNNX_OK;
+    if constexpr (EPI == Epi::kSendSlots)
+        if (fu.ldy % 4 || !aligned16(fu.colsum_partial)) return GNNX_OK;
+    // 4 x 4: 2 x (32 KB + 34 KB) = 132 KB; 4 x 2: 2 x (32 KB + 17 KB) = 98 KB; 2 x 2: 66 KB; kSendSlots: + the two slot-list buffers
+    constexpr size_t lds = GEO::LDS_BYTES + (EPI == Epi::kSendSlots ? 2 * (size_t)BM * 32 : 0);
+    constexpr int wg_per_cu = 160 * 1024 / GEO::LDS_BYTES >= 2 ? 2 : 1;   // resident workgroups: as many as the LDS of a CU holds
+    int64_t gy = ceil_div((int64_t)kNumCU * wg_per_cu, cols);
     if (gy > m_tiles) gy = m_tiles;
-    static std::atomic<uint64_t> done_plain{0}, done_fuse{0}, done_stats{0};
-    static const int ablate = [] { const char *e = experiment_env("GNNX_GEMM_ABLATE"); return e ? atoi(e) : 0; }();
-    const dim3 grid((uint32_t)cols, (uint32_t)gy, 1);
-    if (fuse && fuse_mode == 4) {
-        if constexpr (NG || BKT != 32) return GNNX_OK;
-        else {
-            if (fuse->ldy % 4 || !aligned16(fuse->colsum_partial)) return GNNX_OK;
-            static std::atomic<uint64_t> done_send{0};
-            constexpr size_t lds_send = lds + 2 * (size_t)BM * 32;   // + the two slot-list buffers
-            int rc = lds_opt_in(&gemm_dma_kernel<WM, WN, 4, false, 32>, lds_send, done_send, "gemm_dma_kernel");
-            if (rc) return rc;
-            hipLaunchKernelGGL((gemm_dma_kernel<WM, WN, 4, false, 32>), grid, dim3(GEO::NT), lds_send, st, g, m_tiles, ablate, *fuse);
-        }
-    } else if (fuse_mode == 3) {
-        static std::atomic<uint64_t> done_bf16{0};
-        int rc = lds_opt_in(&gemm_dma_kernel<WM, WN, 3, NG, BKT>, lds, done_bf16, "gemm_dma_kernel");
-        if (rc) return rc;
-        hipLaunchKernelGGL((gemm_dma_kernel<WM, WN, 3, NG, BKT>), grid, dim3(GEO::NT), lds, st, g, m_tiles, ablate, GemmFuse{});
-    } else if (fuse && fuse_mode == 2) {
-        if (!aligned16(fuse->ymask)) return GNNX_OK;
-        int rc = lds_opt_in(&gemm_dma_kernel<WM, WN, 2, NG, BKT>, lds, done_stats, "gemm_dma_kernel");
-        if (rc) return rc;
-        hipLaunchKernelGGL((gemm_dma_kernel<WM, WN, 2, NG, BKT>), grid, dim3(GEO::NT), lds, st, g, m_tiles, ablate, *fuse);
-        if (partial_rows) *partial_rows = gy;
-    } else if (fuse) {
-        if (fuse->ldy % 4 || !aligned16(fuse->ymask) || (int64_t)BM * fuse->ldy >= (1ll << 28)) return GNNX_OK;
-        int rc = lds_opt_in(&gemm_dma_kernel<WM, WN, 1, NG, BKT>, lds, done_fuse, "gemm_dma_kernel");
-        if (rc) return rc;
-        hipLaunchKernelGGL((gemm_dma_kernel<WM, WN, 1, NG, BKT>), grid, dim3(GEO::NT), lds, st, g, m_tiles, ablate, *fuse);
-        if (partial_rows) *partial_rows = gy;
-    } else {
-        bool defer = false;
-#ifdef GNNX_EXPERIMENTS
-        // A/B only (GNNX_GEMM_DEFER=1): the C tile parked in a second accumulator set and stored straight from registers under the
-        // next tile's K-tiles (gemm_dma_kernel: DEFER).  Measured SLOWER than the LDS-staged epilogue -- 10 M x 128 x 128: X.W^T 3.20
-        // against 3.07 ms, dH.W 2.98 against 2.87 -- 64-byte row segments cost more on the store path than the LDS round trip they
-        // save, even spread over the tile: the product library does not instantiate it.
-        if constexpr (WM * WN <= 8 && BKT == 32) {
-            static const int defer_env = [] { const char *e = experiment_env("GNNX_GEMM_DEFER"); return e ? atoi(e) : 0; }();
-            defer = defer_env != 0 && g.K >= 4 * BK && ablate == 0;
-            if (defer) {
-                static std::atomic<uint64_t> done_defer{0};
-                int rc = lds_opt_in(&gemm_dma_kernel<WM, WN, 0, NG, BKT, true>, lds, done_defer, "gemm_dma_kernel");
-                if (rc) return rc;
-                hipLaunchKernelGGL((gemm_dma_kernel<WM, WN, 0, NG, BKT, true>), grid, dim3(GEO::NT), lds, st, g, m_tiles, ablate, GemmFuse{});
-            }
-        }
-#endif
-        if (!defer) {
-            int rc = lds_opt_in(&gemm_dma_kernel<WM, WN, 0, NG, BKT>, lds, done_plain, "gemm_dma_kernel");
-            if (rc) return rc;
-            hipLaunchKernelGGL((gemm_dma_kernel<WM, WN, 0, NG, BKT>), grid, dim3(GEO::NT), lds, st, g, m_tiles, ablate, GemmFuse{});
-        }
-    }
+    static std::atomic<uint64_t> done{0};   // one per (geometry, epilogue)
+    const int rc = lds_opt_in(&gemm_dma_kernel<WM, WN, EPI, NG>, lds, done, "gemm_dma_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL((gemm_dma_kernel<WM, WN, EPI, NG>), dim3((uint32_t)cols, (uint32_t)gy, 1), dim3(GEO::NT), lds, st, g, fu, m_tiles);
     GNNX_LAUNCH_CHECK();
+    if (partial_rows && (EPI == Epi::kReluColsum || EPI == Epi::kBnSums)) *partial_rows = gy;
     *rows_done = m_tiles * BM < g.M ? m_tiles * BM : g.M;
     return GNNX_OK;
 }
 
+// The last, partly filled round of tiles (1.25 M rows x 256: 4 882 tiles of 256 x 256 on 256 CUs = 19 rounds and 18 tiles that cost
+// a 20th; 1 M rows x 128: 15 rounds and 66 tiles) goes to a launch of its own on SMALLER tiles, so that it occupies many CUs for a
+// fraction of a round: whole rounds on the main geometry WM x WN, the rest on the tail's, TWM x TWN.  Same MFMA chain per output
+// element in every geometry: same bits.  Epilogues that store rows only (epi_covers_rows).
+template <int WM, int WN, int TWM, int TWN, Epi EPI>
+int launch_dma_with_tail(const GemmArgs &g, const GemmFuse &fu, hipStream_t st, int64_t *rows_done)
+{
+    static_assert(epi_covers_rows(EPI), "the column-sum epilogues index their partials by workgroup");
+    const int64_t mt256 = g.M / 256;
+    GemmArgs gm = g;
+    gm.M = (mt256 - mt256 % kNumCU) * 256;
+    int64_t rows_main = 0;
+    int rc = launch_dma_geo<WM, WN, EPI, false>(gm, fu, st, &rows_main, nullptr);
+    *rows_done = rows_main;
+    if (rc || rows_main != gm.M) return rc;
+    GemmArgs gt = g;
+    gt.A += rows_main * g.lda;
+    gt.C += rows_main * g.ldc;
+    gt.M = g.M - rows_main;
+    GemmFuse ft = fu;
+    if constexpr (EPI == Epi::kSendSlots) ft.slots += rows_main * 8;
+    int64_t rows_tail = 0;
+    rc = launch_dma_geo<TWM, TWN, EPI, false>(gt, ft, st, &rows_tail, nullptr);
+    *rows_done = rows_main + rows_tail;
+    return rc;
+}
+
 // *rows_done = number of leading rows of C written by the LDS-DMA kernel (0: shape not eligible).  B must be k-major ([K][N]).
-int launch_dma(const GemmArgs &g, hipStream_t st, int64_t *rows_done, const GemmFuse *fuse = nullptr, int64_t *partial_rows = nullptr,
-               int fuse_mode = 1)
+template <Epi EPI>
+int launch_dma(const GemmArgs &g, const GemmFuse &fu, hipStream_t st, int64_t *rows_done, int64_t *partial_rows = nullptr)
 {
     *rows_done = 0;
     if (!dma_shape_ok(g.M, g.N, g.K)) return GNNX_OK;
     if (g.lda % 4 || g.ldb % 4 || g.ldc % 4 || !aligned16(g.A) || !aligned16(g.B) || !aligned16(g.C)) return GNNX_OK;
-    if (fuse_mode == 3 && g.alpha != 1.0f) return GNNX_OK;
-#ifdef GNNX_EXPERIMENTS
-    static const int geo256 = [] { const char *e = experiment_env("GNNX_GEMM_GEO256"); return e ? atoi(e) : 0; }();
-    if (g.N % 256 == 0 && geo256 == 2416) return launch_dma_geo<2, 4, false, 16>(g, st, rows_done, fuse, partial_rows, fuse_mode);
-    // A/B: the 256 x 128 tile (8 wavefronts, 128 VGPRs, 98 KB of LDS per CU) for 256-wide outputs too: half of every SIMD's registers
-    // stay free for wavefronts of ANOTHER kernel (an aggregation on a second stream: scripts/exp_concurrent.py)
-    if (g.N % 256 == 0 && geo256 == 42) return launch_dma_geo<4, 2, false>(g, st, rows_done, fuse, partial_rows, fuse_mode);
-#endif
-    // The last, partly filled round of tiles (1.25 M rows x 256: 4 882 tiles of 256 x 256 on 256 CUs = 19 rounds and 18 tiles that cost
-    // a 20th; 1 M rows x 128: 15 rounds and 66 tiles) goes to a launch of its own on SMALLER tiles, so that it occupies many CUs for a
-    // fraction of a round: 128 x 128 (4 wavefronts) or 256 x 128 (8).  Same MFMA chain per output element in every geometry: same
-    // bits.  Plain products and the send-slot epilogue only (the column-sum epilogues index their partials by workgroup).
-    static const int tail_env = [] { const char *e = experiment_env("GNNX_GEMM_TAIL"); return e ? atoi(e) : 1; }();
-    const bool plain = (!fuse && fuse_mode != 3) || (fuse && fuse_mode == 4);
-    const int64_t mt256 = g.M / 256, r = mt256 % kNumCU;
-    auto with_tail = [&](auto main_geo, auto tail_geo) -> int {   // whole rounds on the main geometry, the rest on the tail's
-        GemmArgs gm = g;
-        gm.M = (mt256 - r) * 256;
-        int64_t rows_main = 0;
-        int rc = main_geo(gm, fuse, &rows_main);
-        *rows_done = rows_main;
-        if (rc || rows_main != gm.M) return rc;
-        GemmArgs gt = g;
-        gt.A += rows_main * g.lda;
-        gt.C += rows_main * g.ldc;
-        gt.M = g.M - rows_main;
-        GemmFuse ft{};
-        if (fuse) {
-            ft = *fuse;
-            ft.slots += rows_main * 8;
+    if constexpr (EPI == Epi::kBf16)
+        if (g.alpha != 1.0f) return GNNX_OK;
+    if constexpr (epi_covers_rows(EPI)) {
+        const int64_t mt256 = g.M / 256, r = mt256 % kNumCU;   // r: tiles of the last round
+        if (mt256 > kNumCU && r > 0) {
+            if (g.N == 256 && r <= kNumCU / 4) return launch_dma_with_tail<4, 4, 2, 2, EPI>(g, fu, st, rows_done);   // a quarter of a round
+            if (g.N == 256 && r <= kNumCU / 2) return launch_dma_with_tail<4, 4, 4, 2, EPI>(g, fu, st, rows_done);   // half
+            if (g.N == 128 && r <= kNumCU / 2) return launch_dma_with_tail<4, 2, 2, 2, EPI>(g, fu, st, rows_done);   // 128 x 128: half a round
         }
-        int64_t rows_tail = 0;
-        rc = tail_geo(gt, fuse ? &ft : nullptr, &rows_tail);
-        *rows_done = rows_main + rows_tail;
-        return rc;
-    };
-    if (g.N % 256 == 0) {
-        auto g44 = [&](const GemmArgs &a, const GemmFuse *f, int64_t *rows) { return launch_dma_geo<4, 4, false>(a, st, rows, f, partial_rows, fuse_mode); };
-        auto g42 = [&](const GemmArgs &a, const GemmFuse *f, int64_t *rows) { return launch_dma_geo<4, 2, false>(a, st, rows, f, partial_rows, fuse_mode); };
-        auto g22 = [&](const GemmArgs &a, const GemmFuse *f, int64_t *rows) { return launch_dma_geo<2, 2, false>(a, st, rows, f, partial_rows, fuse_mode); };
-        if (tail_env > 0 && plain && g.N == 256 && mt256 > kNumCU && r > 0 && r <= kNumCU / 4) return with_tail(g44, g22);   // a quarter of a round
-        if (tail_env > 0 && plain && g.N == 256 && mt256 > kNumCU && r > 0 && r <= kNumCU / 2) return with_tail(g44, g42);   // half
-        return launch_dma_geo<4, 4, false>(g, st, rows_done, fuse, partial_rows, fuse_mode);
     }
-    static const int geo128 = [] { const char *e = experiment_env("GNNX_GEMM_GEO128"); return e ? atoi(e) : 0; }();
-    if (geo128 == 22) {   // A/B: 128 x 128 tiles, two resident workgroups of 4 wavefronts per CU
-        if (g.N % 128 == 0) return launch_dma_geo<2, 2, false>(g, st, rows_done, fuse, partial_rows, fuse_mode);
-        return launch_dma_geo<2, 2, true>(g, st, rows_done, fuse, partial_rows, fuse_mode);
-    }
-#ifdef GNNX_EXPERIMENTS
-    if (geo128 == 4216) {   // A/B: the 256 x 128 tile on K-tiles of 16, two resident workgroups per CU
-        if (g.N % 128 == 0) return launch_dma_geo<4, 2, false, 16>(g, st, rows_done, fuse, partial_rows, fuse_mode);
-        return launch_dma_geo<4, 2, true, 16>(g, st, rows_done, fuse, partial_rows, fuse_mode);
-    }
-#endif
-#ifdef GNNX_EXPERIMENTS
-    static const int w128_env = [] { const char *e = experiment_env("GNNX_GEMM_W128"); return e ? atoi(e) : 0; }();
-    if (w128_env > 0 && geo128 == 0 && !fuse && fuse_mode != 3 && g.N == 128 && g.K == 128 && (int64_t)W128::ROWS * g.lda < (1ll << 28) &&
-        (int64_t)128 * g.ldb < (1ll << 28) && g.M >= W128::ROWS) {
-        // A/B: K = N = 128 with W resident in LDS, a strip of 16 rows per wavefront, no barrier in the loop (gemm_w128_kernel)
-        static std::atomic<uint64_t> done_w128{0};
-        int rc = lds_opt_in(&gemm_w128_kernel, (size_t)W128::LDS_BYTES, done_w128, "gemm_w128_kernel");
-        if (rc) return rc;
-        const int64_t n_strips = ceil_div(g.M, (int64_t)W128::ROWS);
-        int64_t gx = ceil_div(n_strips, (int64_t)W128::NW);
-        if (gx > kNumCU) gx = kNumCU;
-        static const int ablate = [] { const char *e = experiment_env("GNNX_GEMM_ABLATE"); return e ? atoi(e) : 0; }();
-        hipLaunchKernelGGL(gemm_w128_kernel, dim3((uint32_t)gx), dim3(W128::NT), (size_t)W128::LDS_BYTES, st, g, n_strips, ablate);
-        GNNX_LAUNCH_CHECK();
-        *rows_done = g.M;
-        return GNNX_OK;
-    }
-#endif
-    if (g.N % 128 == 0) {
-        if (tail_env > 0 && geo128 == 0 && plain && g.N == 128 && mt256 > kNumCU && r > 0 && r <= kNumCU / 2) {   // 128 x 128: half a round
-            auto g42 = [&](const GemmArgs &a, const GemmFuse *f, int64_t *rows) { return launch_dma_geo<4, 2, false>(a, st, rows, f, partial_rows, fuse_mode); };
-            auto g22 = [&](const GemmArgs &a, const GemmFuse *f, int64_t *rows) { return launch_dma_geo<2, 2, false>(a, st, rows, f, partial_rows, fuse_mode); };
-            return with_tail(g42, g22);
-        }
-        return launch_dma_geo<4, 2, false>(g, st, rows_done, fuse, partial_rows, fuse_mode);
-    }
-    return launch_dma_geo<4, 2, true>(g, st, rows_done, fuse, partial_rows, fuse_mode);
+    if (g.N % 256 == 0) return launch_dma_geo<4, 4, EPI, false>(g, fu, st, rows_done, partial_rows);
+    if (g.N % 128 == 0) return launch_dma_geo<4, 2, EPI, false>(g, fu, st, rows_done, partial_rows);
+    if constexpr (EPI == Epi::kSendSlots) return GNNX_OK;   // no guarded last column tile: its caller asks for N % 128 == 0
+    else return launch_dma_geo<4, 2, EPI, true>(g, fu, st, rows_done, partial_rows);
 }
 
 bool dma_tn_shape_ok(int64_t M, int64_t N, int64_t K) { return M % 128 == 0 && N % 128 == 0 && K % 64 == 0 && K >= 64 * 1024; }
@@ -1593,33 +1153,15 @@ __global__ __launch_bounds__(256) void gemm_transpose_w_kernel(const float *X, i
         if (c0 + k < n_cols && r0 + tx < n_rows) Y[(c0 + k) * ldy + r0 + tx] = t[tx][k];
 }
 
-}  // namespace
-
-#ifdef GNNX_EXPERIMENTS
-// Measurement entry of the EXPERIMENTS build only (scripts/exp_gemm.py; not declared in include/gnnx.h): a register-only f32 MFMA
-// loop, optionally with extra instructions per MFMA (GNNX_PEAK_MODE), to calibrate what bounds such a loop on this chip.
-GNNX_API int gnnx_mfma_peak_f32(int32_t iters, int32_t n_workgroups, float *d_sink, double *flops_out, void *stream)
+// W [N][K] -> wt = W^T [K][N] (ld N) in the workspace: the k-major B operand of the LDS-DMA kernel for X . W^T
+int transpose_w(const float *W, int64_t ldw, int64_t N, int64_t K, float *wt, hipStream_t st)
 {
-    GNNX_REQUIRE(iters > 0 && n_workgroups > 0 && d_sink, GNNX_ERR_INVALID_ARG, "bad arguments");
-    static const int peak_mode = [] { const char *e = experiment_env("GNNX_PEAK_MODE"); return e ? atoi(e) : 0; }();
-    const dim3 pg((uint32_t)n_workgroups), pb(256);
-    hipStream_t pst = as_stream(stream);
-    switch (peak_mode) {
-    case 1: hipLaunchKernelGGL(mfma_peak_kernel<1>, pg, pb, 0, pst, iters, d_sink); break;
-    case 2: hipLaunchKernelGGL(mfma_peak_kernel<2>, pg, pb, 0, pst, iters, d_sink); break;
-    case 4: hipLaunchKernelGGL(mfma_peak_kernel<4>, pg, pb, 0, pst, iters, d_sink); break;
-    case 10: hipLaunchKernelGGL(mfma_peak_kernel<10>, pg, pb, 0, pst, iters, d_sink); break;
-    case 11: hipLaunchKernelGGL(mfma_peak_kernel<11>, pg, pb, 0, pst, iters, d_sink); break;
-    case 12: hipLaunchKernelGGL(mfma_peak_kernel<12>, pg, pb, 0, pst, iters, d_sink); break;
-    case 20: hipLaunchKernelGGL(mfma_peak_kernel<20>, pg, pb, 0, pst, iters, d_sink); break;
-    case 21: hipLaunchKernelGGL(mfma_peak_kernel<21>, pg, pb, 0, pst, iters, d_sink); break;
-    default: hipLaunchKernelGGL(mfma_peak_kernel<0>, pg, pb, 0, pst, iters, d_sink); break;
-    }
+    hipLaunchKernelGGL(gemm_transpose_w_kernel, dim3((uint32_t)ceil_div(K, 32), (uint32_t)ceil_div(N, 32)), dim3(256), 0, st, W, ldw, N, K, wt, N);
     GNNX_LAUNCH_CHECK();
-    if (flops_out) *flops_out = (double)n_workgroups * 4 /*waves*/ * 4 /*acc*/ * (double)iters * (2.0 * 32 * 32 * 2);
     return GNNX_OK;
 }
-#endif  // GNNX_EXPERIMENTS
+
+}  // namespace
 
 GNNX_API int gnnx_gemm_workspace(int transA, int transB, int64_t M, int64_t N, int64_t K, size_t *bytes)
 {
@@ -1636,7 +1178,7 @@ GNNX_API int gnnx_gemm_workspace(int transA, int transB, int64_t M, int64_t N, i
 }
 
 // C = (A . B) with the ReLU mask of the layer below applied, colsum[n] = sum_m C[m][n]: the stacked layers' backward step
-// G_{l-1} = (dH_l . W_l) (.) (Y_{l-1} > 0), db_{l-1} = colsum(G_{l-1}) in ONE pass over the output (LDS-DMA kernel, FUSE epilogue);
+// G_{l-1} = (dH_l . W_l) (.) (Y_{l-1} > 0), db_{l-1} = colsum(G_{l-1}) in ONE pass over the output (LDS-DMA kernel, Epi::kReluColsum);
 // rows outside whole 256-row tiles and shapes the kernel does not cover go through gemm -> mask -> colsum.
 GNNX_API int gnnx_gemm_relu_colsum_workspace(int64_t M, int64_t N, int64_t K, size_t *bytes)
 {
@@ -1671,8 +1213,7 @@ GNNX_API int gnnx_gemm_relu_colsum_f32(int64_t M, int64_t N, int64_t K, const fl
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K; g.A = d_A; g.lda = lda; g.B = d_B; g.ldb = ldb; g.C = d_C; g.ldc = ldc; g.alpha = 1.f; g.beta = 0.f;
     g.k_per_split = K;
-    GemmFuse fu{d_Ymask, ldy, partial};
-    int rc = launch_dma(g, st, &rows, &fu, &prow);
+    int rc = launch_dma<Epi::kReluColsum>(g, GemmFuse{d_Ymask, ldy, partial, nullptr}, st, &rows, &prow);
     if (rc) return rc;
     float beta = 0.f;
     if (rows > 0) {   // the workgroups' partial column sums -> colsum, fixed order
@@ -1770,14 +1311,13 @@ GNNX_API int gnnx_gemm_bn_stats_f32(int64_t M, int64_t N, int64_t K, const float
     }
     hipLaunchKernelGGL(gemm_row0_kernel, dim3((uint32_t)ceil_div(N, 256)), dim3(256), 0, st, d_X, d_W, ldw, N, K, 1, shift);
     GNNX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gemm_transpose_w_kernel, dim3((uint32_t)ceil_div(K, 32), (uint32_t)ceil_div(N, 32)), dim3(256), 0, st, d_W, ldw, N, K, wt, N);
-    GNNX_LAUNCH_CHECK();
+    int rc = transpose_w(d_W, ldw, N, K, wt, st);
+    if (rc) return rc;
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K; g.A = d_X; g.lda = ldx; g.B = wt; g.ldb = N; g.C = d_H; g.ldc = ldh; g.alpha = 1.f; g.beta = 0.f;
     g.k_per_split = K;
-    GemmFuse fu{shift, 0, partial, nullptr};
     int64_t rows = 0, prow = 0;
-    int rc = launch_dma(g, st, &rows, &fu, &prow, 2);
+    rc = launch_dma<Epi::kBnSums>(g, GemmFuse{shift, 0, partial, nullptr}, st, &rows, &prow);
     if (rc) return rc;
     if (rows == 0) {   // the kernel declined (alignment of a sub-buffer): exact path
         rc = gnnx_gemm_f32(0, 1, M, N, K, 1.f, d_X, ldx, d_W, ldw, 0.f, d_H, ldh, wt, sizeof(float) * (size_t)K * N, stream);
@@ -1821,13 +1361,13 @@ GNNX_API int gnnx_gemm_nt_bf16out_f32(int64_t M, int64_t N, int64_t K, const flo
     hipStream_t st = as_stream(stream);
     float *wt = static_cast<float *>(d_workspace);
     float *tail = wt + (size_t)K * N;
-    hipLaunchKernelGGL(gemm_transpose_w_kernel, dim3((uint32_t)ceil_div(K, 32), (uint32_t)ceil_div(N, 32)), dim3(256), 0, st, d_W, ldw, N, K, wt, N);
-    GNNX_LAUNCH_CHECK();
+    int rc = transpose_w(d_W, ldw, N, K, wt, st);
+    if (rc) return rc;
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K; g.A = d_X; g.lda = ldx; g.B = wt; g.ldb = N; g.C = reinterpret_cast<float *>(d_H_bf16); g.ldc = ldh;
     g.alpha = 1.f; g.beta = 0.f; g.k_per_split = K;
     int64_t rows = 0;
-    int rc = launch_dma(g, st, &rows, nullptr, nullptr, 3);
+    rc = launch_dma<Epi::kBf16>(g, GemmFuse{}, st, &rows);
     if (rc) return rc;
     GNNX_REQUIRE(rows > 0, GNNX_ERR_SHAPE, "bf16-output product: shape not taken by the LDS-DMA kernel");
     if (rows < M) {   // ragged tail (< 256 rows): f32 product, then the same rounding
@@ -1875,33 +1415,31 @@ GNNX_API int gnnx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t
                      workspace_bytes, need);
         g.slab = static_cast<float *>(d_workspace);
     }
-    // tall products with whole tiles: the resident streaming kernel takes the whole M-tiles, the generic kernel the rest
     // tall products with whole tiles: the LDS-DMA kernel takes the whole 256-row tiles (B k-major; for X.W^T the small W is
     // transposed once into the workspace, same products in the same order), the generic kernel the ragged rest
-    static const int dma_env = [] { const char *e = experiment_env("GNNX_GEMM_DMA"); return e ? atoi(e) : 1; }();
-    if (dma_env > 0 && a_kc && splits == 1 && beta == 0.f && K > 0 && dma_shape_ok(M, N, K) &&
+    if (a_kc && splits == 1 && beta == 0.f && K > 0 && dma_shape_ok(M, N, K) &&
         (!b_kc || (d_workspace && workspace_bytes >= sizeof(float) * (size_t)K * (size_t)N && aligned16(d_workspace)))) {
         GemmArgs gd = g;
         if (b_kc) {
             float *wt = static_cast<float *>(d_workspace);
-            hipLaunchKernelGGL(gemm_transpose_w_kernel, dim3((uint32_t)ceil_div(K, 32), (uint32_t)ceil_div(N, 32)), dim3(256), 0, st, d_B, ldb,
-                               N, K, wt, N);
-            GNNX_LAUNCH_CHECK();
+            const int trc = transpose_w(d_B, ldb, N, K, wt, st);
+            if (trc != GNNX_OK) return trc;
             gd.B = wt;
             gd.ldb = N;
         }
         int64_t rows = 0;
-        const int src = launch_dma(gd, st, &rows);
+        const int src = launch_dma<Epi::kPlain>(gd, GemmFuse{}, st, &rows);
         if (src != GNNX_OK) return src;
         if (rows == g.M) return GNNX_OK;
         g.A += rows * lda;
         g.C += rows * ldc;
         g.M -= rows;
     }
-    static const int stream_env = [] { const char *e = experiment_env("GNNX_GEMM_STREAM"); return e ? atoi(e) : 1; }();
-    if (stream_env > 0 && a_kc && splits == 1 && beta == 0.f && va && vb && K > 0) {
+    // what is left and still tall (K % 32 == 0 but K % 64 != 0, no workspace for W^T): the resident streaming kernel takes the whole
+    // M-tiles, the generic kernel the rest
+    if (a_kc && splits == 1 && beta == 0.f && va && vb && K > 0) {
         int64_t rows = 0;  // leading rows of C written by the streaming kernel
-        const int src = launch_stream(g, b_kc, stream_env, st, &rows);
+        const int src = launch_stream(g, b_kc, st, &rows);
         if (src != GNNX_OK) return src;
         if (rows == g.M) return GNNX_OK;
         g.A += rows * lda;
@@ -1910,7 +1448,7 @@ GNNX_API int gnnx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t
     }
     int rc;
     // dW = dH^T . X on the LDS-DMA loop: both operands k-major, whole 256 x 256 tiles, K in whole pairs of K-tiles per split
-    const bool dma_tn = dma_env > 0 && !a_kc && !b_kc && splits > 1 && g.slab && k_dma > 0 && g.k_per_split % 64 == 0 &&
+    const bool dma_tn = !a_kc && !b_kc && splits > 1 && g.slab && k_dma > 0 && g.k_per_split % 64 == 0 &&
                         lda % 4 == 0 && ldb % 4 == 0 && aligned16(d_A) && aligned16(d_B) && aligned16(g.slab) &&
                         32 * lda < (1ll << 28) && 32 * ldb < (1ll << 28);
     int reduce_slabs = splits;
@@ -1975,13 +1513,12 @@ GNNX_API int gnnx_gemm_nt_rows_to_slots_f32(int64_t M, int64_t N, int64_t K, con
     int64_t rows = 0;
     if (dma_shape_ok(M, N, K) && N % 128 == 0 && aligned16(d_workspace)) {
         float *wt = static_cast<float *>(d_workspace);
-        hipLaunchKernelGGL(gemm_transpose_w_kernel, dim3((uint32_t)ceil_div(K, 32), (uint32_t)ceil_div(N, 32)), dim3(256), 0, st, d_W, ldw, N, K, wt, N);
-        GNNX_LAUNCH_CHECK();
+        int rc = transpose_w(d_W, ldw, N, K, wt, st);
+        if (rc) return rc;
         GemmArgs g{};
         g.M = M; g.N = N; g.K = K; g.A = d_X; g.lda = ldx; g.B = wt; g.ldb = N; g.C = d_H; g.ldc = ldh; g.alpha = 1.f; g.beta = 0.f;
         g.k_per_split = K;
-        GemmFuse fu{nullptr, ld_send, d_send, d_slots};
-        int rc = launch_dma(g, st, &rows, &fu, nullptr, 4);
+        rc = launch_dma<Epi::kSendSlots>(g, GemmFuse{nullptr, ld_send, d_send, d_slots}, st, &rows);
         if (rc) return rc;
     }
     if (rows < M) {   // what the kernel left: the plain product, then the pack as a pass of its own

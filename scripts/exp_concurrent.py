@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Do an HBM-bound aggregation and an MFMA-bound dense product overlap when they are launched on two streams?
-Bench graph (10M / 100M, F = 256): X.W^T on stream A beside the backward aggregation on stream B, against the two run in sequence.
-Also the same with the dense product's persistent grid restricted to fewer CUs (GNNX_GEMM_DMA_GRID, experiment builds only)."""
+Bench graph (10M / 100M, F = 256): X.W^T on stream A beside the backward aggregation on stream B, against the two run in sequence."""
 import ctypes as C
 import importlib
 import os

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The sharded step's transform at one rank's size (1.25 M rows x 256 x 256, 1.79 M send rows to 7 peers):
-product + pack pass against the product with the pack in its epilogue (gnnx_gemm_nt_rows_to_slots_f32), and the products' last
-partial round on smaller tiles against the plain launch (EXPERIMENTS build: GNNX_GEMM_TAIL=0 in a second run).
+product + pack pass against the product with the pack in its epilogue (gnnx_gemm_nt_rows_to_slots_f32); the products' last partial
+round runs on smaller tiles (the tail launch of gnnx_gemm.hip).
 usage (GPU box): python scripts/exp_gemm_send.py            one JSON line per shape
 """
 import json
@@ -44,7 +44,7 @@ for M, F, peers, frac in SHAPES:
     G = ops.uniform_pm1(3, (M, F), device=dev)
     dX = torch.empty((M, F), dtype=torch.float32, device=dev)
     dW = torch.empty((F, F), dtype=torch.float32, device=dev)
-    rec = {"M": M, "F": F, "gemm_tail_env": os.environ.get("GNNX_GEMM_TAIL", ""), "lib": os.environ.get("GNNX_HIP_LIB", "")}
+    rec = {"M": M, "F": F, "lib": os.environ.get("GNNX_HIP_LIB", "")}
     rec["xwT_ms"] = round(timed(lambda: ops.linear_fwd(X, W, out=H)), 4)
     rec["dX_ms"] = round(timed(lambda: ops.gemm(G, W, out=dX)), 4)
     rec["dW_ms"] = round(timed(lambda: ops.gemm(G, X, transA=True, out=dW)), 4)

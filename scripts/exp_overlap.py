@@ -74,7 +74,7 @@ def main():
     t_g = wall(gemms)
     t_ser = wall(serial)
     t_con = wall(concurrent)
-    print(f"tile={os.environ.get('GNNX_GEMM_TILE', 'default')}: spmm {t_s:.2f} ms, gemms {t_g:.2f} ms, serial {t_ser:.2f} ms, "
+    print(f"spmm {t_s:.2f} ms, gemms {t_g:.2f} ms, serial {t_ser:.2f} ms, "
           f"two streams {t_con:.2f} ms (ideal max {max(t_s, t_g):.2f})", flush=True)
 
 

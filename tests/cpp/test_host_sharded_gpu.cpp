@@ -654,7 +654,7 @@ int main()
             for (int world : {2, 4}) run_sharded(p, hot, world, ref);
         }
         // a width the LDS-DMA product takes (K % 64 == 0, N % 128 == 0, >= 2048 local rows): the transform's send rows leave from the
-        // product kernel's own epilogue (gemm_dma_kernel, FUSE 4), not from the two calls it falls back to on other shapes
+        // product kernel's own epilogue (gemm_dma_kernel, Epi::kSendSlots), not from the two calls it falls back to on other shapes
         {
             const Problem wide = make_problem(12000, 150000, 64, 128);
             const Result wref = run_unsharded(wide, true);
