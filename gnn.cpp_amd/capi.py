@@ -147,6 +147,12 @@ _SIGS = {
     "gnnx_argmax_rows_workspace": [C.POINTER(_sz)],
     "gnnx_argmax_rows_f32": [_vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp],
     "gnnx_accuracy_rows_f32": [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, C.POINTER(_i64), _vp, _sz, _vp],
+    "gnnx_frontier_mark_workspace": [_i64, C.POINTER(_sz)],
+    "gnnx_frontier_mark": [_vp, _vp, _i32, _i32, _vp, _i64, _vp, C.POINTER(_i64), _vp, _sz, _vp],
+    "gnnx_rows_to_positions_workspace": [C.POINTER(_sz)],
+    "gnnx_rows_to_positions": [_vp, _i64, _i64, _vp, _vp, _sz, _vp],
+    "gnnx_csr_extract_rows_workspace": [_i64, C.POINTER(_sz)],
+    "gnnx_csr_extract_rows": [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _sz, _vp],
     "gnnx_comm_unique_id": [_vp],
     "gnnx_comm_init": [C.POINTER(_vp), C.c_int, C.c_int, _vp],
     "gnnx_comm_init_local": [C.POINTER(_vp), C.c_int],

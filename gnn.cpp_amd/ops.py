@@ -211,6 +211,11 @@ class CsrGraph:
         layer: a LabelledSet in this graph's row order.  mask: [n] bool / uint8 in VERTEX order (as X before to_new_order)."""
         return LabelledSet(self, mask)
 
+    def receptive_field(self, query, n_layers):
+        """The n_layers-hop receptive field of a vertex set, prepared once for GcnStack.predict / evaluate_field: a ReceptiveField.
+        query: 1-D integer tensor of VERTEX ids, any order, repeats allowed."""
+        return ReceptiveField(self, query, n_layers)
+
 
 class LabelledSet:
     """rows / n_labelled of a train mask, the row-restricted CSR(A) (entries whose row is labelled) and the column-restricted
@@ -281,6 +286,119 @@ def csr_restrict(rowptr, colidx, vals=None, row_keep=None, col_keep=None, n_cols
     # (an empty result stays a view of its 1-element buffer: the aggregation wants a device pointer even for no entries)
     shrink = lambda t: None if t is None else (t[:k].clone() if k else t[:0])  # noqa: E731
     return rowptr_o, shrink(colidx_o), shrink(vals_o)
+
+
+def _row_list(rows):
+    r = rows.reshape(-1)
+    return (r if r.dtype == torch.int32 else r.to(torch.int32)).contiguous()
+
+
+def _frontier(rowptr, colidx, rows, n_cols):
+    """frontier() and the number of entries of the listed rows (gnnx_frontier_mark's count)"""
+    rows = _row_list(rows)
+    n_rows, k, dev = int(rowptr.numel() - 1), int(rows.numel()), rowptr.device
+    mark = torch.zeros(max(int(n_cols), 1), dtype=torch.uint8, device=dev)
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_frontier_mark_workspace", k, C.byref(wsb))
+    ws = _workspace(wsb.value, dev, "field")
+    nnz = C.c_int64(0)
+    capi.call("gnnx_frontier_mark", _ptr(rowptr), _ptr(colidx) if int(colidx.numel()) else None, n_rows, int(n_cols), _ptr(rows) if k else None, k,
+              _ptr(mark), C.byref(nnz), _ptr(ws), ws.numel(), _stream())
+    return rows_from_mask(mark[:int(n_cols)]), nnz.value
+
+
+def frontier(rowptr, colidx, rows, n_cols):
+    """gnnx_frontier_mark + gnnx_mask_to_rows: the ascending int32 list of the columns stored in the listed rows (ascending, no
+    repeats) of a CSR with n_cols columns -- the rows of the layer below that the listed rows of a layer read."""
+    return _frontier(rowptr, colidx, rows, n_cols)[0]
+
+
+def rows_to_positions(rows, n):
+    """gnnx_rows_to_positions: int32 [n], pos[rows[k]] = k and -1 for a row that is not listed."""
+    rows = _row_list(rows)
+    k, dev = int(rows.numel()), rows.device
+    pos = torch.empty(max(int(n), 1), dtype=torch.int32, device=dev)
+    ws = _workspace(512, dev, "field_pos")
+    capi.call("gnnx_rows_to_positions", _ptr(rows) if k else None, k, int(n), _ptr(pos), _ptr(ws), ws.numel(), _stream())
+    return pos[:int(n)]
+
+
+def csr_extract_rows(rowptr, colidx, rows, vals=None, col_pos=None, n_cols=None, nnz_capacity=None):
+    """gnnx_csr_extract_rows: the CSR of the listed rows (ascending, no repeats), entries in stored order, columns renumbered through
+    the position table col_pos ([n_cols] int32 from rows_to_positions; None keeps the column ids).  nnz_capacity: entries the outputs
+    may hold (default: what the listed rows hold, from rowptr).  -> (rowptr' [len(rows) + 1], colidx', vals' or None)."""
+    rows = _row_list(rows)
+    n_rows, k, dev = int(rowptr.numel() - 1), int(rows.numel()), rowptr.device
+    if n_cols is None:
+        n_cols = int(col_pos.numel()) if col_pos is not None else n_rows
+    if col_pos is not None and int(col_pos.numel()) != n_cols:
+        raise ValueError("col_pos must have one entry per column")
+    if nnz_capacity is None:
+        r = rows.long()
+        nnz_capacity = int((rowptr[r + 1] - rowptr[r]).sum()) if k else 0
+    cap = int(nnz_capacity)
+    rowptr_o = torch.empty(k + 1, dtype=torch.int32, device=dev)
+    colidx_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    vals_o = torch.empty(max(cap, 1), dtype=torch.float32, device=dev) if vals is not None else None
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_csr_extract_rows_workspace", k, C.byref(wsb))
+    ws = _workspace(wsb.value, dev, "field")
+    out_nnz = C.c_int64(0)
+    capi.call("gnnx_csr_extract_rows", n_rows, int(n_cols), _ptr(rowptr), _ptr(colidx) if int(colidx.numel()) else None, _ptr(vals),
+              _ptr(rows) if k else None, k, _ptr(col_pos), _ptr(rowptr_o), _ptr(colidx_o), _ptr(vals_o), cap, C.byref(out_nnz), _ptr(ws),
+              ws.numel(), _stream())
+    m = out_nnz.value
+    # (an empty result stays a view of its 1-element buffer, as csr_restrict's: the aggregation wants a device pointer)
+    shrink = lambda t: None if t is None else (t[:m] if m else t[:0])  # noqa: E731
+    return rowptr_o, shrink(colidx_o), shrink(vals_o)
+
+
+class ReceptiveField:
+    """The L-hop receptive field of a query set on a CsrGraph, built once and reusable (a validation mask evaluated every epoch).
+    With Q_L = the query's rows and Q_{l-1} = the columns stored in rows Q_l of CSR(A) (no self term: the diagonal is not stored):
+      rows[l]   l = 0..L   ascending int32 rows of the graph (row order, nid applied); a row's compact id is its position
+      nnz[l]    l = 1..L   entries of the block of A with rows Q_l and columns Q_{l-1} (nnz[0] is 0)
+      block[l]  l = 1..L   (rowptr, colidx) of that block, entries in stored order, columns as positions in rows[l - 1]
+      norm[l]   l = 1..L   g.norm on rows[l];   plan[l]: an SpmmPlan of the block when the graph has plans (same arguments)
+      n_query, query_rows (the query's rows in the caller's order), query_pos (their compact rows in rows[L])
+    Needs g.norm; the transposed CSR is not used."""
+
+    def __init__(self, g, query, n_layers):
+        if g.norm is None:
+            raise ValueError("receptive_field() needs the norm (from_coo(norm=True))")
+        L = int(n_layers)
+        if L < 1:
+            raise ValueError("n_layers must be at least 1")
+        q = query.reshape(-1)
+        if q.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or query.dim() != 1:
+            raise ValueError("query must be a 1-D integer tensor of vertex ids")
+        dev = g.rowptr.device
+        q = q.to(dev).long()
+        self.n_query = int(q.numel())
+        if self.n_query and (int(q.min()) < 0 or int(q.max()) >= g.n):
+            raise ValueError(f"query holds a vertex id outside [0, {g.n})")
+        r = q if g.nid is None else g.nid[q].long()
+        self.g, self.n, self.n_layers = g, g.n, L
+        member = torch.zeros(g.n, dtype=torch.uint8, device=dev)
+        member[r] = 1
+        self.rows = [None] * (L + 1)
+        self.rows[L] = rows_from_mask(member)
+        self.query_rows = r.to(torch.int32)
+        self.query_pos = rows_to_positions(self.rows[L], g.n)[r].contiguous()
+        self.nnz, self.block, self.norm, self.plan = [0] * (L + 1), [None] * (L + 1), [None] * (L + 1), [None] * (L + 1)
+        for l in range(L, 0, -1):
+            k = int(self.rows[l].numel())
+            self.rows[l - 1], self.nnz[l] = _frontier(g.rowptr, g.colidx, self.rows[l], g.n)
+            pos = rows_to_positions(self.rows[l - 1], g.n)
+            rp, ci, _ = csr_extract_rows(g.rowptr, g.colidx, self.rows[l], col_pos=pos, n_cols=g.n, nnz_capacity=self.nnz[l])
+            self.block[l] = (rp, ci)
+            self.norm[l] = gather_rows(g.norm.reshape(-1, 1), self.rows[l]).reshape(-1) if k else g.norm[:0]
+            if g.plan is not None and k:
+                chunk, max_feat, big_rows = g._plan_args
+                self.plan[l] = SpmmPlan(rp, chunk, max_feat)
+                if big_rows is not None:
+                    self.plan[l].set_big_row_threshold(big_rows)
+        self.compact_rows = torch.arange(int(self.rows[L].numel()), dtype=torch.int32, device=dev)
 
 
 def to_bf16(X, out=None):
@@ -952,4 +1070,57 @@ class GcnStack:
         logits = self.forward(X)
         loss, _ = softmax_ce_rows(logits, target, rows, want_grad=False)
         correct, count = accuracy(logits, target, rows)
+        return loss, correct, count
+
+    def _field_logits(self, X, field):
+        """[len(field.rows[L]), C] logits of the field's unique query rows (compact row k = graph row field.rows[L][k]), each layer a
+        plain product and aggregation on the compact matrices of the field.  Same layout rules as forward (padded: streamed
+        matrices on the 128-float widths, gathered H on its own width), buffers of its own: _saved and _buf are not touched."""
+        L = len(self.W)
+        if not isinstance(field, ReceptiveField) or field.n_layers != L:
+            raise ValueError(f"the stack has {L} layers, the receptive field was built for {getattr(field, 'n_layers', None)}")
+        if field.n != self.g.n or X.shape[0] != self.g.n or X.shape[1] != self.dims[0]:
+            raise ValueError("X must be the full [n, d0] input of the graph the field was built on")
+        d, P, dev = self.dims, self.P, X.device
+
+        def rows_buf(m, width):   # [m, width] zero-filled when a pad exists, on a buffer of at least one row (a device pointer even for m = 0)
+            make = torch.zeros if self.padded else torch.empty
+            return make((max(m, 1), width), dtype=torch.float32, device=dev)[:m]
+
+        m = int(field.rows[0].numel())
+        hp = rows_buf(m, P[0])
+        if m:
+            gather_rows(X, field.rows[0], out=hp[:, :d[0]])     # the only read of the input: rows Q_0
+        for l in range(1, L + 1):
+            m_in, m_out = m, int(field.rows[l].numel())
+            if m_in:
+                H = linear_fwd(hp, self.Wp[l - 1][:d[l]])        # K = P[l-1] (zero pads), N = d[l]: gathered, own width
+            else:   # an empty frontier: a block of no entries over one row nobody reads (the aggregation wants a device pointer)
+                H = torch.zeros((1, d[l]), dtype=torch.float32, device=dev)
+            Yp = rows_buf(m_out, P[l])
+            if m_out:
+                rp, ci = field.block[l]
+                spmm(rp, ci, H, out=Yp[:, :d[l]], rowscale=field.norm[l], bias=self.b[l - 1], plan=field.plan[l], n_rows=m_out,
+                     relu_out=l < L)
+            hp, m = Yp, m_out
+        return hp[:, :d[L]]
+
+    def predict(self, X, field):
+        """Logits [len(query), C] of the field's query, one row per query entry in the caller's order, computed on the field's compact
+        matrices: bit for bit forward(X)[field.query_rows].  X: the full [n, d0] input in row order, as forward takes it; only rows
+        field.rows[0] are read.  There is no fallback to the full forward: field.rows / field.nnz say what the call costs."""
+        logits = self._field_logits(X, field)
+        if field.n_query == 0:
+            return torch.empty((0, self.dims[-1]), dtype=torch.float32, device=X.device)
+        return gather_rows(logits, field.query_pos)
+
+    def evaluate_field(self, X, target, field):
+        """evaluate(X, target, field.rows[L]) from predict's compact logits: (loss over the query's rows as a 1-element tensor, correct
+        predictions among them, their number) -- the same loss bits and the same count.  target: [n] in row order, read at the
+        query's rows only."""
+        logits = self._field_logits(X, field)
+        rows = field.rows[len(self.W)]
+        t = target.reshape(-1)[rows.long()].to(torch.int32).contiguous()
+        loss, _ = softmax_ce_rows(logits, t, field.compact_rows, want_grad=False)
+        correct, count = accuracy(logits, t, field.compact_rows)
         return loss, correct, count

@@ -509,6 +509,48 @@ int gnnx_accuracy_rows_f32(const float *d_logits, int64_t ldx, const int32_t *d_
                            int64_t n_rows, int32_t n_classes, int32_t *d_pred, int64_t *correct_out, void *d_workspace,
                            size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ query inference: receptive fields ---- */
+/*
+ * Logits for a vertex set from its L-hop field instead of a forward over every vertex.  The reference's layer (src/graph.cpp:170-191) is
+ * Y_l = act(norm (.) (A . (Y_{l-1} W_l^T)) + b_l) with the diagonal of A zeroed (graph.cpp:68-75, :172: a vertex is not its own
+ * neighbour), so rows Q_l of Y_l need Y_{l-1} only on Q_{l-1} = the columns stored in rows Q_l of CSR(A); Q_L is the query -- e.g. a
+ * validation or test mask (graph.cpp:130-151 Data::set_mask) evaluated every epoch.  Layer l then runs on compact matrices: the block
+ * of A with rows Q_l and columns Q_{l-1}, norm on Q_l, and X rows Q_0 as the only input read.  Every Q_l is an ASCENDING row list and a
+ * row's compact id is its position in the list; a block keeps each row's entries in STORED ORDER, every aggregation kernel walks a
+ * row in stored order with one accumulator per output element, and every row-parallel product is one k-ascending fmaf chain per
+ * output element: the compact layers give the bits of the full forward on the listed rows.
+ *
+ *   gnnx_frontier_mark      d_mark[c] = 1 for every column c stored in the listed rows (one byte per column, n_cols bytes; bytes of
+ *                           other columns are left as they are: the caller zeroes the mask, or keeps marks to form a union).
+ *                           *nnz_listed_out (HOST) = the number of entries of the listed rows.  gnnx_mask_to_rows turns the mask into
+ *                           the ascending list Q_{l-1}.
+ *   gnnx_rows_to_positions  d_pos[0..n) = -1 ("not in the set"), then d_pos[d_rows[k]] = k.
+ *   gnnx_csr_extract_rows   the CSR of the n_listed listed rows: d_rowptr_out [n_listed + 1] = exclusive scan of their lengths;
+ *                           d_colidx_out[p] = d_col_pos[c] for the entries' columns c in stored order (d_col_pos NULL: c itself; else
+ *                           a position table over [0, n_cols)); d_vals_out carried along when d_vals is given (both or neither).
+ *                           *nnz_out (HOST) = the entries of the listed rows -- set even when nnz_capacity (the capacity of
+ *                           d_colidx_out / d_vals_out in entries) is too small, which is GNNX_ERR_INVALID_ARG with nothing written,
+ *                           never a truncated CSR.  n_listed == 0 is a valid result: d_rowptr_out = [0].
+ *
+ * d_rows: ascending, no repeats, each in [0, n_rows) -- checked on the device, GNNX_ERR_INDEX_RANGE otherwise.  A stored column outside
+ * [0, n_cols), or one whose position is "not in the set", is GNNX_ERR_INDEX_RANGE, never a wrong index.  Negative sizes are
+ * GNNX_ERR_INVALID_ARG before any device is touched.  Work is dealt in the non-zero domain of the LISTED rows (scan of the listed
+ * lengths, 64 entries per wavefront, owning row by search): a hub row is spread over many wavefronts.  Cost O(n_listed + entries of
+ * the listed rows), plus the O(n) fill of gnnx_rows_to_positions; nothing is O(nnz of the graph).  All three synchronise `stream`.
+ */
+int gnnx_frontier_mark_workspace(int64_t n_listed, size_t *bytes);
+int gnnx_frontier_mark(const int32_t *d_rowptr, const int32_t *d_colidx, int32_t n_rows, int32_t n_cols, const int32_t *d_rows,
+                       int64_t n_listed, uint8_t *d_mark, int64_t *nnz_listed_out, void *d_workspace, size_t workspace_bytes,
+                       void *stream);
+int gnnx_rows_to_positions_workspace(size_t *bytes);
+int gnnx_rows_to_positions(const int32_t *d_rows, int64_t n_listed, int64_t n, int32_t *d_pos, void *d_workspace, size_t workspace_bytes,
+                           void *stream);
+int gnnx_csr_extract_rows_workspace(int64_t n_listed, size_t *bytes);
+int gnnx_csr_extract_rows(int32_t n_rows, int32_t n_cols, const int32_t *d_rowptr, const int32_t *d_colidx, const float *d_vals,
+                          const int32_t *d_rows, int64_t n_listed, const int32_t *d_col_pos, int32_t *d_rowptr_out,
+                          int32_t *d_colidx_out, float *d_vals_out, int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */
