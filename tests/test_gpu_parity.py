@@ -133,6 +133,8 @@ def make_graph(env, n, e, seed, kind="rmat"):
                                    (5000, 60000, 64), (5000, 60000, 16), (3000, 20000, 7), (3000, 20000, 1),
                                    (2000, 30000, 512), (2000, 30000, 300), (1000, 5000, 33)])
 def test_spmm_forward_backward_bit_exact_vs_oracle(env, n, e, F):
+    """The bench's widths and a few narrow ones against the oracle; the widths this list does not carry -- every lane group, both edges
+    of its range, ragged feature tiles, unaligned calls -- are tests/test_gpu_spmm_dispatch.py."""
     ops = env["ops"]
     src, dst, rp, ci, g = make_graph(env, n, e, seed=7 + F)
     assert np.array_equal(host(g.rowptr), rp.astype(np.int32)) and np.array_equal(host(g.colidx), ci)
