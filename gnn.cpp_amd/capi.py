@@ -138,6 +138,10 @@ _SIGS = {
     "gnnx_softmax_ce_colsum_f32": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_softmax_ce_partial_f32": [_vp, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_sgd_step_f32": [_vp, _vp, _i64, _f32, _f32, _vp],
+    "gnnx_bce_logits_workspace": [_i64, C.POINTER(_sz)],
+    "gnnx_bce_logits_f32": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp],
+    "gnnx_sddmm_csr_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "gnnx_csr_transpose_map": [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnnx_mask_to_rows_workspace": [_i64, C.POINTER(_sz)],
     "gnnx_mask_to_rows": [_vp, _i64, _vp, C.POINTER(_i32), _vp, _sz, _vp],
     "gnnx_csr_restrict_workspace": [_i32, _i64, C.POINTER(_sz)],

@@ -319,3 +319,65 @@ GNNX_API int gnnx_sgd_step_f32(float *d_param, const float *d_grad, int64_t n, f
     GNNX_LAUNCH_CHECK();
     return GNNX_OK;
 }
+
+// ---- binary cross-entropy on logits: the loss over scored pairs (link prediction; include/gnnx.h) --------------------------------
+//   l_p = max(x, 0) - x * y + log1p(exp(-|x|))          the stable form: exp never sees a positive argument, no inf / NaN for any
+//                                                        finite x (x = +-100: l = 100 or 0 up to exp(-100))
+//   ds_p = (sigmoid(x) - y) / n_total,  sigmoid from exp(-|x|) as well
+// One pass: a fixed grid of kSumBlocks workgroups strides the entries, a thread adds its terms in index order, the workgroup folds
+// its 256 sums in a fixed tree, sum_stage2 adds the kSumBlocks partials in order (the scheme of the softmax loss above and of
+// gnnx_colsum_f32: the same bits on every run).
+namespace {
+
+__global__ __launch_bounds__(256) void bce_logits_kernel(const float *x, const float *y, int64_t n, float inv_n, float *partial, float *dx)
+{
+    __shared__ float red[256];
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float xi = x[i], yi = y[i];
+        const float e = expf(-fabsf(xi));   // in (0, 1]
+        if (partial) acc += (fmaxf(xi, 0.f) - xi * yi) + log1pf(e);
+        if (dx) {
+            const float sig = xi >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+            dx[i] = (sig - yi) * inv_n;
+        }
+    }
+    if (!partial) return;
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+}  // namespace
+
+GNNX_API int gnnx_bce_logits_workspace(int64_t n, size_t *bytes)
+{
+    GNNX_REQUIRE(bytes && n >= 0, GNNX_ERR_INVALID_ARG, "bad arguments");
+    *bytes = sizeof(float) * kSumBlocks;
+    return GNNX_OK;
+}
+
+GNNX_API int gnnx_bce_logits_f32(const float *d_scores, const float *d_target, int64_t n, int64_t n_total, float *d_loss, float *d_dscores,
+                                 void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    GNNX_REQUIRE(n > 0, GNNX_ERR_INVALID_ARG, "empty score list");
+    GNNX_REQUIRE(n_total >= n, GNNX_ERR_INVALID_ARG, "n_total < n");
+    GNNX_REQUIRE(d_scores && d_target, GNNX_ERR_INVALID_ARG, "null pointer");
+    if (!d_loss && !d_dscores) return GNNX_OK;
+    GNNX_REQUIRE(!d_loss || (d_workspace && workspace_bytes >= sizeof(float) * kSumBlocks), GNNX_ERR_WORKSPACE, "workspace %zu < required %zu",
+                 workspace_bytes, sizeof(float) * kSumBlocks);
+    hipStream_t st = as_stream(stream);
+    float *partial = d_loss ? static_cast<float *>(d_workspace) : nullptr;
+    const float inv_n = 1.0f / (float)n_total;
+    hipLaunchKernelGGL(bce_logits_kernel, dim3(kSumBlocks), dim3(256), 0, st, d_scores, d_target, n, inv_n, partial, d_dscores);
+    GNNX_LAUNCH_CHECK();
+    if (d_loss) {
+        hipLaunchKernelGGL(sum_stage2, dim3(1), dim3(64), 0, st, partial, kSumBlocks, inv_n, d_loss);
+        GNNX_LAUNCH_CHECK();
+    }
+    return GNNX_OK;
+}

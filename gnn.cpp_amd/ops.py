@@ -481,6 +481,89 @@ def spmm(rowptr, colidx, X, out=None, vals=None, colscale=None, rowscale=None, b
     return out
 
 
+def sddmm(rowptr, colidx, L, R, rowscale=None, colscale=None, out=None):
+    """gnnx_sddmm_csr_f32: out[p] = (<L[i,:], R[c_p,:]> * rowscale[i]) * colscale[c_p] for every stored entry p of row i -- float32
+    [nnz].  L: [n_rows, F], R: [n_cols, F] (L is R is allowed).  The dot product's order is a function of F alone (include/gnnx.h)."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    n_cols, F = R.shape
+    if L.shape[0] != n_rows or L.shape[1] != F:
+        raise capi.GnnxError(-2, "sddmm", f"L is {tuple(L.shape)}, the pattern has {n_rows} rows and R {F} features")
+    if out is None:
+        out = torch.empty(nnz, dtype=torch.float32, device=R.device)
+    assert out.numel() == nnz and out.is_contiguous()
+    capi.call("gnnx_sddmm_csr_f32", n_rows, n_cols, F, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(L) if L.numel() else None, _ld(L),
+              _ptr(R) if R.numel() else None, _ld(R), _ptr(rowscale), _ptr(colscale), _ptr(out) if nnz else None, _stream())
+    return out
+
+
+def spmm_vals_grad(rowptr, colidx, G, X, rowscale=None, colscale=None):
+    """dL/dvals of Y = rowscale (.) sum_p vals[p] * colscale[c_p] * X[c_p,:] (spmm) for the upstream gradient G = dL/dY: the dense
+    G . X^T of the reference's MatMul::_backward (operation.h:516-523) on the stored entries only -- sddmm(L = G, R = X)."""
+    return sddmm(rowptr, colidx, G, X, rowscale=rowscale, colscale=colscale)
+
+
+def csr_transpose_map(rowptr, colidx, rowptr_t, colidx_t):
+    """gnnx_csr_transpose_map: int32 [nnz], map_t[q] = the position in CSR(A) of entry q of CSR(A^T); vals[map_t.long()] (or
+    gather_rows on a [nnz, 1] view) carries per-entry values to the transposed order.  GnnxError (status -3) when the two are not
+    each other's transpose with strictly ascending rows."""
+    n_rows, n_cols, nnz = int(rowptr.numel() - 1), int(rowptr_t.numel() - 1), int(colidx.numel())
+    if int(colidx_t.numel()) != nnz:
+        raise capi.GnnxError(-3, "csr_transpose_map", f"{nnz} entries against {int(colidx_t.numel())} in the transposed pattern")
+    map_t = torch.empty(nnz, dtype=torch.int32, device=rowptr.device)
+    capi.call("gnnx_csr_transpose_map", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(rowptr_t),
+              _ptr(colidx_t) if nnz else None, _ptr(map_t) if nnz else None, _stream())
+    return map_t
+
+
+def bce_logits(scores, target, want_grad=True, n_total=None, grad_out=None):
+    """gnnx_bce_logits_f32: (mean binary cross-entropy of the logits `scores` against the float targets -- soft labels allowed -- as a
+    1-element device tensor, dscores = (sigmoid(scores) - target) / n_total or None).  n_total: the divisor (default: len(scores))."""
+    n = int(scores.numel())
+    assert scores.is_contiguous() and target.is_contiguous() and target.dtype == torch.float32 and int(target.numel()) == n
+    loss = torch.empty(1, dtype=torch.float32, device=scores.device)
+    d = (torch.empty_like(scores) if grad_out is None else grad_out) if want_grad else None
+    assert d is None or (d.is_contiguous() and d.numel() == n)
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_bce_logits_workspace", n, C.byref(wsb))
+    ws = _workspace(wsb.value, scores.device, "bce")
+    capi.call("gnnx_bce_logits_f32", _ptr(scores) if n else None, _ptr(target) if n else None, n, int(n if n_total is None else n_total),
+              _ptr(loss), _ptr(d), _ptr(ws), wsb.value, _stream())
+    return loss, d
+
+
+class EdgeSet:
+    """Labelled vertex pairs as a sparse pattern: the CSR of the pairs (rowptr, colidx) with the per-entry targets `target`, the
+    transposed pattern (rowptr_t, colidx_t) and map_t (csr_transpose_map) -- what GcnStack.link_scores / link_train_step score, and what
+    sends the score gradient back to both endpoints without atomics."""
+
+    def __init__(self, n, rowptr, colidx, target, rowptr_t, colidx_t, map_t):
+        self.n = int(n)
+        self.rowptr, self.colidx, self.target = rowptr, colidx, target
+        self.rowptr_t, self.colidx_t, self.map_t = rowptr_t, colidx_t, map_t
+        self.nnz = int(colidx.numel())
+
+    @classmethod
+    def from_pairs(cls, src, dst, label, n):
+        """src, dst: int32 endpoints in the graph's ROW order (g.nid[v] of vertex ids on a relabelled graph); label: float32 per pair
+        (1 = an edge, 0 = a non-edge; soft labels allowed); n: the number of vertices.  The pattern is built with
+        csr_from_coo_weighted(src, dst, label, DIAG_KEEP): of duplicate pairs the LAST one in the list wins, and explicit 0 labels stay
+        as entries.  So negatives concatenated BEFORE the positives lose a collision with a positive: a sampled "non-edge" that is in
+        fact an edge is scored as the edge it is.  Uniform negatives: rmat_edges(seed, n, k, a=.25, b=.25, c=.25)."""
+        src, dst = src.to(torch.int32).contiguous(), dst.to(torch.int32).contiguous()
+        label = label.to(torch.float32).contiguous()
+        rowptr, colidx, target = csr_from_coo_weighted(src, dst, label, n, DIAG_KEEP)
+        rowptr_t, colidx_t, _ = csr_from_coo_weighted(dst, src, label, n, DIAG_KEEP)
+        return cls(n, rowptr, colidx, target, rowptr_t, colidx_t, csr_transpose_map(rowptr, colidx, rowptr_t, colidx_t))
+
+    def to_transposed(self, vals, out=None):
+        """Per-entry values of the pattern in the transposed pattern's order: out[q] = vals[map_t[q]]."""
+        if out is None:
+            out = torch.empty(self.nnz, dtype=torch.float32, device=vals.device)
+        if self.nnz:
+            gather_rows(vals.reshape(-1, 1), self.map_t, out=out.reshape(-1, 1))
+        return out
+
+
 def gemm(A, B, transA=False, transB=False, out=None, alpha=1.0, beta=0.0):
     """gnnx_gemm_f32: C = alpha * op(A) . op(B) + beta * C (row-major, no operand is transposed in memory)."""
     M = A.shape[1] if transA else A.shape[0]
@@ -1061,6 +1144,33 @@ class GcnStack:
         logits = self.forward(X, labelled=labelled)
         loss, G = softmax_ce_rows(logits, target, labelled.rows, colsum_out=self.db[-1], grad_out=self.masked_grad_buffer(labelled))
         self.backward(G, input_grad=False, have_last_bias_grad=True, labelled=labelled)
+        self.step(lr, weight_decay)
+        return loss
+
+    def link_scores(self, X, edges):
+        """Inner-product decoder on the stack's embeddings Z = forward(X): the logit <Z[i], Z[c]> of every pair (i, c) of the EdgeSet, in
+        the order of its pattern (edges.rowptr / edges.colidx) -- sddmm(edges.rowptr, edges.colidx, Z, Z)."""
+        Z = self.forward(X)
+        return sddmm(edges.rowptr, edges.colidx, Z, Z)
+
+    def link_grad(self, Z, edges, ds, out=None):
+        """dZ of sum_p loss_p(<Z[i_p], Z[c_p]>) from ds = dloss/dscores: row i collects ds[p] * Z[c_p] over its own entries (an
+        aggregation on the pattern with vals = ds), then ds[p] * Z[i_p] over the entries that name it as a column (the transposed
+        pattern with the mapped values, beta = 1).  No atomics; the order is the aggregation's own contract, the same bits every run."""
+        if out is None:
+            out = self.grad_buffer(Z.shape[0])
+        spmm(edges.rowptr, edges.colidx, Z, out=out, vals=ds)
+        spmm(edges.rowptr_t, edges.colidx_t, Z, out=out, vals=edges.to_transposed(ds), beta=1.0)
+        return out
+
+    def link_train_step(self, X, edges, lr, weight_decay=0.0):
+        """One link-prediction SGD step: forward -> pair scores (sddmm) -> bce_logits against edges.target -> dZ (link_grad, into
+        grad_buffer()) -> backward without an input gradient -> step.  X in the graph's ROW order.  Returns the loss tensor."""
+        Z = self.forward(X)
+        scores = sddmm(edges.rowptr, edges.colidx, Z, Z)
+        loss, ds = bce_logits(scores, edges.target)
+        dZ = self.link_grad(Z, edges, ds)
+        self.backward(dZ, input_grad=False)
         self.step(lr, weight_decay)
         return loss
 

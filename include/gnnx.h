@@ -457,6 +457,17 @@ int gnnx_softmax_ce_partial_f32(const float *d_logits, int64_t ldx, const int32_
                                 int64_t n_total, float *d_loss, float *d_dlogits, int64_t ldd, float *d_colsum, void *d_workspace,
                                 size_t workspace_bytes, void *stream);
 int gnnx_sgd_step_f32(float *d_param, const float *d_grad, int64_t n, float lr, float weight_decay, void *stream);
+/* Binary cross-entropy on logits -- the loss over scored pairs (link prediction: the inner-product decoder of the graph
+ * auto-encoder scores a pair with gnnx_sddmm_csr_f32; the reference has no counterpart, its one loss is nn.cpp:442-453):
+ *   loss       = (1 / n_total) sum_p [ max(x_p, 0) - x_p y_p + log1p(exp(-|x_p|)) ]    the stable form: no inf / NaN for any finite x
+ *   dscores[p] = (sigmoid(x_p) - y_p) / n_total
+ * d_target is float: soft labels are allowed.  n_total >= n is the divisor (n on one GPU).  d_loss (one device float) and d_dscores
+ * [n] may each be NULL.  The sum is two-stage on a fixed grid in a fixed order (as gnnx_colsum_f32): the same bits on every run.
+ * Asynchronous.  n == 0 is GNNX_ERR_INVALID_ARG, never a NaN loss (as gnnx_softmax_ce_rows_f32).  Workspace:
+ * gnnx_bce_logits_workspace() bytes. */
+int gnnx_bce_logits_workspace(int64_t n, size_t *bytes);
+int gnnx_bce_logits_f32(const float *d_scores, const float *d_target, int64_t n, int64_t n_total, float *d_loss, float *d_dscores,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ semi-supervised training: masks ---- */
 /*
@@ -550,6 +561,50 @@ int gnnx_csr_extract_rows(int32_t n_rows, int32_t n_cols, const int32_t *d_rowpt
                           const int32_t *d_rows, int64_t n_listed, const int32_t *d_col_pos, int32_t *d_rowptr_out,
                           int32_t *d_colidx_out, float *d_vals_out, int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace,
                           size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ edge scores (SDDMM) ---------- */
+/*
+ * A value per STORED entry from the two endpoint rows -- the other half of message passing (the aggregation is a row per vertex from
+ * its entries):
+ *   out[p] = (dot_p * rowscale[i]) * colscale[c_p],   dot_p = <L[i,:], R[c_p,:]>   for entry p of row i of the CSR pattern.
+ * Each scale is skipped when NULL; each multiply is rounded on its own.  L: [n_rows, F] ld ldl.  R: [n_cols, F] ld ldr.  out: [nnz].
+ * Asynchronous on `stream`; nothing is allocated or synchronised.  The CSR and nnz (= rowptr[n_rows]) are TRUSTED, as the
+ * aggregation trusts its CSR (gnnx_csr_validate is the check).  d_out aliases nothing; L == R is allowed (link scores <z_i, z_c>).
+ * n_feat == 0 writes +0 to d_out; nnz == 0 is GNNX_OK with no launch.  Null pointers, negative sizes and ld < F are
+ * GNNX_ERR_INVALID_ARG before any device call.
+ *
+ * The ORDER of dot_p is a function of F alone (every operation separately rounded fp32; -ffp-contract=off):
+ *   - Split the row into Q = ceil(F/4) chunks.  Chunk q holds features 4q .. min(4q+3, F-1).
+ *   - G is the smallest power of two with G >= Q, capped at 64 (F <= 4 gives G = 1).
+ *   - Lane l < G starts from +0.  For q = l, l+G, l+2G, ... < Q, and within a chunk in ascending f, it does
+ *     acc_l = acc_l + (L[i,f] * R[c,f]).  The product is rounded first, then the sum.
+ *   - A lane with no chunk holds +0.
+ *   - For s = 1, 2, 4, ..., G/2, every lane does acc_l = acc_l + acc_{l xor s}.  IEEE addition is commutative, so all lanes end
+ *     with the same bits.
+ *   - dot_p = acc_0.
+ * This is a vec4 lane group: F = 256 is one wavefront per entry with one 16-byte load per lane, F = 128 two entries per wavefront.
+ * The order does not depend on alignment: rows that fail the vec4 conditions (F % 4 != 0, a pointer or ld not 16-byte aligned) take
+ * scalar loads with the same feature-to-lane assignment and give the same bits.  tests/sddmm_ref.py restates the order in NumPy and
+ * the GPU tests hold the kernel to it bit for bit.  Work is dealt in the non-zero domain (a fixed number of entries per wavefront,
+ * the owning row by a search in rowptr): a hub row spreads over the device, no plan.
+ *
+ * Second use -- the gradient of the aggregation's per-entry values: for Y = rowscale (.) sum_p vals[p] * colscale[c_p] * X[c_p,:]
+ * (gnnx_spmm_csr_f32) with upstream gradient G,
+ *   dL/dvals = gnnx_sddmm_csr_f32(L = G, R = X, rowscale, colscale).
+ * The reference computes this gradient as the dense N x N product G . X^T (MatMul::_backward, reference operation.h:516-523); on a CSR
+ * adjacency only the stored entries exist, and the product restricted to them is this call.
+ *
+ * gnnx_csr_transpose_map: for entry q = (c, r) of CSR(A^T), map_t[q] = the position p of (r, c) in CSR(A), found by binary search
+ * in row r.  Both CSRs must have ascending columns and no duplicates (what the COO builds produce).  Built once per pattern;
+ * synchronises `stream`.  GNNX_ERR_INDEX_RANGE -- never a wrong index -- when an entry has no partner, a row is not strictly ascending
+ * (e.g. a relabelled graph stored in original-id order), or rowptr[n_rows], rowptr_t[n_cols] and nnz disagree.  Per-entry values move
+ * to the transposed order with a 1-column gather: gnnx_gather_rows_f32(vals as [nnz, 1], map_t, n_feat = 1).
+ */
+int gnnx_sddmm_csr_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                       const float *d_L, int64_t ldl, const float *d_R, int64_t ldr, const float *d_rowscale, const float *d_colscale,
+                       float *d_out, void *stream);
+int gnnx_csr_transpose_map(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                           const int32_t *d_rowptr_t, const int32_t *d_colidx_t, int32_t *d_map_t, void *stream);
 
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
