@@ -1,0 +1,629 @@
+// Softmax over the stored entries of each CSR row, forward and backward -- include/gnnx.h "edge softmax".
+//   t_p = (scores[p] + rowterm[i]) + colterm[c_p];  e_p = leaky_relu(t_p);  m_i = max_p e_p;  x_p = expf(e_p - m_i);
+//   z_i = row sum of x_p;  alpha_p = x_p / z_i                                              for entry p of row i
+// The ORDER of a row sum is part of the contract and a function of the row length d alone (the header states it): d <= S = 4096
+// entries meet in G = min(64, pow2 >= d) virtual lanes (lane l adds entries l, l + G, ... ascending from +0, then the xor butterfly
+// s = 1 .. G / 2); a longer row is cut into segments of S entries, each summed with G = 64, and the segment sums are added in
+// ascending order.  How rows and segments map to wavefronts is NOT in the result:
+//   * rows of d <= kShortW entries: kShortW lanes per row (64 / kShortW rows per wavefront), one entry per lane, everything in
+//     registers -- the bulk of a power-law graph's rows.  The same kernel appends every longer row to one of two lists in the
+//     caller's workspace (one global atomic per workgroup of 128 rows for the long rows, hubs are rare);
+//   * long rows, kShortW < d <= S: a wavefront per listed row; up to 64 entries stay in registers, a longer row walks its entries
+//     in three passes and parks e_p, then x_p, in d_out between them (each lane re-reads only what it stored itself): the column
+//     term is gathered once;
+//   * hub rows, d > S: a fixed grid strides over the (hub, segment) pairs listed in the workspace; the maximum, the sum and the
+//     division are separate launches because each needs the previous one complete for the whole row.  The segments' partial results
+//     sit in the workspace and are combined in the fixed order by one lane per hub.
+// Every launch is on the caller's stream and every ordering is a stream ordering; nothing is allocated or synchronised.  The
+// order in which rows land in the lists varies from call to call, the values do not: a row's result never depends on its slot.
+#include "gnnx_common.h"
+
+#pragma clang fp contract(off)
+
+using namespace gnnx;
+
+namespace {
+
+constexpr int kSeg = 4096;          // S: the contract's segment length
+constexpr int kShortW = 16;         // lanes per row of the short-row kernel
+constexpr int kShortR = 8;          // rows per lane group of the short-row kernel
+constexpr int kShortRowsPerBlock = (256 / kShortW) * kShortR;
+constexpr int kLongWaves = 8192;    // wavefronts of the long-row kernel (grid stride over the list)
+constexpr int kHubWaves = 4096;     // wavefronts of the hub kernels (stride over (hub, segment) pairs)
+constexpr int kCounters = 16;       // int32 words in front of the workspace: [0] long rows, [1] hubs, [2] segments
+
+// the three operands of the pre-activation (each may be null, not all three) and the slope
+struct Pre {
+    const int32_t *colidx;
+    const float *scores, *rowterm, *colterm;
+    int64_t rs, cs;
+    float slope;
+};
+
+// the caller's workspace, carved
+struct Lists {
+    int32_t *counters;      // kCounters words, zeroed by a memset on the stream in front of the first kernel
+    int32_t *long_rows;     // [cap_long]
+    int32_t *hub_rows;      // [cap_hub]; -1: a hub whose segments did not fit (only a broken CSR can do that)
+    int32_t *hub_seg0;      // [cap_hub] first slot of the hub's segments in `part`
+    float *hub_val;         // [cap_hub] the row's maximum, later its sum (forward); dot_i (backward)
+    float *part;            // [cap_seg] one value per segment
+    int32_t *seg_hub;       // [cap_seg] the hub (its slot in hub_rows) that a segment slot belongs to; -1: none
+    int64_t cap_long, cap_hub, cap_seg;
+};
+
+size_t carve(int32_t n_rows, int64_t nnz, void *base, Lists *out)
+{
+    Lists w{};
+    w.cap_long = nnz / (kShortW + 1) < n_rows ? nnz / (kShortW + 1) : n_rows;   // rows of more than kShortW entries
+    w.cap_hub = nnz / (kSeg + 1) < n_rows ? nnz / (kSeg + 1) : n_rows;          // rows of more than S entries
+    w.cap_seg = nnz / kSeg + w.cap_hub;                                         // sum of ceil(d / S) <= nnz / S + hubs
+    char *p = static_cast<char *>(base);
+    size_t off = 0;
+    auto take = [&](size_t words) {
+        char *q = p ? p + off : nullptr;
+        off += 4 * words;
+        return q;
+    };
+    w.counters = reinterpret_cast<int32_t *>(take(kCounters));
+    w.long_rows = reinterpret_cast<int32_t *>(take((size_t)w.cap_long));
+    w.hub_rows = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
+    w.hub_seg0 = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
+    w.hub_val = reinterpret_cast<float *>(take((size_t)w.cap_hub));
+    w.part = reinterpret_cast<float *>(take((size_t)w.cap_seg));
+    w.seg_hub = reinterpret_cast<int32_t *>(take((size_t)w.cap_seg));
+    if (out) *out = w;
+    return (off + 255) & ~(size_t)255;
+}
+
+// t_p = (scores[p] + rowterm[i]) + colterm[c_p], a null operand skipped; rt = rowterm[i * rs], loaded once per row
+__device__ __forceinline__ float pre_activation(const Pre &a, int64_t p, float rt)
+{
+    float t = 0.f;
+    if (a.scores) {
+        t = a.scores[p];
+        if (a.rowterm) t = t + rt;
+    } else if (a.rowterm) {
+        t = rt;
+    }
+    if (a.colterm) {
+        const float ct = a.colterm[(int64_t)a.colidx[p] * a.cs];
+        t = (a.scores || a.rowterm) ? t + ct : ct;
+    }
+    return t;
+}
+
+__device__ __forceinline__ float leaky(float t, float slope) { return t > 0.f ? t : t * slope; }
+
+// f(k, t_p) for the entries k = l, l + 64, ... < n of a row piece whose first entry is b, in ascending k; the gathers of four entries
+// are issued before the first is consumed (a lane's chain of dependent column-term loads is what a long row waits for)
+template <class F>
+__device__ __forceinline__ void for_lane_entries(const Pre &a, int64_t b, int64_t n, float rt, int l, F f)
+{
+    for (int64_t k0 = l; k0 < n; k0 += 4 * 64) {
+        float t[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int64_t k = k0 + 64 * j;
+            t[j] = k < n ? pre_activation(a, b + k, rt) : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int64_t k = k0 + 64 * j;
+            if (k < n) f(k, t[j]);
+        }
+    }
+}
+
+// G of a row or segment of d <= S entries: the smallest power of two >= d, capped at 64
+__device__ __forceinline__ int lanes_of(int64_t d)
+{
+    int G = 1;
+    while (G < d && G < 64) G <<= 1;
+    return G;
+}
+
+// acc_l = acc_l + acc_{l xor s} for s = 1 .. G / 2 (G <= MAXG): every lane runs every shuffle, a stage with s >= G changes nothing.
+// Partners stay inside the aligned group of G lanes, so lane groups with different G share a wavefront.
+template <int MAXG>
+__device__ __forceinline__ float add_lanes(float acc, int G)
+{
+#pragma unroll
+    for (int s = 1; s < MAXG; s <<= 1) {
+        const float o = __shfl_xor(acc, s, 64);
+        if (s < G) acc = acc + o;
+    }
+    return acc;
+}
+
+template <int W>
+__device__ __forceinline__ float max_lanes(float m)
+{
+#pragma unroll
+    for (int s = 1; s < W; s <<= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+    return m;
+}
+
+// Rows of one workgroup of the short-row kernels: 256 / kShortW lane groups, kShortR rows each; group g takes rows
+// first + g, first + g + 16, ... so that neighbouring groups read neighbouring rowptr words.
+struct ShortRows {
+    int32_t row[kShortR];   // -1: behind the last row
+    int32_t b[kShortR];     // the row's first entry
+    int32_t d[kShortR];     // its length
+};
+
+__device__ __forceinline__ ShortRows load_short_rows(const int32_t *__restrict__ rowptr, int32_t n_rows)
+{
+    ShortRows r;
+    const int64_t first = (int64_t)blockIdx.x * kShortRowsPerBlock + threadIdx.x / kShortW;
+#pragma unroll
+    for (int j = 0; j < kShortR; j++) {
+        const int64_t row = first + j * (256 / kShortW);
+        const bool in = row < n_rows;
+        r.row[j] = in ? (int32_t)row : -1;
+        r.b[j] = in ? rowptr[row] : 0;
+        const int32_t d = in ? rowptr[row + 1] - r.b[j] : 0;
+        r.d[j] = d < 0 ? 0 : d;
+    }
+    return r;
+}
+
+// Every row of the workgroup with more than kShortW entries goes to the lists.  Long rows: the workgroup counts them in LDS and
+// reserves its run of slots with ONE global atomic (one per row, or per wavefront, serialises on the counter's address: a tenth of a
+// power-law graph's rows are long).  Hubs are rare: an atomic each, which also reserves the hub's run of segment slots.
+__device__ __forceinline__ void classify(const Lists &w, const ShortRows &r)
+{
+    __shared__ int32_t s_count, s_base;
+    const bool leader = (threadIdx.x & (kShortW - 1)) == 0;
+    if (threadIdx.x == 0) s_count = 0;
+    __syncthreads();
+    int32_t slot[kShortR];
+#pragma unroll
+    for (int j = 0; j < kShortR; j++) {
+        slot[j] = -1;
+        if (!leader || r.d[j] <= kShortW) continue;
+        if (r.d[j] <= kSeg) {
+            slot[j] = atomicAdd(&s_count, 1);
+            continue;
+        }
+        const int32_t nseg = (r.d[j] + kSeg - 1) / kSeg;
+        const int32_t h = atomicAdd(&w.counters[1], 1);
+        const int32_t s0 = atomicAdd(&w.counters[2], nseg);
+        const bool fits = h < w.cap_hub && (int64_t)s0 + nseg <= w.cap_seg;   // holds on a valid CSR
+        if (h < w.cap_hub) {
+            w.hub_rows[h] = fits ? r.row[j] : -1;
+            w.hub_seg0[h] = fits ? s0 : 0;
+        }
+        for (int64_t s = s0; s < (int64_t)s0 + nseg && s < w.cap_seg; s++) w.seg_hub[s] = fits ? h : -1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_count > 0) s_base = atomicAdd(&w.counters[0], s_count);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kShortR; j++) {
+        if (slot[j] < 0) continue;
+        const int64_t at = (int64_t)s_base + slot[j];
+        if (at < w.cap_long) w.long_rows[at] = r.row[j];   // the bound holds on a valid CSR
+    }
+}
+
+__device__ __forceinline__ int64_t listed(const int32_t *counter, int64_t cap)
+{
+    const int64_t n = *counter;
+    return n < cap ? n : cap;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------
+// kShortW lanes per row, lane l holds entry l: e, x and the sum never leave registers.  The loads of a group's kShortR rows are all
+// issued before the first is consumed.
+__global__ __launch_bounds__(256) void fwd_short_kernel(int32_t n_rows, const int32_t *__restrict__ rowptr, Pre a, int unnorm,
+                                                        float *__restrict__ out, float *__restrict__ rowmax, float *__restrict__ rowsum, Lists w)
+{
+    const int l = threadIdx.x & (kShortW - 1);
+    const ShortRows r = load_short_rows(rowptr, n_rows);
+    float e[kShortR];
+#pragma unroll
+    for (int j = 0; j < kShortR; j++) {
+        e[j] = -INFINITY;
+        if (r.d[j] <= kShortW && l < r.d[j]) {   // this kernel computes the row and this lane holds an entry
+            const float rt = a.rowterm ? a.rowterm[(int64_t)r.row[j] * a.rs] : 0.f;
+            e[j] = leaky(pre_activation(a, (int64_t)r.b[j] + l, rt), a.slope);
+        }
+    }
+    classify(w, r);
+#pragma unroll
+    for (int j = 0; j < kShortR; j++) {
+        const bool own = r.row[j] >= 0 && r.d[j] <= kShortW;
+        const bool have = own && l < r.d[j];
+        const float m = max_lanes<kShortW>(e[j]);
+        float acc = 0.f;
+        float x = 0.f;
+        if (have) {
+            x = expf(e[j] - m);
+            acc = acc + x;
+        }
+        const float z = add_lanes<kShortW>(acc, lanes_of(r.d[j]));
+        if (have) out[(int64_t)r.b[j] + l] = unnorm ? x : __fdiv_rn(x, z);
+        if (own && l == 0) {
+            if (rowmax) rowmax[r.row[j]] = m;   // an empty row: -inf
+            if (rowsum) rowsum[r.row[j]] = z;   //               +0
+        }
+    }
+}
+
+// a wavefront per listed row of kShortW < d <= S entries
+__global__ __launch_bounds__(256) void fwd_long_kernel(const int32_t *__restrict__ rowptr, Pre a, int unnorm, float *__restrict__ out,
+                                                       float *__restrict__ rowmax, float *__restrict__ rowsum, Lists w)
+{
+    const int l = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
+    const int64_t n_long = listed(&w.counters[0], w.cap_long);
+    for (int64_t i = wave; i < n_long; i += n_waves) {
+        const int32_t row = w.long_rows[i];
+        const int64_t b = rowptr[row], d = (int64_t)rowptr[row + 1] - b;
+        const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
+        const int G = lanes_of(d);
+        float m, z;
+        if (d <= 64) {   // one entry per lane
+            const bool have = l < d;
+            const float e = have ? leaky(pre_activation(a, b + l, rt), a.slope) : -INFINITY;
+            m = max_lanes<64>(e);
+            float acc = 0.f, x = 0.f;
+            if (have) {
+                x = expf(e - m);
+                acc = acc + x;
+            }
+            z = add_lanes<64>(acc, G);
+            if (have) out[b + l] = unnorm ? x : __fdiv_rn(x, z);
+        } else {         // G = 64: lane l owns entries l, l + 64, ...; e, then x, wait in out[] for the next pass
+            m = -INFINITY;
+            for_lane_entries(a, b, d, rt, l, [&](int64_t k, float t) {
+                const float e = leaky(t, a.slope);
+                out[b + k] = e;
+                m = fmaxf(m, e);
+            });
+            m = max_lanes<64>(m);
+            float acc = 0.f;
+            for (int64_t k = l; k < d; k += 64) {
+                const float x = expf(out[b + k] - m);
+                out[b + k] = x;
+                acc = acc + x;
+            }
+            z = add_lanes<64>(acc, 64);
+            if (!unnorm)
+                for (int64_t k = l; k < d; k += 64) out[b + k] = __fdiv_rn(out[b + k], z);
+        }
+        if (l == 0) {
+            if (rowmax) rowmax[row] = m;
+            if (rowsum) rowsum[row] = z;
+        }
+    }
+}
+
+// Hub passes: the wavefronts stride over the segment slots the short-row kernel handed out; a slot names its hub, the hub its row
+// and its first slot.  b, n: the segment's first entry and length; part[s]: its slot.
+#define GNNX_FOR_HUB_SEGMENTS(BODY)                                                                                \
+    const int l = threadIdx.x & 63;                                                                                \
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;        \
+    const int64_t n_slots = listed(&w.counters[2], w.cap_seg);                                                     \
+    for (int64_t slot = wave; slot < n_slots; slot += n_waves) {                                                   \
+        const int32_t h = w.seg_hub[slot];                                                                         \
+        if (h < 0) continue;                                                                                       \
+        const int32_t row = w.hub_rows[h];                                                                         \
+        const int64_t s = slot - w.hub_seg0[h];                                                                    \
+        const int64_t rb = rowptr[row], d = (int64_t)rowptr[row + 1] - rb;                                         \
+        const int64_t b = rb + s * kSeg;                                                                           \
+        const int64_t n = d - s * kSeg < kSeg ? d - s * kSeg : kSeg;                                               \
+        float *part = w.part + w.hub_seg0[h];                                                                      \
+        (void)part;                                                                                                \
+        BODY                                                                                                       \
+    }
+
+// e_p -> out, the segment's maximum -> part
+__global__ __launch_bounds__(256) void fwd_hub_max_kernel(const int32_t *__restrict__ rowptr, Pre a, float *__restrict__ out, Lists w)
+{
+    GNNX_FOR_HUB_SEGMENTS({
+        const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
+        float m = -INFINITY;
+        for_lane_entries(a, b, n, rt, l, [&](int64_t k, float t) {
+            const float e = leaky(t, a.slope);
+            out[b + k] = e;
+            m = fmaxf(m, e);
+        });
+        m = max_lanes<64>(m);
+        if (l == 0) part[s] = m;
+    })
+}
+
+// a wavefront per hub: the maximum of its segments' maxima -> hub_val (and rowmax)
+__global__ __launch_bounds__(256) void hub_combine_max_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ rowmax, Lists w)
+{
+    const int l = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
+    const int64_t n_hub = listed(&w.counters[1], w.cap_hub);
+    for (int64_t h = wave; h < n_hub; h += n_waves) {
+        const int32_t row = w.hub_rows[h];
+        if (row < 0) continue;
+        const int64_t nseg = ((int64_t)rowptr[row + 1] - rowptr[row] + kSeg - 1) / kSeg;
+        const float *part = w.part + w.hub_seg0[h];
+        float m = -INFINITY;
+        for (int64_t s = l; s < nseg; s += 64) m = fmaxf(m, part[s]);
+        m = max_lanes<64>(m);
+        if (l == 0) {
+            w.hub_val[h] = m;
+            if (rowmax) rowmax[row] = m;
+        }
+    }
+}
+
+// x_p = expf(e_p - m) -> out, the segment's sum (G = 64) -> part
+__global__ __launch_bounds__(256) void fwd_hub_exp_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ out, Lists w)
+{
+    GNNX_FOR_HUB_SEGMENTS({
+        const float m = w.hub_val[h];
+        float acc = 0.f;
+        for (int64_t k = l; k < n; k += 64) {
+            const float x = expf(out[b + k] - m);
+            out[b + k] = x;
+            acc = acc + x;
+        }
+        acc = add_lanes<64>(acc, 64);
+        if (l == 0) part[s] = acc;
+    })
+}
+
+// one lane per hub: ((seg_0 + seg_1) + seg_2) + ... -> hub_val and, when given, rows[row]
+__global__ __launch_bounds__(256) void hub_combine_sum_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ rows, Lists w)
+{
+    const int64_t n_hub = listed(&w.counters[1], w.cap_hub);
+    for (int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x; h < n_hub; h += (int64_t)gridDim.x * 256) {
+        const int32_t row = w.hub_rows[h];
+        if (row < 0) continue;
+        const int64_t nseg = ((int64_t)rowptr[row + 1] - rowptr[row] + kSeg - 1) / kSeg;
+        const float *part = w.part + w.hub_seg0[h];
+        float z = part[0];
+        for (int64_t s = 1; s < nseg; s++) z = z + part[s];
+        w.hub_val[h] = z;
+        if (rows) rows[row] = z;
+    }
+}
+
+// alpha_p = x_p / z
+__global__ __launch_bounds__(256) void fwd_hub_div_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ out, Lists w)
+{
+    GNNX_FOR_HUB_SEGMENTS({
+        const float z = w.hub_val[h];
+        for (int64_t k = l; k < n; k += 64) out[b + k] = __fdiv_rn(out[b + k], z);
+    })
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------------
+// dt_p of one entry from the row's dot_i
+__device__ __forceinline__ float dt_of(float t, float slope, float al, float da, float dot)
+{
+    const float de = al * (da - dot);
+    return t > 0.f ? de : de * slope;
+}
+
+__global__ __launch_bounds__(256) void bwd_short_kernel(int32_t n_rows, const int32_t *__restrict__ rowptr, Pre a, const float *__restrict__ alpha,
+                                                        const float *__restrict__ dalpha, float *__restrict__ dt, float *__restrict__ drowterm, Lists w)
+{
+    const int l = threadIdx.x & (kShortW - 1);
+    const ShortRows r = load_short_rows(rowptr, n_rows);
+    float al[kShortR], da[kShortR], t[kShortR];
+#pragma unroll
+    for (int j = 0; j < kShortR; j++) {
+        al[j] = da[j] = t[j] = 0.f;
+        if (r.d[j] <= kShortW && l < r.d[j]) {
+            const int64_t p = (int64_t)r.b[j] + l;
+            const float rt = a.rowterm ? a.rowterm[(int64_t)r.row[j] * a.rs] : 0.f;
+            al[j] = alpha[p];
+            da[j] = dalpha[p];
+            t[j] = pre_activation(a, p, rt);
+        }
+    }
+    classify(w, r);
+#pragma unroll
+    for (int j = 0; j < kShortR; j++) {
+        const bool own = r.row[j] >= 0 && r.d[j] <= kShortW;
+        const bool have = own && l < r.d[j];
+        const int G = lanes_of(r.d[j]);
+        float acc = 0.f;
+        if (have) acc = acc + (al[j] * da[j]);
+        const float dot = add_lanes<kShortW>(acc, G);
+        acc = 0.f;
+        if (have) {
+            const float de = al[j] * (da[j] - dot);
+            const float v = t[j] > 0.f ? de : de * a.slope;
+            dt[(int64_t)r.b[j] + l] = v;
+            acc = acc + v;
+        }
+        const float sum = add_lanes<kShortW>(acc, G);
+        if (own && l == 0 && drowterm) drowterm[r.row[j]] = sum;   // an empty row: +0
+    }
+}
+
+__global__ __launch_bounds__(256) void bwd_long_kernel(const int32_t *__restrict__ rowptr, Pre a, const float *__restrict__ alpha,
+                                                       const float *__restrict__ dalpha, float *__restrict__ dt, float *__restrict__ drowterm, Lists w)
+{
+    const int l = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
+    const int64_t n_long = listed(&w.counters[0], w.cap_long);
+    for (int64_t i = wave; i < n_long; i += n_waves) {
+        const int32_t row = w.long_rows[i];
+        const int64_t b = rowptr[row], d = (int64_t)rowptr[row + 1] - b;
+        const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
+        const int G = lanes_of(d);
+        float sum;
+        if (d <= 64) {
+            const bool have = l < d;
+            float al = 0.f, da = 0.f, acc = 0.f;
+            if (have) {
+                al = alpha[b + l];
+                da = dalpha[b + l];
+                acc = acc + (al * da);
+            }
+            const float dot = add_lanes<64>(acc, G);
+            acc = 0.f;
+            if (have) {
+                const float v = dt_of(pre_activation(a, b + l, rt), a.slope, al, da, dot);
+                dt[b + l] = v;
+                acc = acc + v;
+            }
+            sum = add_lanes<64>(acc, G);
+        } else {
+            float acc = 0.f;
+            for (int64_t k = l; k < d; k += 64) acc = acc + (alpha[b + k] * dalpha[b + k]);
+            const float dot = add_lanes<64>(acc, 64);
+            acc = 0.f;
+            for_lane_entries(a, b, d, rt, l, [&](int64_t k, float t) {
+                const float v = dt_of(t, a.slope, alpha[b + k], dalpha[b + k], dot);
+                dt[b + k] = v;
+                acc = acc + v;
+            });
+            sum = add_lanes<64>(acc, 64);
+        }
+        if (l == 0 && drowterm) drowterm[row] = sum;
+    }
+}
+
+// the segment's sum of w_p = alpha_p * dalpha_p -> part
+__global__ __launch_bounds__(256) void bwd_hub_dot_kernel(const int32_t *__restrict__ rowptr, const float *__restrict__ alpha,
+                                                          const float *__restrict__ dalpha, Lists w)
+{
+    GNNX_FOR_HUB_SEGMENTS({
+        float acc = 0.f;
+        for (int64_t k = l; k < n; k += 64) acc = acc + (alpha[b + k] * dalpha[b + k]);
+        acc = add_lanes<64>(acc, 64);
+        if (l == 0) part[s] = acc;
+    })
+}
+
+// dt_p -> dt, the segment's sum of dt_p -> part
+__global__ __launch_bounds__(256) void bwd_hub_dt_kernel(const int32_t *__restrict__ rowptr, Pre a, const float *__restrict__ alpha,
+                                                         const float *__restrict__ dalpha, float *__restrict__ dt, Lists w)
+{
+    GNNX_FOR_HUB_SEGMENTS({
+        const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
+        const float dot = w.hub_val[h];
+        float acc = 0.f;
+        for_lane_entries(a, b, n, rt, l, [&](int64_t k, float t) {
+            const float v = dt_of(t, a.slope, alpha[b + k], dalpha[b + k], dot);
+            dt[b + k] = v;
+            acc = acc + v;
+        });
+        acc = add_lanes<64>(acc, 64);
+        if (l == 0) part[s] = acc;
+    })
+}
+
+#undef GNNX_FOR_HUB_SEGMENTS
+
+inline uint32_t blocks_for_waves(int64_t waves, int64_t cap) { return (uint32_t)ceil_div(waves < cap ? waves : cap, 4); }
+
+// what both entry points check before any device call
+int check_args(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, const float *d_scores,
+               const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm, int64_t colterm_stride)
+{
+    GNNX_REQUIRE(n_rows >= 0 && n_cols >= 0 && nnz >= 0, GNNX_ERR_INVALID_ARG, "negative size");
+    GNNX_REQUIRE(nnz < (1ll << 31), GNNX_ERR_INVALID_ARG, "nnz does not fit the int32 CSR");
+    GNNX_REQUIRE(d_scores || d_rowterm || d_colterm, GNNX_ERR_INVALID_ARG, "scores, rowterm and colterm are all null");
+    GNNX_REQUIRE((!d_rowterm || rowterm_stride >= 1) && (!d_colterm || colterm_stride >= 1), GNNX_ERR_INVALID_ARG, "term stride < 1");
+    GNNX_REQUIRE(d_rowptr, GNNX_ERR_INVALID_ARG, "null pointer");
+    GNNX_REQUIRE(nnz == 0 || (n_rows > 0 && n_cols > 0), GNNX_ERR_INVALID_ARG, "entries in a matrix without rows or columns");
+    GNNX_REQUIRE(nnz == 0 || d_colidx, GNNX_ERR_INVALID_ARG, "null pointer");
+    return GNNX_OK;
+}
+
+}  // namespace
+
+GNNX_API int gnnx_edge_softmax_workspace(int32_t n_rows, int64_t nnz, size_t *bytes)
+{
+    GNNX_REQUIRE(bytes && n_rows >= 0 && nnz >= 0 && nnz < (1ll << 31), GNNX_ERR_INVALID_ARG, "bad arguments");
+    *bytes = carve(n_rows, nnz, nullptr, nullptr);
+    return GNNX_OK;
+}
+
+GNNX_API int gnnx_edge_softmax_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                       const float *d_scores, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm,
+                                       int64_t colterm_stride, float negative_slope, uint32_t flags, float *d_out, float *d_rowmax,
+                                       float *d_rowsum, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_args(n_rows, n_cols, nnz, d_rowptr, d_colidx, d_scores, d_rowterm, rowterm_stride, d_colterm, colterm_stride);
+    if (rc) return rc;
+    GNNX_REQUIRE(!(flags & ~(uint32_t)GNNX_EDGE_SOFTMAX_UNNORMALISED), GNNX_ERR_INVALID_ARG, "unknown flag");
+    GNNX_REQUIRE(nnz == 0 || d_out, GNNX_ERR_INVALID_ARG, "null pointer");
+    if (n_rows == 0) return GNNX_OK;
+    Lists w;
+    const size_t need = carve(n_rows, nnz, d_workspace, &w);
+    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    const Pre a{d_colidx, d_scores, d_rowterm, d_colterm, rowterm_stride, colterm_stride, negative_slope};
+    const int unnorm = (flags & GNNX_EDGE_SOFTMAX_UNNORMALISED) ? 1 : 0;
+    GNNX_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(int32_t) * kCounters, st));
+    hipLaunchKernelGGL(fwd_short_kernel, dim3((uint32_t)ceil_div(n_rows, kShortRowsPerBlock)), dim3(256), 0, st, n_rows, d_rowptr, a, unnorm,
+                       d_out, d_rowmax, d_rowsum, w);
+    GNNX_LAUNCH_CHECK();
+    if (w.cap_long > 0) {
+        hipLaunchKernelGGL(fwd_long_kernel, dim3(blocks_for_waves(w.cap_long, kLongWaves)), dim3(256), 0, st, d_rowptr, a, unnorm, d_out, d_rowmax,
+                           d_rowsum, w);
+        GNNX_LAUNCH_CHECK();
+    }
+    if (w.cap_hub > 0) {
+        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves)), hub_grid(blocks_for_waves(w.cap_hub, 1024));
+        hipLaunchKernelGGL(fwd_hub_max_kernel, seg_grid, dim3(256), 0, st, d_rowptr, a, d_out, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hub_combine_max_kernel, hub_grid, dim3(256), 0, st, d_rowptr, d_rowmax, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(fwd_hub_exp_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_out, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hub_combine_sum_kernel, dim3((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256)), dim3(256), 0, st, d_rowptr,
+                           d_rowsum, w);
+        GNNX_LAUNCH_CHECK();
+        if (!unnorm) {
+            hipLaunchKernelGGL(fwd_hub_div_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_out, w);
+            GNNX_LAUNCH_CHECK();
+        }
+    }
+    return GNNX_OK;
+}
+
+GNNX_API int gnnx_edge_softmax_bwd_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                           const float *d_scores, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm,
+                                           int64_t colterm_stride, float negative_slope, const float *d_alpha, const float *d_dalpha,
+                                           float *d_dt, float *d_drowterm, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_args(n_rows, n_cols, nnz, d_rowptr, d_colidx, d_scores, d_rowterm, rowterm_stride, d_colterm, colterm_stride);
+    if (rc) return rc;
+    GNNX_REQUIRE(nnz == 0 || (d_alpha && d_dalpha && d_dt), GNNX_ERR_INVALID_ARG, "null pointer");
+    if (n_rows == 0) return GNNX_OK;
+    Lists w;
+    const size_t need = carve(n_rows, nnz, d_workspace, &w);
+    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    const Pre a{d_colidx, d_scores, d_rowterm, d_colterm, rowterm_stride, colterm_stride, negative_slope};
+    GNNX_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(int32_t) * kCounters, st));
+    hipLaunchKernelGGL(bwd_short_kernel, dim3((uint32_t)ceil_div(n_rows, kShortRowsPerBlock)), dim3(256), 0, st, n_rows, d_rowptr, a, d_alpha,
+                       d_dalpha, d_dt, d_drowterm, w);
+    GNNX_LAUNCH_CHECK();
+    if (w.cap_long > 0) {
+        hipLaunchKernelGGL(bwd_long_kernel, dim3(blocks_for_waves(w.cap_long, kLongWaves)), dim3(256), 0, st, d_rowptr, a, d_alpha, d_dalpha, d_dt,
+                           d_drowterm, w);
+        GNNX_LAUNCH_CHECK();
+    }
+    if (w.cap_hub > 0) {
+        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves));
+        const dim3 lane_grid((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256));
+        hipLaunchKernelGGL(bwd_hub_dot_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_alpha, d_dalpha, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hub_combine_sum_kernel, lane_grid, dim3(256), 0, st, d_rowptr, (float *)nullptr, w);   // dot_i -> hub_val
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bwd_hub_dt_kernel, seg_grid, dim3(256), 0, st, d_rowptr, a, d_alpha, d_dalpha, d_dt, w);
+        GNNX_LAUNCH_CHECK();
+        if (d_drowterm) {
+            hipLaunchKernelGGL(hub_combine_sum_kernel, lane_grid, dim3(256), 0, st, d_rowptr, d_drowterm, w);
+            GNNX_LAUNCH_CHECK();
+        }
+    }
+    return GNNX_OK;
+}

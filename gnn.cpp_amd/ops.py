@@ -194,6 +194,19 @@ class CsrGraph:
                     pl.set_big_row_threshold(big_rows)
         return self.plan, self.plan_t
 
+    def attention_map(self):
+        """map_t of this graph (csr_transpose_map, built once and kept): per-entry values of CSR(A) -- attention coefficients, their
+        gradients -- move to the order of CSR(A^T) as vals[map_t].  GnnxError on a relabelled graph: its rows store their entries in
+        ORIGINAL-id order, not ascending, so the map's binary search has nothing to search (build the graph without `relabel` for an
+        attention layer); and on a graph without a transposed CSR."""
+        if self.nid is not None:
+            raise capi.GnnxError(-7, "attention_map", "a relabelled graph keeps each row in original-id order, not ascending: the "
+                                 "transpose map cannot be built on it (build the graph without relabel)")
+        if self.rowptr_t is None or self.colidx_t is None:
+            raise capi.GnnxError(-1, "attention_map", "the graph has no transposed CSR (from_coo(..., transpose=True))")
+        if getattr(self, "_map_t", None) is None:
+            self._map_t = csr_transpose_map(self.rowptr, self.colidx, self.rowptr_t, self.colidx_t)
+        return self._map_t
 
     def mask_in_row_order(self, mask):
         """A vertex-order mask ([n] bool / uint8, vertex v at position v) as uint8 in this graph's row order (vertex v at nid[v])."""
@@ -446,9 +459,11 @@ def csr_from_coo_weighted(src, dst, w, n_nodes, diag_mode=DIAG_KEEP, diag_value=
     return rowptr, colidx[: nnz.value].clone(), vals[: nnz.value].clone()
 
 
-def csr_rowsum(rowptr, vals=None):
+def csr_rowsum(rowptr, vals=None, out=None):
     n = int(rowptr.numel() - 1)
-    out = torch.empty(n, dtype=torch.float32, device=rowptr.device)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=rowptr.device)
+    assert out.numel() == n and out.is_contiguous()
     capi.call("gnnx_csr_rowsum_f32", _ptr(rowptr), _ptr(vals), n, _ptr(out), _stream())
     return out
 
@@ -562,6 +577,77 @@ class EdgeSet:
         if self.nnz:
             gather_rows(vals.reshape(-1, 1), self.map_t, out=out.reshape(-1, 1))
         return out
+
+
+EDGE_SOFTMAX_UNNORMALISED = 1
+
+
+def _edge_term(t, n, what):
+    """(pointer, stride in elements) of a per-vertex term: float32 [n], contiguous or a 1-D strided view (a column of an [n, 2] matrix)."""
+    if t is None:
+        return None, 0
+    if t.dim() != 1 or int(t.numel()) != n or t.dtype != torch.float32:
+        raise capi.GnnxError(-2, "edge_softmax", f"{what} must be a float32 vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
+    stride = int(t.stride(0)) if n > 1 else 1
+    if stride < 1:
+        raise capi.GnnxError(-1, "edge_softmax", f"{what} has stride {stride}")
+    return _ptr(t), stride
+
+
+def _edge_softmax_args(rowptr, colidx, scores, rowterm, colterm):
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    if scores is not None and (int(scores.numel()) != nnz or not scores.is_contiguous() or scores.dtype != torch.float32):
+        raise capi.GnnxError(-2, "edge_softmax", f"scores must be a contiguous float32 vector of {nnz} entries")
+    n_cols = int(colterm.numel()) if colterm is not None else n_rows
+    rt, rs = _edge_term(rowterm, n_rows, "rowterm")
+    ct, cs = _edge_term(colterm, n_cols, "colterm")
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_edge_softmax_workspace", n_rows, nnz, C.byref(wsb))
+    ws = _workspace(wsb.value, rowptr.device, "edge_softmax")
+    return n_rows, n_cols, nnz, rt, rs, ct, cs, ws
+
+
+def edge_softmax(rowptr, colidx, scores=None, rowterm=None, colterm=None, negative_slope=1.0, unnormalised=False, want_stats=False):
+    """gnnx_edge_softmax_csr_f32: alpha[p] = softmax over the stored entries of row i of leaky_relu((scores[p] + rowterm[i]) +
+    colterm[c_p]) -- float32 [nnz]; operands that are None are skipped (at least one is needed), slope 1 is the identity.  rowterm /
+    colterm: float32 [n_rows] / [n_cols], 1-D strided views allowed (the two columns of an [n, 2] matrix).  unnormalised: exp(e_p - max_i)
+    instead.  want_stats: (alpha, rowmax, rowsum).  The order of the row sums is a function of the row length alone (include/gnnx.h)."""
+    n_rows, n_cols, nnz, rt, rs, ct, cs, ws = _edge_softmax_args(rowptr, colidx, scores, rowterm, colterm)
+    dev = rowptr.device
+    out = torch.empty(nnz, dtype=torch.float32, device=dev)
+    rowmax = torch.empty(n_rows, dtype=torch.float32, device=dev) if want_stats else None
+    rowsum = torch.empty(n_rows, dtype=torch.float32, device=dev) if want_stats else None
+    capi.call("gnnx_edge_softmax_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(scores), rt, rs, ct, cs,
+              float(negative_slope), EDGE_SOFTMAX_UNNORMALISED if unnormalised else 0, _ptr(out) if nnz else None, _ptr(rowmax), _ptr(rowsum),
+              _ptr(ws), ws.numel(), _stream())
+    return (out, rowmax, rowsum) if want_stats else out
+
+
+def edge_softmax_bwd(rowptr, colidx, alpha, dalpha, scores=None, rowterm=None, colterm=None, negative_slope=1.0, drowterm_out=None):
+    """gnnx_edge_softmax_bwd_csr_f32: (dt, drowterm) from alpha = edge_softmax(...) of the same operands and dalpha = dL/dalpha.  dt
+    [nnz] is the gradient of scores; drowterm [n_rows] (the row sums of dt) that of rowterm; the gradient of colterm is
+    csr_rowsum(rowptr_t, dt[map_t]) on the transposed pattern (CsrGraph.attention_map / csr_transpose_map)."""
+    n_rows, n_cols, nnz, rt, rs, ct, cs, ws = _edge_softmax_args(rowptr, colidx, scores, rowterm, colterm)
+    for t, what in ((alpha, "alpha"), (dalpha, "dalpha")):
+        if int(t.numel()) != nnz or not t.is_contiguous() or t.dtype != torch.float32:
+            raise capi.GnnxError(-2, "edge_softmax_bwd", f"{what} must be a contiguous float32 vector of {nnz} entries")
+    dev = rowptr.device
+    dt = torch.empty(nnz, dtype=torch.float32, device=dev)
+    drow = torch.empty(n_rows, dtype=torch.float32, device=dev) if drowterm_out is None else drowterm_out
+    assert drow.numel() == n_rows and drow.is_contiguous()
+    capi.call("gnnx_edge_softmax_bwd_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(scores), rt, rs, ct, cs,
+              float(negative_slope), _ptr(alpha) if nnz else None, _ptr(dalpha) if nnz else None, _ptr(dt) if nnz else None, _ptr(drow),
+              _ptr(ws), ws.numel(), _stream())
+    return dt, drow
+
+
+def transpose(X, out=None):
+    """gnnx_transpose_f32: out[c, r] = X[r, c] (materialised)."""
+    R, Cn = X.shape
+    if out is None:
+        out = torch.empty((Cn, R), dtype=torch.float32, device=X.device)
+    capi.call("gnnx_transpose_f32", _ptr(X), _ld(X), R, Cn, _ptr(out), _ld(out), _stream())
+    return out
 
 
 def gemm(A, B, transA=False, transB=False, out=None, alpha=1.0, beta=0.0):
@@ -1233,4 +1319,129 @@ class GcnStack:
         t = target.reshape(-1)[rows.long()].to(torch.int32).contiguous()
         loss, _ = softmax_ce_rows(logits, t, field.compact_rows, want_grad=False)
         correct, count = accuracy(logits, t, field.compact_rows)
+        return loss, correct, count
+
+
+class GatStack:
+    """L single-head graph-attention layers (GAT, Velickovic et al. 2018) on one graph, the surface of GcnStack:
+        H = h W^T;   el = H a_l,  er = H a_r;   alpha_ic = softmax over the stored entries c of row i of leaky_relu(el_i + er_c);
+        h' = act( sum_c alpha_ic H_c + b ),  ReLU between layers, none after the last.
+    Row i attends over its STORED columns -- the direction of the project's aggregation.  forward / backward / step / train_step /
+    evaluate; every operation is a C-ABI call: the dense products (the two attention vectors ride as one [2, d] matrix A = [a_l; a_r],
+    so el and er are the columns of ER = H A^T), edge_softmax, the aggregation with vals = alpha, its value gradient (spmm_vals_grad),
+    edge_softmax_bwd, and the transposed pattern with g.attention_map() for everything that flows back to a column's vertex.  No
+    atomics; the same bits every run.
+
+    The stack takes any CsrGraph that has a transposed CSR and is not relabelled.  CsrGraph.from_coo strips the diagonal; the paper's
+    self attention wants every vertex in its own row, a pattern with the whole diagonal:
+        w = torch.ones(src.numel(), device=src.device)
+        rp, ci, _ = csr_from_coo_weighted(src, dst, w, n, DIAG_FILL)          # the values are discarded
+        rp_t, ci_t, _ = csr_from_coo_weighted(dst, src, w, n, DIAG_FILL)
+        g = CsrGraph(n, rp, ci, rp_t, ci_t)                                   # g.make_plans(...) for a power-law graph
+    A vertex without entries (only possible without the diagonal) has an empty softmax: its row is the bias alone.
+    One head; several heads would be a loop over column slabs of H (the aggregation takes one value per entry)."""
+
+    def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda"):
+        self.g = g
+        self.dims = list(dims)
+        self.negative_slope = float(negative_slope)
+        self.map_t = g.attention_map()
+        L = len(dims) - 1
+        self.W = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.A = [uniform_pm1(seed + 2 * l + 1, (2, dims[l + 1]), scale=dims[l + 1] ** -0.5, device=device) for l in range(L)]   # [a_l; a_r]
+        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
+        self.dW = [torch.zeros_like(w) for w in self.W]
+        self.dA = [torch.zeros_like(a) for a in self.A]
+        self.db = [torch.zeros_like(b) for b in self.b]
+        self._saved = None
+        self._buf = {}
+
+    def _tmp(self, key, shape, device, zero=False):
+        t = self._buf.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._buf[key] = (torch.zeros if zero else torch.empty)(shape, dtype=torch.float32, device=device)
+        return t
+
+    def grad_buffer(self):
+        """Where the loss should write dlogits ([n, dims[-1]])."""
+        return self._tmp("G", (self.g.n, self.dims[-1]), self.W[0].device)
+
+    def attention(self, H, l):
+        """(ER, alpha) of layer l from H = h W_l^T: ER = H [a_l; a_r]^T as [n, 2], alpha = edge_softmax(rowterm = ER[:, 0], colterm = ER[:, 1])."""
+        g = self.g
+        ER = gemm(H, self.A[l], transB=True)
+        alpha = edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=self.negative_slope)
+        return ER, alpha
+
+    def forward(self, X):
+        g, L = self.g, len(self.W)
+        saved, h = [], X
+        for l in range(L):
+            H = linear_fwd(h, self.W[l])
+            ER, alpha = self.attention(H, l)
+            # the ReLU between layers rides in the aggregation's epilogue: only relu(Z) is stored (its sign is the mask)
+            Y = spmm(g.rowptr, g.colidx, H, vals=alpha, bias=self.b[l], plan=g.plan, relu_out=l + 1 < L)
+            saved.append((h, H, ER, alpha, Y))
+            h = Y
+        self._saved = saved
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """dW, dA ([da_l; da_r]) and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        g, L, n = self.g, len(self.W), self.g.n
+        G = dOut
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            h, H, ER, alpha, _ = self._saved[l]
+            dev = G.device
+            dalpha = spmm_vals_grad(g.rowptr, g.colidx, G, H)
+            dER_t = self._tmp("dER_t", (2, n), dev)                                   # row 0: del, row 1: der
+            dt, _ = edge_softmax_bwd(g.rowptr, g.colidx, alpha, dalpha, rowterm=ER[:, 0], colterm=ER[:, 1],
+                                     negative_slope=self.negative_slope, drowterm_out=dER_t[0])
+            vals_t = self._tmp("vals_t", (g.nnz,), dev)
+            self._to_transposed(dt, vals_t)
+            csr_rowsum(g.rowptr_t, vals_t, out=dER_t[1])                              # der: what flows back to a column's vertex
+            self._to_transposed(alpha, vals_t)
+            dH = spmm(g.rowptr_t, g.colidx_t, G, vals=vals_t, plan=g.plan_t)          # through the aggregated rows
+            dER = transpose(dER_t, out=self._tmp("dER", (n, 2), dev))
+            gemm(dER, self.A[l], out=dH, beta=1.0)                                    # + [del der] . [a_l; a_r], through ER
+            gemm(dER, H, transA=True, out=self.dA[l])
+            gemm(dH, h, transA=True, out=self.dW[l])
+            if l == 0:
+                G = gemm(dH, self.W[l]) if input_grad else None
+            else:   # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue
+                G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
+        return G
+
+    def _to_transposed(self, vals, out):
+        if self.g.nnz:
+            gather_rows(vals.reshape(-1, 1), self.map_t, out=out.reshape(-1, 1))
+        return out
+
+    def step(self, lr, weight_decay=0.0):
+        for p, gr in zip(self.W + self.A + self.b, self.dW + self.dA + self.db):
+            sgd_step(p, gr, lr, weight_decay)
+
+    def train_step(self, X, target, rows, lr, weight_decay=0.0):
+        """One SGD step on the listed rows: forward -> softmax_ce_rows over `rows` (db[-1] from the loss kernel) -> backward without an
+        input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)); target is read at listed rows only.  No layer is
+        pruned to the listed rows.  Returns the loss tensor."""
+        logits = self.forward(X)
+        G = self.grad_buffer()
+        key = (id(rows), G.data_ptr())
+        if getattr(self, "_grad_zeroed_for", None) != key:   # softmax_ce_rows writes the listed rows only: the rest must be zero
+            G.zero_()
+            self._grad_zeroed_for, self._grad_rows = key, rows
+        loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=G)
+        self.backward(G, input_grad=False, have_last_bias_grad=True)
+        self.step(lr, weight_decay)
+        return loss
+
+    def evaluate(self, X, target, rows):
+        """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows))."""
+        logits = self.forward(X)
+        loss, _ = softmax_ce_rows(logits, target, rows, want_grad=False)
+        correct, count = accuracy(logits, target, rows)
         return loss, correct, count

@@ -606,6 +606,64 @@ int gnnx_sddmm_csr_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t n
 int gnnx_csr_transpose_map(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
                            const int32_t *d_rowptr_t, const int32_t *d_colidx_t, int32_t *d_map_t, void *stream);
 
+/* ------------------------------------------------------------------ edge softmax ----------------- */
+/*
+ * A softmax over the STORED entries of each row of a CSR pattern, forward and backward: the one step of a graph-attention layer that
+ * is not a composition of the calls above (scores: gnnx_sddmm_csr_f32 or two per-vertex terms; aggregation with vals = alpha:
+ * gnnx_spmm_csr_f32; gradient of vals: gnnx_sddmm_csr_f32; transposed order: gnnx_csr_transpose_map).  The reference has no
+ * attention layer: the contract is this comment, restated in NumPy by tests/edge_softmax_ref.py.
+ *
+ * Forward, for entry p of row i with column c = colidx[p]; every operation is a separately rounded fp32 operation:
+ *   t_p     = (scores[p] + rowterm[i * rowterm_stride]) + colterm[c * colterm_stride]
+ *             A NULL operand is skipped; at least one of the three must be given.  Strides are in elements (>= 1), so the two
+ *             terms can be the two columns of one [N, 2] matrix.
+ *   e_p     = t_p > 0 ? t_p : t_p * negative_slope          (slope 1: the identity -- scaled dot-product attention is
+ *                                                            scores = sddmm(Q, K, rowscale = 1/sqrt(d)) and no terms)
+ *   m_i     = max_p e_p                                      (exact; a maximum has no order)
+ *   x_p     = expf(e_p - m_i)                                (the subtraction rounded once; expf is the device library's)
+ *   z_i     = the row sum of x_p in the ROW ORDER below
+ *   alpha_p = x_p / z_i                                      (one correctly rounded IEEE division, not a multiply by 1 / z_i)
+ *   d_out[p] = alpha_p, or x_p with flags & GNNX_EDGE_SOFTMAX_UNNORMALISED (what a sharded softmax would exchange);
+ *   d_rowmax[i] = m_i and d_rowsum[i] = z_i when those pointers are given.
+ * An empty row writes no entry, rowmax = -inf and rowsum = +0.  Inputs are finite; NaN and inf give unspecified values but never an
+ * out-of-bounds access.  d_out aliases no input.
+ *
+ * ROW ORDER -- of every row sum of both calls, a function of the row length d alone.  Entries are numbered k = 0 .. d-1 in stored
+ * order; S = 4096 is a fixed segment length.
+ *   d <= S:  G is the smallest power of two with G >= d, capped at 64.  Virtual lane l < G starts from +0 and does
+ *            acc_l = acc_l + v_k for k = l, l+G, l+2G, ... ascending; a lane with no entry holds +0.  For s = 1, 2, ..., G/2 every
+ *            lane does acc_l = acc_l + acc_{l xor s}.  The sum is acc_0.
+ *   d > S:   the row is cut into segments of S consecutive entries (the last may be short); each segment is summed by the rule
+ *            above with G = 64; the row sum is ((seg_0 + seg_1) + seg_2) + ... in ascending segment order.
+ * The lanes are virtual: how rows, segments and lanes map to wavefronts does not appear in the result.  The segment rule lets a hub
+ * row of 10^5 .. 10^6 entries spread over many wavefronts: the segments' partial sums go to the workspace and are combined in the
+ * fixed order.
+ *
+ * Backward (no transcendental: restatable bit for bit), from alpha (the normalised forward output) and dalpha = dL/dalpha:
+ *   w_p   = alpha_p * dalpha_p;   dot_i = the row sum of w_p in the row order
+ *   de_p  = alpha_p * (dalpha_p - dot_i)
+ *   dt_p  = t_p > 0 ? de_p : de_p * negative_slope           (t_p recomputed from the same three inputs with the forward's additions)
+ *   d_dt[p] = dt_p -- the gradient of scores[p];  d_drowterm[i] (when given) = the row sum of dt_p in the row order, +0 on an empty
+ *   row -- the gradient of rowterm[i].  d_dt aliases nothing.  The gradient of colterm is not this call's job: it is
+ *   gnnx_csr_rowsum_f32(rowptr_t, vals = dt[map_t]) on the transposed pattern (gnnx_csr_transpose_map); no atomics anywhere.
+ *
+ * Both calls are asynchronous on `stream` (a chain of launches on that one stream); they allocate nothing and synchronise nothing and
+ * TRUST the CSR and nnz (= rowptr[n_rows]) as the aggregation does.  Null pointers, negative sizes, a stride < 1, all three operands
+ * NULL and nnz >= 2^31 are GNNX_ERR_INVALID_ARG before any device call; a workspace smaller than gnnx_edge_softmax_workspace() bytes
+ * is GNNX_ERR_WORKSPACE.  nnz == 0 still writes the per-row outputs.  The workspace (lists of the rows longer than 16 and than S
+ * entries, one value per segment) serves either call and holds nothing between calls.
+ */
+#define GNNX_EDGE_SOFTMAX_UNNORMALISED 1u
+int gnnx_edge_softmax_workspace(int32_t n_rows, int64_t nnz, size_t *bytes);
+int gnnx_edge_softmax_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                              const float *d_scores, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm,
+                              int64_t colterm_stride, float negative_slope, uint32_t flags, float *d_out, float *d_rowmax,
+                              float *d_rowsum, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_edge_softmax_bwd_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                  const float *d_scores, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm,
+                                  int64_t colterm_stride, float negative_slope, const float *d_alpha, const float *d_dalpha,
+                                  float *d_dt, float *d_drowterm, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */

@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Measurement (GPU box): the edge softmax (ops.edge_softmax / ops.edge_softmax_bwd), the three skinny dense products of a
+graph-attention layer, and one GatStack.train_step, with the PLANNED FORWARD AGGREGATION and the edge-score kernel (ops.sddmm) on the
+same CSR and width in the same process as yardsticks (each of those gathers nnz * 4 F bytes of rows; the softmax moves 12 - 20 bytes
+per entry).
+
+    every kernel: --repeats single calls between two device events after --warmup calls; the median and the range are reported
+
+One JSON line per configuration:
+
+    rmat1m    R-MAT 1 M vertices / 10 M edges, F = 128, plus one training step of a 2-layer stack [128, 128, 128] over a tenth of the rows
+    headline  R-MAT 10 M vertices / 100 M edges, F = 256 (BASELINE.md's headline graph), kernels only
+
+The graph is NOT relabelled (CsrGraph.attention_map needs ascending rows), so the aggregation yardstick here is not BASELINE.md's
+scrambled-order number.  Without --config the script is a driver: it runs every configuration as a child process of its own under a
+time limit and stops at the first one that fails.  --trace N: no timing, N calls of the softmax forward and backward in a row (run
+under `rocprofv3 --kernel-trace --stats -- python scripts/bench_gat_step.py --config rmat1m --trace 5` for the kernel times).
+"""
+import argparse
+import ctypes as C
+import importlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CONFIGS = {"rmat1m": dict(nodes=1_000_000, edges=10_000_000, feat=128, step=True, limit=300),
+           "headline": dict(nodes=10_000_000, edges=100_000_000, feat=256, step=False, limit=420)}
+
+
+def driver(args):
+    for name in args.configs.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--repeats", str(args.repeats), "--warmup", str(args.warmup)]
+        try:
+            r = subprocess.run(cmd, timeout=CONFIGS[name]["limit"])
+        except subprocess.TimeoutExpired:
+            print(json.dumps({"config": name, "error": "time limit"}), flush=True)
+            return 1
+        if r.returncode != 0:
+            print(json.dumps({"config": name, "error": f"exit status {r.returncode}"}), flush=True)
+            return 1
+    return 0
+
+
+def measure(args):
+    import torch
+
+    from __graft_entry__ import load_package
+    load_package()
+    ops = importlib.import_module("gnncpp_amd.ops")
+    capi = importlib.import_module("gnncpp_amd.capi")
+    dev = torch.device("cuda:0")
+    cfg = CONFIGS[args.config]
+    n, e, F = cfg["nodes"], cfg["edges"], cfg["feat"]
+
+    def stream():
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def one_call_ms(fn):
+        a, b = capi.Event(), capi.Event()
+        a.record(stream())
+        fn()
+        b.record(stream())
+        b.sync()
+        return a.elapsed_ms(b)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        return [one_call_ms(fn) for _ in range(args.repeats)]
+
+    src, dst = ops.rmat_edges(args.seed, n, e, 0.57, 0.19, 0.19, device=dev)
+    g = ops.CsrGraph.from_coo(src, dst, n)
+    g.make_plans(args.chunk, F)
+    map_t = g.attention_map()
+    deg = (g.rowptr[1:] - g.rowptr[:-1])
+    H = ops.uniform_pm1(args.seed + 1, (n, F), device=dev)
+    G = ops.uniform_pm1(args.seed + 2, (n, F), device=dev)
+    A = ops.uniform_pm1(args.seed + 3, (2, F), scale=F ** -0.5, device=dev)
+    Y = torch.empty((n, F), dtype=torch.float32, device=dev)
+    dH = torch.zeros((n, F), dtype=torch.float32, device=dev)
+    dA = torch.empty((2, F), dtype=torch.float32, device=dev)
+    scores = torch.empty(g.nnz, dtype=torch.float32, device=dev)
+    ER = ops.gemm(H, A, transB=True)
+    dER = ops.uniform_pm1(args.seed + 4, (n, 2), scale=1e-3, device=dev)
+    alpha = ops.edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2)
+    dalpha = ops.uniform_pm1(args.seed + 5, (g.nnz,), device=dev)
+    vals_t = torch.empty(g.nnz, dtype=torch.float32, device=dev)
+    kernels = {
+        "aggregation": lambda: ops.spmm(g.rowptr, g.colidx, H, out=Y, vals=alpha, plan=g.plan),
+        "sddmm": lambda: ops.sddmm(g.rowptr, g.colidx, G, H, out=scores),
+        "edge_softmax_fwd": lambda: ops.edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2),
+        "edge_softmax_bwd": lambda: ops.edge_softmax_bwd(g.rowptr, g.colidx, alpha, dalpha, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2),
+        "to_transposed": lambda: ops.gather_rows(alpha.reshape(-1, 1), map_t, out=vals_t.reshape(-1, 1)),
+        "colterm_grad_rowsum": lambda: ops.csr_rowsum(g.rowptr_t, vals_t),
+        "gemm_ER": lambda: ops.gemm(H, A, transB=True, out=ER),
+        "gemm_dH_K2": lambda: ops.gemm(dER, A, out=dH, beta=1.0),
+        "gemm_dA_transA": lambda: ops.gemm(dER, H, transA=True, out=dA),
+    }
+    if args.trace:
+        for key in ("edge_softmax_fwd", "edge_softmax_bwd"):
+            for _ in range(args.trace):
+                kernels[key]()
+        torch.cuda.synchronize()
+        return 0
+    ms = {k: timed(fn) for k, fn in kernels.items()}
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    model_fwd = g.nnz * 12 + n * 16          # colidx + gathered colterm + out per entry; rowptr, rowterm per row
+    model_bwd = g.nnz * 20 + n * 16          # + alpha, dalpha
+    out = {"config": args.config, "nodes": n, "edges": e, "nnz": g.nnz, "feat": F, "chunk": args.chunk,
+           "max_degree": int(deg.max()), "rows_over_16": int((deg > 16).sum()), "rows_over_4096": int((deg > 4096).sum()),
+           "ms_median": {k: round(v, 4) for k, v in med.items()},
+           "ms_range": {k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
+           "edge_softmax_fwd_model_TBps": round(model_fwd / med["edge_softmax_fwd"] / 1e9, 3),
+           "edge_softmax_bwd_model_TBps": round(model_bwd / med["edge_softmax_bwd"] / 1e9, 3),
+           "repeats": args.repeats, "warmup": args.warmup, "device": capi.device_name(0)}
+    if cfg["step"]:
+        del Y, dH, scores, G, dalpha, vals_t
+        net = ops.GatStack(g, [F, F, F], seed=args.seed + 100, device=dev)
+        X = ops.uniform_pm1(args.seed + 6, (n, F), device=dev)
+        target = (torch.arange(n, device=dev) % F).to(torch.int32)
+        rows = torch.arange(0, n, 10, device=dev, dtype=torch.int32)
+        step = lambda: net.train_step(X, target, rows, 0.0)                      # noqa: E731
+        t = timed(step)
+        skinny = 2 * (med["gemm_ER"] + med["gemm_dH_K2"] + med["gemm_dA_transA"])
+        out.update({"gat_dims": [F, F, F], "train_step_ms": [round(x, 4) for x in t], "train_step_ms_median": round(statistics.median(t), 4),
+                    "skinny_products_share_of_step": round(skinny / statistics.median(t), 4)})
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", choices=sorted(CONFIGS), default=None, help="measure this configuration in this process")
+    ap.add_argument("--configs", default="rmat1m,headline", help="driver mode: the configurations to run, each in a child process")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--chunk", type=int, default=1024)
+    ap.add_argument("--trace", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=1)
+    args = ap.parse_args()
+    return measure(args) if args.config else driver(args)
+
+
+if __name__ == "__main__":
+    sys.exit(main())
