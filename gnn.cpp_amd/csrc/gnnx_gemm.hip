@@ -1408,9 +1408,10 @@ GNNX_API int gnnx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t
     // pairs, the generic kernel the last K % 64 rows into one more slab, added last by the in-order reduction
     const int64_t k_dma = transA && !transB && splits > 1 && dma_tn_shape_ok(M, N, K - K % 64) ? K - K % 64 : 0;
     if (k_dma > 0) g.k_per_split = ceil_div(k_dma / 64, splits) * 64;  // the LDS-DMA loop takes K-tiles in pairs
-    const int slabs = splits + (k_dma > 0 && k_dma < K ? 1 : 0);
     if (splits > 1) {
-        size_t need = sizeof(float) * (size_t)slabs * (size_t)M * (size_t)N;
+        // what gnnx_gemm_workspace() asks for, whether or not this call fills the slab of the last K % 64 rows: one figure, so that a
+        // caller who passes less is refused on every shape and not only where the remainder slab exists
+        size_t need = sizeof(float) * (size_t)(splits + 1) * (size_t)M * (size_t)N;
         GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu",
                      workspace_bytes, need);
         g.slab = static_cast<float *>(d_workspace);

@@ -266,8 +266,15 @@ int gnnx_gemm_nt_bf16out_f32(int64_t M, int64_t N, int64_t K, const float *d_X, 
  * N % 128 == 0 and K % 64 == 0 take the LDS-DMA kernels; for X . W^T those want the small W k-major, so
  * gnnx_gemm_workspace() asks for K * N floats and the call transposes W into them first (same products, same order).  Every
  * kernel computes an output element as the same k-ascending fmaf chain: which kernel ran never changes a bit.
- * Workspace: gnnx_gemm_workspace() bytes (split-K slabs for transA=1; W^T for the tall transB=1 case; else 0).  A call with
- * less workspace than that still works, on the generic kernels.
+ * Workspace: gnnx_gemm_workspace() bytes (split-K slabs for transA=1; W^T for the tall transB=1 case; else 0).  The W^T
+ * workspace is optional: a tall transB=1 call with less (or none) still works, on the register-staged kernels, and gives the
+ * same bits.  The split-K slabs are required, and the required size is gnnx_gemm_workspace()'s figure, not the slabs a given call
+ * happens to fill: a transA=1 call for which that figure is not 0 and that passes less returns GNNX_ERR_WORKSPACE and leaves C
+ * untouched (one workgroup per output tile over millions of rows would be far slower, silently).
+ * Epilogue, the same in every kernel: v = fl(alpha * acc), then, only if beta != 0, fl(v + fl(beta * C)) -- three separately
+ * rounded float32 operations, nothing fused; with beta == 0, C is never read (it may hold NaN).  K == 0 gives C = beta * C;
+ * M == 0 or N == 0 returns GNNX_OK and writes nothing.  ldc < N is GNNX_ERR_INVALID_ARG; lda or ldb below the operand's row
+ * length (K, or M resp. N for a k-major operand) is GNNX_ERR_SHAPE.
  */
 int gnnx_gemm_workspace(int transA, int transB, int64_t M, int64_t N, int64_t K, size_t *bytes);
 int gnnx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, float alpha, const float *d_A,
