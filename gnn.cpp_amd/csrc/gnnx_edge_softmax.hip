@@ -16,6 +16,8 @@
 //     sit in the workspace and are combined in the fixed order by one lane per hub.
 // Every launch is on the caller's stream and every ordering is a stream ordering; nothing is allocated or synchronised.  The
 // order in which rows land in the lists varies from call to call, the values do not: a row's result never depends on its slot.
+// Several heads (include/gnnx.h "multi-head attention"): every kernel takes the head from blockIdx.y and reads column h of the entry-major
+// per-entry arrays; the lists are the pattern's and are written by head 0 only.  The single-head entry points launch one head.
 #include "gnnx_common.h"
 
 #pragma clang fp contract(off)
@@ -36,7 +38,8 @@ constexpr int kCounters = 16;       // int32 words in front of the workspace: [0
 struct Pre {
     const int32_t *colidx;
     const float *scores, *rowterm, *colterm;
-    int64_t rs, cs;
+    int64_t rs, cs;        // strides of the two terms
+    int64_t ls;            // leading dimension of scores ([nnz, H] entry-major; 1 in the single-head calls)
     float slope;
 };
 
@@ -46,13 +49,13 @@ struct Lists {
     int32_t *long_rows;     // [cap_long]
     int32_t *hub_rows;      // [cap_hub]; -1: a hub whose segments did not fit (only a broken CSR can do that)
     int32_t *hub_seg0;      // [cap_hub] first slot of the hub's segments in `part`
-    float *hub_val;         // [cap_hub] the row's maximum, later its sum (forward); dot_i (backward)
-    float *part;            // [cap_seg] one value per segment
+    float *hub_val;         // [H, cap_hub] the row's maximum, later its sum (forward); dot_i (backward)
+    float *part;            // [H, cap_seg] one value per segment
     int32_t *seg_hub;       // [cap_seg] the hub (its slot in hub_rows) that a segment slot belongs to; -1: none
     int64_t cap_long, cap_hub, cap_seg;
 };
 
-size_t carve(int32_t n_rows, int64_t nnz, void *base, Lists *out)
+size_t carve(int32_t n_rows, int64_t nnz, int32_t H, void *base, Lists *out)
 {
     Lists w{};
     w.cap_long = nnz / (kShortW + 1) < n_rows ? nnz / (kShortW + 1) : n_rows;   // rows of more than kShortW entries
@@ -69,8 +72,8 @@ size_t carve(int32_t n_rows, int64_t nnz, void *base, Lists *out)
     w.long_rows = reinterpret_cast<int32_t *>(take((size_t)w.cap_long));
     w.hub_rows = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
     w.hub_seg0 = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
-    w.hub_val = reinterpret_cast<float *>(take((size_t)w.cap_hub));
-    w.part = reinterpret_cast<float *>(take((size_t)w.cap_seg));
+    w.hub_val = reinterpret_cast<float *>(take((size_t)w.cap_hub * H));   // head h: hub_val + h cap_hub
+    w.part = reinterpret_cast<float *>(take((size_t)w.cap_seg * H));      //         part + h cap_seg
     w.seg_hub = reinterpret_cast<int32_t *>(take((size_t)w.cap_seg));
     if (out) *out = w;
     return (off + 255) & ~(size_t)255;
@@ -81,7 +84,7 @@ __device__ __forceinline__ float pre_activation(const Pre &a, int64_t p, float r
 {
     float t = 0.f;
     if (a.scores) {
-        t = a.scores[p];
+        t = a.scores[p * a.ls];
         if (a.rowterm) t = t + rt;
     } else if (a.rowterm) {
         t = rt;
@@ -94,6 +97,20 @@ __device__ __forceinline__ float pre_activation(const Pre &a, int64_t p, float r
 }
 
 __device__ __forceinline__ float leaky(float t, float slope) { return t > 0.f ? t : t * slope; }
+
+// The head coordinate: blockIdx.y of every kernel below.  Head h reads column h of the entry-major per-entry arrays and element h of each
+// term's row, and owns its own run of hub values and segment slots; the row lists (a function of the pattern alone) are shared and
+// written by head 0 of the short-row kernel.  The single-head entry points are H = 1: every stride below is then 1 and head() adds 0.
+__device__ __forceinline__ int head(Pre &a, Lists &w)
+{
+    const int h = blockIdx.y;
+    if (a.scores) a.scores += h;
+    if (a.rowterm) a.rowterm += h;
+    if (a.colterm) a.colterm += h;
+    w.hub_val += (int64_t)h * w.cap_hub;
+    w.part += (int64_t)h * w.cap_seg;
+    return h;
+}
 
 // f(k, t_p) for the entries k = l, l + 64, ... < n of a row piece whose first entry is b, in ascending k; the gathers of four entries
 // are issued before the first is consumed (a lane's chain of dependent column-term loads is what a long row waits for)
@@ -217,8 +234,11 @@ __device__ __forceinline__ int64_t listed(const int32_t *counter, int64_t cap)
 // kShortW lanes per row, lane l holds entry l: e, x and the sum never leave registers.  The loads of a group's kShortR rows are all
 // issued before the first is consumed.
 __global__ __launch_bounds__(256) void fwd_short_kernel(int32_t n_rows, const int32_t *__restrict__ rowptr, Pre a, int unnorm,
-                                                        float *__restrict__ out, float *__restrict__ rowmax, float *__restrict__ rowsum, Lists w)
+                                                        float *__restrict__ out, int64_t ldo, float *__restrict__ rowmax,
+                                                        float *__restrict__ rowsum, Lists w)
 {
+    const int hd = head(a, w), H = gridDim.y;
+    out += hd;
     const int l = threadIdx.x & (kShortW - 1);
     const ShortRows r = load_short_rows(rowptr, n_rows);
     float e[kShortR];
@@ -230,7 +250,7 @@ __global__ __launch_bounds__(256) void fwd_short_kernel(int32_t n_rows, const in
             e[j] = leaky(pre_activation(a, (int64_t)r.b[j] + l, rt), a.slope);
         }
     }
-    classify(w, r);
+    if (hd == 0) classify(w, r);   // uniform in the workgroup
 #pragma unroll
     for (int j = 0; j < kShortR; j++) {
         const bool own = r.row[j] >= 0 && r.d[j] <= kShortW;
@@ -243,18 +263,20 @@ __global__ __launch_bounds__(256) void fwd_short_kernel(int32_t n_rows, const in
             acc = acc + x;
         }
         const float z = add_lanes<kShortW>(acc, lanes_of(r.d[j]));
-        if (have) out[(int64_t)r.b[j] + l] = unnorm ? x : __fdiv_rn(x, z);
+        if (have) out[((int64_t)r.b[j] + l) * ldo] = unnorm ? x : __fdiv_rn(x, z);
         if (own && l == 0) {
-            if (rowmax) rowmax[r.row[j]] = m;   // an empty row: -inf
-            if (rowsum) rowsum[r.row[j]] = z;   //               +0
+            if (rowmax) rowmax[(int64_t)r.row[j] * H + hd] = m;   // an empty row: -inf
+            if (rowsum) rowsum[(int64_t)r.row[j] * H + hd] = z;   //               +0
         }
     }
 }
 
 // a wavefront per listed row of kShortW < d <= S entries
 __global__ __launch_bounds__(256) void fwd_long_kernel(const int32_t *__restrict__ rowptr, Pre a, int unnorm, float *__restrict__ out,
-                                                       float *__restrict__ rowmax, float *__restrict__ rowsum, Lists w)
+                                                       int64_t ldo, float *__restrict__ rowmax, float *__restrict__ rowsum, Lists w)
 {
+    const int hd = head(a, w), H = gridDim.y;
+    out += hd;
     const int l = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
     const int64_t n_long = listed(&w.counters[0], w.cap_long);
@@ -274,28 +296,28 @@ __global__ __launch_bounds__(256) void fwd_long_kernel(const int32_t *__restrict
                 acc = acc + x;
             }
             z = add_lanes<64>(acc, G);
-            if (have) out[b + l] = unnorm ? x : __fdiv_rn(x, z);
+            if (have) out[(b + l) * ldo] = unnorm ? x : __fdiv_rn(x, z);
         } else {         // G = 64: lane l owns entries l, l + 64, ...; e, then x, wait in out[] for the next pass
             m = -INFINITY;
             for_lane_entries(a, b, d, rt, l, [&](int64_t k, float t) {
                 const float e = leaky(t, a.slope);
-                out[b + k] = e;
+                out[(b + k) * ldo] = e;
                 m = fmaxf(m, e);
             });
             m = max_lanes<64>(m);
             float acc = 0.f;
             for (int64_t k = l; k < d; k += 64) {
-                const float x = expf(out[b + k] - m);
-                out[b + k] = x;
+                const float x = expf(out[(b + k) * ldo] - m);
+                out[(b + k) * ldo] = x;
                 acc = acc + x;
             }
             z = add_lanes<64>(acc, 64);
             if (!unnorm)
-                for (int64_t k = l; k < d; k += 64) out[b + k] = __fdiv_rn(out[b + k], z);
+                for (int64_t k = l; k < d; k += 64) out[(b + k) * ldo] = __fdiv_rn(out[(b + k) * ldo], z);
         }
         if (l == 0) {
-            if (rowmax) rowmax[row] = m;
-            if (rowsum) rowsum[row] = z;
+            if (rowmax) rowmax[(int64_t)row * H + hd] = m;
+            if (rowsum) rowsum[(int64_t)row * H + hd] = z;
         }
     }
 }
@@ -320,14 +342,16 @@ __global__ __launch_bounds__(256) void fwd_long_kernel(const int32_t *__restrict
     }
 
 // e_p -> out, the segment's maximum -> part
-__global__ __launch_bounds__(256) void fwd_hub_max_kernel(const int32_t *__restrict__ rowptr, Pre a, float *__restrict__ out, Lists w)
+__global__ __launch_bounds__(256) void fwd_hub_max_kernel(const int32_t *__restrict__ rowptr, Pre a, float *__restrict__ out, int64_t ldo,
+                                                          Lists w)
 {
+    out += head(a, w);
     GNNX_FOR_HUB_SEGMENTS({
         const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
         float m = -INFINITY;
         for_lane_entries(a, b, n, rt, l, [&](int64_t k, float t) {
             const float e = leaky(t, a.slope);
-            out[b + k] = e;
+            out[(b + k) * ldo] = e;
             m = fmaxf(m, e);
         });
         m = max_lanes<64>(m);
@@ -338,6 +362,8 @@ __global__ __launch_bounds__(256) void fwd_hub_max_kernel(const int32_t *__restr
 // a wavefront per hub: the maximum of its segments' maxima -> hub_val (and rowmax)
 __global__ __launch_bounds__(256) void hub_combine_max_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ rowmax, Lists w)
 {
+    Pre none{};
+    const int hd = head(none, w), H = gridDim.y;
     const int l = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
     const int64_t n_hub = listed(&w.counters[1], w.cap_hub);
@@ -351,20 +377,22 @@ __global__ __launch_bounds__(256) void hub_combine_max_kernel(const int32_t *__r
         m = max_lanes<64>(m);
         if (l == 0) {
             w.hub_val[h] = m;
-            if (rowmax) rowmax[row] = m;
+            if (rowmax) rowmax[(int64_t)row * H + hd] = m;
         }
     }
 }
 
 // x_p = expf(e_p - m) -> out, the segment's sum (G = 64) -> part
-__global__ __launch_bounds__(256) void fwd_hub_exp_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ out, Lists w)
+__global__ __launch_bounds__(256) void fwd_hub_exp_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ out, int64_t ldo, Lists w)
 {
+    Pre none{};
+    out += head(none, w);
     GNNX_FOR_HUB_SEGMENTS({
         const float m = w.hub_val[h];
         float acc = 0.f;
         for (int64_t k = l; k < n; k += 64) {
-            const float x = expf(out[b + k] - m);
-            out[b + k] = x;
+            const float x = expf(out[(b + k) * ldo] - m);
+            out[(b + k) * ldo] = x;
             acc = acc + x;
         }
         acc = add_lanes<64>(acc, 64);
@@ -373,8 +401,11 @@ __global__ __launch_bounds__(256) void fwd_hub_exp_kernel(const int32_t *__restr
 }
 
 // one lane per hub: ((seg_0 + seg_1) + seg_2) + ... -> hub_val and, when given, rows[row]
-__global__ __launch_bounds__(256) void hub_combine_sum_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ rows, Lists w)
+// rows: [n_rows] with stride ldr between rows, head h at element h
+__global__ __launch_bounds__(256) void hub_combine_sum_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ rows, int64_t ldr, Lists w)
 {
+    Pre none{};
+    const int hd = head(none, w);
     const int64_t n_hub = listed(&w.counters[1], w.cap_hub);
     for (int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x; h < n_hub; h += (int64_t)gridDim.x * 256) {
         const int32_t row = w.hub_rows[h];
@@ -384,16 +415,18 @@ __global__ __launch_bounds__(256) void hub_combine_sum_kernel(const int32_t *__r
         float z = part[0];
         for (int64_t s = 1; s < nseg; s++) z = z + part[s];
         w.hub_val[h] = z;
-        if (rows) rows[row] = z;
+        if (rows) rows[(int64_t)row * ldr + hd] = z;
     }
 }
 
 // alpha_p = x_p / z
-__global__ __launch_bounds__(256) void fwd_hub_div_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ out, Lists w)
+__global__ __launch_bounds__(256) void fwd_hub_div_kernel(const int32_t *__restrict__ rowptr, float *__restrict__ out, int64_t ldo, Lists w)
 {
+    Pre none{};
+    out += head(none, w);
     GNNX_FOR_HUB_SEGMENTS({
         const float z = w.hub_val[h];
-        for (int64_t k = l; k < n; k += 64) out[b + k] = __fdiv_rn(out[b + k], z);
+        for (int64_t k = l; k < n; k += 64) out[(b + k) * ldo] = __fdiv_rn(out[(b + k) * ldo], z);
     })
 }
 
@@ -405,9 +438,30 @@ __device__ __forceinline__ float dt_of(float t, float slope, float al, float da,
     return t > 0.f ? de : de * slope;
 }
 
-__global__ __launch_bounds__(256) void bwd_short_kernel(int32_t n_rows, const int32_t *__restrict__ rowptr, Pre a, const float *__restrict__ alpha,
-                                                        const float *__restrict__ dalpha, float *__restrict__ dt, float *__restrict__ drowterm, Lists w)
+// the backward's per-entry arrays with their leading dimensions, and the stride between two rows of drowterm
+struct Bwd {
+    const float *alpha;
+    int64_t lda;
+    const float *dalpha;
+    int64_t ldd;
+    float *dt;
+    int64_t ldt;
+    float *drowterm;
+    int64_t drs;
+};
+
+__device__ __forceinline__ void head(Bwd &g, int h)
 {
+    g.alpha += h;
+    g.dalpha += h;
+    g.dt += h;
+    if (g.drowterm) g.drowterm += h;
+}
+
+__global__ __launch_bounds__(256) void bwd_short_kernel(int32_t n_rows, const int32_t *__restrict__ rowptr, Pre a, Bwd g, Lists w)
+{
+    const int hd = head(a, w);
+    head(g, hd);
     const int l = threadIdx.x & (kShortW - 1);
     const ShortRows r = load_short_rows(rowptr, n_rows);
     float al[kShortR], da[kShortR], t[kShortR];
@@ -417,12 +471,12 @@ __global__ __launch_bounds__(256) void bwd_short_kernel(int32_t n_rows, const in
         if (r.d[j] <= kShortW && l < r.d[j]) {
             const int64_t p = (int64_t)r.b[j] + l;
             const float rt = a.rowterm ? a.rowterm[(int64_t)r.row[j] * a.rs] : 0.f;
-            al[j] = alpha[p];
-            da[j] = dalpha[p];
+            al[j] = g.alpha[p * g.lda];
+            da[j] = g.dalpha[p * g.ldd];
             t[j] = pre_activation(a, p, rt);
         }
     }
-    classify(w, r);
+    if (hd == 0) classify(w, r);   // uniform in the workgroup
 #pragma unroll
     for (int j = 0; j < kShortR; j++) {
         const bool own = r.row[j] >= 0 && r.d[j] <= kShortW;
@@ -435,17 +489,17 @@ __global__ __launch_bounds__(256) void bwd_short_kernel(int32_t n_rows, const in
         if (have) {
             const float de = al[j] * (da[j] - dot);
             const float v = t[j] > 0.f ? de : de * a.slope;
-            dt[(int64_t)r.b[j] + l] = v;
+            g.dt[((int64_t)r.b[j] + l) * g.ldt] = v;
             acc = acc + v;
         }
         const float sum = add_lanes<kShortW>(acc, G);
-        if (own && l == 0 && drowterm) drowterm[r.row[j]] = sum;   // an empty row: +0
+        if (own && l == 0 && g.drowterm) g.drowterm[(int64_t)r.row[j] * g.drs] = sum;   // an empty row: +0
     }
 }
 
-__global__ __launch_bounds__(256) void bwd_long_kernel(const int32_t *__restrict__ rowptr, Pre a, const float *__restrict__ alpha,
-                                                       const float *__restrict__ dalpha, float *__restrict__ dt, float *__restrict__ drowterm, Lists w)
+__global__ __launch_bounds__(256) void bwd_long_kernel(const int32_t *__restrict__ rowptr, Pre a, Bwd g, Lists w)
 {
+    head(g, head(a, w));
     const int l = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
     const int64_t n_long = listed(&w.counters[0], w.cap_long);
@@ -459,57 +513,58 @@ __global__ __launch_bounds__(256) void bwd_long_kernel(const int32_t *__restrict
             const bool have = l < d;
             float al = 0.f, da = 0.f, acc = 0.f;
             if (have) {
-                al = alpha[b + l];
-                da = dalpha[b + l];
+                al = g.alpha[(b + l) * g.lda];
+                da = g.dalpha[(b + l) * g.ldd];
                 acc = acc + (al * da);
             }
             const float dot = add_lanes<64>(acc, G);
             acc = 0.f;
             if (have) {
                 const float v = dt_of(pre_activation(a, b + l, rt), a.slope, al, da, dot);
-                dt[b + l] = v;
+                g.dt[(b + l) * g.ldt] = v;
                 acc = acc + v;
             }
             sum = add_lanes<64>(acc, G);
         } else {
             float acc = 0.f;
-            for (int64_t k = l; k < d; k += 64) acc = acc + (alpha[b + k] * dalpha[b + k]);
+            for (int64_t k = l; k < d; k += 64) acc = acc + (g.alpha[(b + k) * g.lda] * g.dalpha[(b + k) * g.ldd]);
             const float dot = add_lanes<64>(acc, 64);
             acc = 0.f;
             for_lane_entries(a, b, d, rt, l, [&](int64_t k, float t) {
-                const float v = dt_of(t, a.slope, alpha[b + k], dalpha[b + k], dot);
-                dt[b + k] = v;
+                const float v = dt_of(t, a.slope, g.alpha[(b + k) * g.lda], g.dalpha[(b + k) * g.ldd], dot);
+                g.dt[(b + k) * g.ldt] = v;
                 acc = acc + v;
             });
             sum = add_lanes<64>(acc, 64);
         }
-        if (l == 0 && drowterm) drowterm[row] = sum;
+        if (l == 0 && g.drowterm) g.drowterm[(int64_t)row * g.drs] = sum;
     }
 }
 
 // the segment's sum of w_p = alpha_p * dalpha_p -> part
-__global__ __launch_bounds__(256) void bwd_hub_dot_kernel(const int32_t *__restrict__ rowptr, const float *__restrict__ alpha,
-                                                          const float *__restrict__ dalpha, Lists w)
+__global__ __launch_bounds__(256) void bwd_hub_dot_kernel(const int32_t *__restrict__ rowptr, Bwd g, Lists w)
 {
+    Pre none{};
+    head(g, head(none, w));
     GNNX_FOR_HUB_SEGMENTS({
         float acc = 0.f;
-        for (int64_t k = l; k < n; k += 64) acc = acc + (alpha[b + k] * dalpha[b + k]);
+        for (int64_t k = l; k < n; k += 64) acc = acc + (g.alpha[(b + k) * g.lda] * g.dalpha[(b + k) * g.ldd]);
         acc = add_lanes<64>(acc, 64);
         if (l == 0) part[s] = acc;
     })
 }
 
 // dt_p -> dt, the segment's sum of dt_p -> part
-__global__ __launch_bounds__(256) void bwd_hub_dt_kernel(const int32_t *__restrict__ rowptr, Pre a, const float *__restrict__ alpha,
-                                                         const float *__restrict__ dalpha, float *__restrict__ dt, Lists w)
+__global__ __launch_bounds__(256) void bwd_hub_dt_kernel(const int32_t *__restrict__ rowptr, Pre a, Bwd g, Lists w)
 {
+    head(g, head(a, w));
     GNNX_FOR_HUB_SEGMENTS({
         const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
         const float dot = w.hub_val[h];
         float acc = 0.f;
         for_lane_entries(a, b, n, rt, l, [&](int64_t k, float t) {
-            const float v = dt_of(t, a.slope, alpha[b + k], dalpha[b + k], dot);
-            dt[b + k] = v;
+            const float v = dt_of(t, a.slope, g.alpha[(b + k) * g.lda], g.dalpha[(b + k) * g.ldd], dot);
+            g.dt[(b + k) * g.ldt] = v;
             acc = acc + v;
         });
         acc = add_lanes<64>(acc, 64);
@@ -521,17 +576,106 @@ __global__ __launch_bounds__(256) void bwd_hub_dt_kernel(const int32_t *__restri
 
 inline uint32_t blocks_for_waves(int64_t waves, int64_t cap) { return (uint32_t)ceil_div(waves < cap ? waves : cap, 4); }
 
-// what both entry points check before any device call
-int check_args(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, const float *d_scores,
-               const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm, int64_t colterm_stride)
+// what every entry point checks before any device call
+int check_args(int32_t n_rows, int32_t n_cols, int64_t nnz, int32_t n_heads, const int32_t *d_rowptr, const int32_t *d_colidx,
+               const float *d_scores, int64_t lds, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm,
+               int64_t colterm_stride)
 {
     GNNX_REQUIRE(n_rows >= 0 && n_cols >= 0 && nnz >= 0, GNNX_ERR_INVALID_ARG, "negative size");
     GNNX_REQUIRE(nnz < (1ll << 31), GNNX_ERR_INVALID_ARG, "nnz does not fit the int32 CSR");
+    GNNX_REQUIRE(n_heads >= 1 && n_heads < 65536, GNNX_ERR_INVALID_ARG, "n_heads outside [1, 65535]");
     GNNX_REQUIRE(d_scores || d_rowterm || d_colterm, GNNX_ERR_INVALID_ARG, "scores, rowterm and colterm are all null");
-    GNNX_REQUIRE((!d_rowterm || rowterm_stride >= 1) && (!d_colterm || colterm_stride >= 1), GNNX_ERR_INVALID_ARG, "term stride < 1");
+    GNNX_REQUIRE(!d_scores || lds >= n_heads, GNNX_ERR_INVALID_ARG, "leading dimension of scores < n_heads");
+    GNNX_REQUIRE((!d_rowterm || rowterm_stride >= n_heads) && (!d_colterm || colterm_stride >= n_heads), GNNX_ERR_INVALID_ARG,
+                 "term stride < %d", n_heads);
     GNNX_REQUIRE(d_rowptr, GNNX_ERR_INVALID_ARG, "null pointer");
     GNNX_REQUIRE(nnz == 0 || (n_rows > 0 && n_cols > 0), GNNX_ERR_INVALID_ARG, "entries in a matrix without rows or columns");
     GNNX_REQUIRE(nnz == 0 || d_colidx, GNNX_ERR_INVALID_ARG, "null pointer");
+    return GNNX_OK;
+}
+
+int forward(int32_t n_rows, int32_t n_cols, int64_t nnz, int32_t H, const int32_t *d_rowptr, const int32_t *d_colidx, const float *d_scores,
+            int64_t lds, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm, int64_t colterm_stride, float negative_slope,
+            uint32_t flags, float *d_out, int64_t ldo, float *d_rowmax, float *d_rowsum, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_args(n_rows, n_cols, nnz, H, d_rowptr, d_colidx, d_scores, lds, d_rowterm, rowterm_stride, d_colterm, colterm_stride);
+    if (rc) return rc;
+    GNNX_REQUIRE(!(flags & ~(uint32_t)GNNX_EDGE_SOFTMAX_UNNORMALISED), GNNX_ERR_INVALID_ARG, "unknown flag");
+    GNNX_REQUIRE(ldo >= H, GNNX_ERR_INVALID_ARG, "leading dimension of out < n_heads");
+    GNNX_REQUIRE(nnz == 0 || d_out, GNNX_ERR_INVALID_ARG, "null pointer");
+    if (n_rows == 0) return GNNX_OK;
+    Lists w;
+    const size_t need = carve(n_rows, nnz, H, d_workspace, &w);
+    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    const Pre a{d_colidx, d_scores, d_rowterm, d_colterm, rowterm_stride, colterm_stride, lds, negative_slope};
+    const int unnorm = (flags & GNNX_EDGE_SOFTMAX_UNNORMALISED) ? 1 : 0;
+    const uint32_t Hy = (uint32_t)H;
+    GNNX_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(int32_t) * kCounters, st));
+    hipLaunchKernelGGL(fwd_short_kernel, dim3((uint32_t)ceil_div(n_rows, kShortRowsPerBlock), Hy), dim3(256), 0, st, n_rows, d_rowptr, a, unnorm,
+                       d_out, ldo, d_rowmax, d_rowsum, w);
+    GNNX_LAUNCH_CHECK();
+    if (w.cap_long > 0) {
+        hipLaunchKernelGGL(fwd_long_kernel, dim3(blocks_for_waves(w.cap_long, kLongWaves), Hy), dim3(256), 0, st, d_rowptr, a, unnorm, d_out, ldo,
+                           d_rowmax, d_rowsum, w);
+        GNNX_LAUNCH_CHECK();
+    }
+    if (w.cap_hub > 0) {
+        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves), Hy), hub_grid(blocks_for_waves(w.cap_hub, 1024), Hy);
+        hipLaunchKernelGGL(fwd_hub_max_kernel, seg_grid, dim3(256), 0, st, d_rowptr, a, d_out, ldo, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hub_combine_max_kernel, hub_grid, dim3(256), 0, st, d_rowptr, d_rowmax, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(fwd_hub_exp_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_out, ldo, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hub_combine_sum_kernel, dim3((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256), Hy), dim3(256), 0, st,
+                           d_rowptr, d_rowsum, (int64_t)H, w);
+        GNNX_LAUNCH_CHECK();
+        if (!unnorm) {
+            hipLaunchKernelGGL(fwd_hub_div_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_out, ldo, w);
+            GNNX_LAUNCH_CHECK();
+        }
+    }
+    return GNNX_OK;
+}
+
+int backward(int32_t n_rows, int32_t n_cols, int64_t nnz, int32_t H, const int32_t *d_rowptr, const int32_t *d_colidx, const float *d_scores,
+             int64_t lds, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm, int64_t colterm_stride, float negative_slope,
+             const Bwd &g, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_args(n_rows, n_cols, nnz, H, d_rowptr, d_colidx, d_scores, lds, d_rowterm, rowterm_stride, d_colterm, colterm_stride);
+    if (rc) return rc;
+    GNNX_REQUIRE(g.lda >= H && g.ldd >= H && g.ldt >= H && (!g.drowterm || g.drs >= H), GNNX_ERR_INVALID_ARG,
+                 "a leading dimension or the drowterm stride < n_heads");
+    GNNX_REQUIRE(nnz == 0 || (g.alpha && g.dalpha && g.dt), GNNX_ERR_INVALID_ARG, "null pointer");
+    if (n_rows == 0) return GNNX_OK;
+    Lists w;
+    const size_t need = carve(n_rows, nnz, H, d_workspace, &w);
+    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    const Pre a{d_colidx, d_scores, d_rowterm, d_colterm, rowterm_stride, colterm_stride, lds, negative_slope};
+    const uint32_t Hy = (uint32_t)H;
+    GNNX_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(int32_t) * kCounters, st));
+    hipLaunchKernelGGL(bwd_short_kernel, dim3((uint32_t)ceil_div(n_rows, kShortRowsPerBlock), Hy), dim3(256), 0, st, n_rows, d_rowptr, a, g, w);
+    GNNX_LAUNCH_CHECK();
+    if (w.cap_long > 0) {
+        hipLaunchKernelGGL(bwd_long_kernel, dim3(blocks_for_waves(w.cap_long, kLongWaves), Hy), dim3(256), 0, st, d_rowptr, a, g, w);
+        GNNX_LAUNCH_CHECK();
+    }
+    if (w.cap_hub > 0) {
+        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves), Hy);
+        const dim3 lane_grid((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256), Hy);
+        hipLaunchKernelGGL(bwd_hub_dot_kernel, seg_grid, dim3(256), 0, st, d_rowptr, g, w);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hub_combine_sum_kernel, lane_grid, dim3(256), 0, st, d_rowptr, (float *)nullptr, (int64_t)0, w);   // dot_i -> hub_val
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bwd_hub_dt_kernel, seg_grid, dim3(256), 0, st, d_rowptr, a, g, w);
+        GNNX_LAUNCH_CHECK();
+        if (g.drowterm) {
+            hipLaunchKernelGGL(hub_combine_sum_kernel, lane_grid, dim3(256), 0, st, d_rowptr, g.drowterm, g.drs, w);
+            GNNX_LAUNCH_CHECK();
+        }
+    }
     return GNNX_OK;
 }
 
@@ -540,7 +684,14 @@ int check_args(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_row
 GNNX_API int gnnx_edge_softmax_workspace(int32_t n_rows, int64_t nnz, size_t *bytes)
 {
     GNNX_REQUIRE(bytes && n_rows >= 0 && nnz >= 0 && nnz < (1ll << 31), GNNX_ERR_INVALID_ARG, "bad arguments");
-    *bytes = carve(n_rows, nnz, nullptr, nullptr);
+    *bytes = carve(n_rows, nnz, 1, nullptr, nullptr);
+    return GNNX_OK;
+}
+
+GNNX_API int gnnx_edge_softmax_heads_workspace(int32_t n_rows, int64_t nnz, int32_t n_heads, size_t *bytes)
+{
+    GNNX_REQUIRE(bytes && n_rows >= 0 && nnz >= 0 && nnz < (1ll << 31) && n_heads >= 1 && n_heads < 65536, GNNX_ERR_INVALID_ARG, "bad arguments");
+    *bytes = carve(n_rows, nnz, n_heads, nullptr, nullptr);
     return GNNX_OK;
 }
 
@@ -549,43 +700,18 @@ GNNX_API int gnnx_edge_softmax_csr_f32(int32_t n_rows, int32_t n_cols, int64_t n
                                        int64_t colterm_stride, float negative_slope, uint32_t flags, float *d_out, float *d_rowmax,
                                        float *d_rowsum, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_args(n_rows, n_cols, nnz, d_rowptr, d_colidx, d_scores, d_rowterm, rowterm_stride, d_colterm, colterm_stride);
-    if (rc) return rc;
-    GNNX_REQUIRE(!(flags & ~(uint32_t)GNNX_EDGE_SOFTMAX_UNNORMALISED), GNNX_ERR_INVALID_ARG, "unknown flag");
-    GNNX_REQUIRE(nnz == 0 || d_out, GNNX_ERR_INVALID_ARG, "null pointer");
-    if (n_rows == 0) return GNNX_OK;
-    Lists w;
-    const size_t need = carve(n_rows, nnz, d_workspace, &w);
-    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
-    const Pre a{d_colidx, d_scores, d_rowterm, d_colterm, rowterm_stride, colterm_stride, negative_slope};
-    const int unnorm = (flags & GNNX_EDGE_SOFTMAX_UNNORMALISED) ? 1 : 0;
-    GNNX_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(int32_t) * kCounters, st));
-    hipLaunchKernelGGL(fwd_short_kernel, dim3((uint32_t)ceil_div(n_rows, kShortRowsPerBlock)), dim3(256), 0, st, n_rows, d_rowptr, a, unnorm,
-                       d_out, d_rowmax, d_rowsum, w);
-    GNNX_LAUNCH_CHECK();
-    if (w.cap_long > 0) {
-        hipLaunchKernelGGL(fwd_long_kernel, dim3(blocks_for_waves(w.cap_long, kLongWaves)), dim3(256), 0, st, d_rowptr, a, unnorm, d_out, d_rowmax,
-                           d_rowsum, w);
-        GNNX_LAUNCH_CHECK();
-    }
-    if (w.cap_hub > 0) {
-        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves)), hub_grid(blocks_for_waves(w.cap_hub, 1024));
-        hipLaunchKernelGGL(fwd_hub_max_kernel, seg_grid, dim3(256), 0, st, d_rowptr, a, d_out, w);
-        GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hub_combine_max_kernel, hub_grid, dim3(256), 0, st, d_rowptr, d_rowmax, w);
-        GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(fwd_hub_exp_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_out, w);
-        GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hub_combine_sum_kernel, dim3((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256)), dim3(256), 0, st, d_rowptr,
-                           d_rowsum, w);
-        GNNX_LAUNCH_CHECK();
-        if (!unnorm) {
-            hipLaunchKernelGGL(fwd_hub_div_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_out, w);
-            GNNX_LAUNCH_CHECK();
-        }
-    }
-    return GNNX_OK;
+    return forward(n_rows, n_cols, nnz, 1, d_rowptr, d_colidx, d_scores, 1, d_rowterm, rowterm_stride, d_colterm, colterm_stride, negative_slope,
+                   flags, d_out, 1, d_rowmax, d_rowsum, d_workspace, workspace_bytes, stream);
+}
+
+GNNX_API int gnnx_edge_softmax_csr_heads_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                             int32_t n_heads, const float *d_scores, int64_t lds, const float *d_rowterm, int64_t rowterm_stride,
+                                             const float *d_colterm, int64_t colterm_stride, float negative_slope, uint32_t flags, float *d_out,
+                                             int64_t ldo, float *d_rowmax, float *d_rowsum, void *d_workspace, size_t workspace_bytes,
+                                             void *stream)
+{
+    return forward(n_rows, n_cols, nnz, n_heads, d_rowptr, d_colidx, d_scores, lds, d_rowterm, rowterm_stride, d_colterm, colterm_stride,
+                   negative_slope, flags, d_out, ldo, d_rowmax, d_rowsum, d_workspace, workspace_bytes, stream);
 }
 
 GNNX_API int gnnx_edge_softmax_bwd_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
@@ -593,37 +719,19 @@ GNNX_API int gnnx_edge_softmax_bwd_csr_f32(int32_t n_rows, int32_t n_cols, int64
                                            int64_t colterm_stride, float negative_slope, const float *d_alpha, const float *d_dalpha,
                                            float *d_dt, float *d_drowterm, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_args(n_rows, n_cols, nnz, d_rowptr, d_colidx, d_scores, d_rowterm, rowterm_stride, d_colterm, colterm_stride);
-    if (rc) return rc;
-    GNNX_REQUIRE(nnz == 0 || (d_alpha && d_dalpha && d_dt), GNNX_ERR_INVALID_ARG, "null pointer");
-    if (n_rows == 0) return GNNX_OK;
-    Lists w;
-    const size_t need = carve(n_rows, nnz, d_workspace, &w);
-    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
-    const Pre a{d_colidx, d_scores, d_rowterm, d_colterm, rowterm_stride, colterm_stride, negative_slope};
-    GNNX_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(int32_t) * kCounters, st));
-    hipLaunchKernelGGL(bwd_short_kernel, dim3((uint32_t)ceil_div(n_rows, kShortRowsPerBlock)), dim3(256), 0, st, n_rows, d_rowptr, a, d_alpha,
-                       d_dalpha, d_dt, d_drowterm, w);
-    GNNX_LAUNCH_CHECK();
-    if (w.cap_long > 0) {
-        hipLaunchKernelGGL(bwd_long_kernel, dim3(blocks_for_waves(w.cap_long, kLongWaves)), dim3(256), 0, st, d_rowptr, a, d_alpha, d_dalpha, d_dt,
-                           d_drowterm, w);
-        GNNX_LAUNCH_CHECK();
-    }
-    if (w.cap_hub > 0) {
-        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves));
-        const dim3 lane_grid((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256));
-        hipLaunchKernelGGL(bwd_hub_dot_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_alpha, d_dalpha, w);
-        GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hub_combine_sum_kernel, lane_grid, dim3(256), 0, st, d_rowptr, (float *)nullptr, w);   // dot_i -> hub_val
-        GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(bwd_hub_dt_kernel, seg_grid, dim3(256), 0, st, d_rowptr, a, d_alpha, d_dalpha, d_dt, w);
-        GNNX_LAUNCH_CHECK();
-        if (d_drowterm) {
-            hipLaunchKernelGGL(hub_combine_sum_kernel, lane_grid, dim3(256), 0, st, d_rowptr, d_drowterm, w);
-            GNNX_LAUNCH_CHECK();
-        }
-    }
-    return GNNX_OK;
+    const Bwd g{d_alpha, 1, d_dalpha, 1, d_dt, 1, d_drowterm, 1};
+    return backward(n_rows, n_cols, nnz, 1, d_rowptr, d_colidx, d_scores, 1, d_rowterm, rowterm_stride, d_colterm, colterm_stride, negative_slope,
+                    g, d_workspace, workspace_bytes, stream);
+}
+
+GNNX_API int gnnx_edge_softmax_bwd_csr_heads_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                                 int32_t n_heads, const float *d_scores, int64_t lds, const float *d_rowterm,
+                                                 int64_t rowterm_stride, const float *d_colterm, int64_t colterm_stride, float negative_slope,
+                                                 const float *d_alpha, int64_t lda, const float *d_dalpha, int64_t ldd, float *d_dt, int64_t ldt,
+                                                 float *d_drowterm, int64_t drowterm_stride, void *d_workspace, size_t workspace_bytes,
+                                                 void *stream)
+{
+    const Bwd g{d_alpha, lda, d_dalpha, ldd, d_dt, ldt, d_drowterm, drowterm_stride};
+    return backward(n_rows, n_cols, nnz, n_heads, d_rowptr, d_colidx, d_scores, lds, d_rowterm, rowterm_stride, d_colterm, colterm_stride,
+                    negative_slope, g, d_workspace, workspace_bytes, stream);
 }

@@ -641,6 +641,127 @@ def edge_softmax_bwd(rowptr, colidx, alpha, dalpha, scores=None, rowterm=None, c
     return dt, drow
 
 
+def _entry_major(t, nnz, H, what, where):
+    """Leading dimension of a per-entry, per-head array: float32 [nnz, H], unit stride along the heads (a column slab of a wider
+    [nnz, ld] array is fine)."""
+    if t.dim() != 2 or tuple(t.shape) != (nnz, H) or t.dtype != torch.float32 or (H > 1 and t.stride(1) != 1):
+        raise capi.GnnxError(-2, where, f"{what} must be an entry-major float32 [{nnz}, {H}] array, got {tuple(t.shape)} {t.dtype}")
+    return int(t.stride(0)) if nnz > 1 else H
+
+
+def _heads_of(X, n_heads, where):
+    F = int(X.shape[1])
+    if n_heads < 1 or F % n_heads or F == 0:
+        raise capi.GnnxError(-2, where, f"{F} features do not split into {n_heads} heads")
+    return F // n_heads
+
+
+def csr_rowsum_heads(rowptr, vals, out=None):
+    """gnnx_csr_rowsum_heads_f32: out[i, h] = the sum of vals[p, h] over the entries p of row i, added in ascending p from +0 -- column h
+    carries the bits of csr_rowsum(rowptr, vals[:, h]).  vals: entry-major float32 [nnz, H]; out: [n_rows, H], a column slab of a wider
+    matrix allowed."""
+    n_rows, nnz, H = int(rowptr.numel() - 1), int(vals.shape[0]), int(vals.shape[1])
+    ldv = _entry_major(vals, nnz, H, "vals", "csr_rowsum_heads")
+    if out is None:
+        out = torch.empty((n_rows, H), dtype=torch.float32, device=rowptr.device)
+    op, ldo = _edge_terms_heads(out, n_rows, H, "out")
+    capi.call("gnnx_csr_rowsum_heads_f32", _ptr(rowptr), _ptr(vals) if nnz else None, ldv, n_rows, H, op, ldo, _stream())
+    return out
+
+
+def spmm_heads(rowptr, colidx, X, vals, n_heads, bias=None, beta=0.0, relu_out=False, out=None):
+    """gnnx_spmm_csr_heads_f32: Y[i, hD + j] = beta*Y + sum_p vals[p, h] * X[c_p, hD + j] + bias, optional ReLU -- head h carries the bits
+    of spmm(vals = vals[:, h]) on column slab h of X.  X: [n_cols, H*D]; vals: entry-major float32 [nnz, H] (a slab of a wider array is
+    fine); out: [n_rows, H*D], a column slab of a wider matrix allowed (the other columns are not touched).  No plan: a row is one lane
+    group's chain."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    n_cols = int(X.shape[0])
+    D = _heads_of(X, n_heads, "spmm_heads")
+    ldv = _entry_major(vals, nnz, n_heads, "vals", "spmm_heads")
+    if out is None:
+        out = torch.empty((n_rows, n_heads * D), dtype=torch.float32, device=X.device)
+    assert tuple(out.shape) == (n_rows, n_heads * D) and (bias is None or int(bias.numel()) == n_heads * D)
+    # an empty pattern has no entry to read: any non-null pointer stands in for the two per-entry arrays
+    capi.call("gnnx_spmm_csr_heads_f32", n_rows, n_cols, n_heads, D, _ptr(rowptr), _ptr(colidx) if nnz else _ptr(rowptr),
+              _ptr(vals) if nnz else _ptr(rowptr), ldv, _ptr(bias), _ptr(X), _ld(X), float(beta), int(bool(relu_out)), _ptr(out), _ld(out), _stream())
+    return out
+
+
+def sddmm_heads(rowptr, colidx, L, R, n_heads, out=None):
+    """gnnx_sddmm_csr_heads_f32: out[p, h] = <L[i, slab h], R[c_p, slab h]> for every stored entry p of row i -- entry-major float32
+    [nnz, H]; head h carries the bits of sddmm on column slab h.  L: [n_rows, H*D], R: [n_cols, H*D] (L is R is allowed)."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    n_cols = int(R.shape[0])
+    D = _heads_of(R, n_heads, "sddmm_heads")
+    if tuple(L.shape) != (n_rows, n_heads * D):
+        raise capi.GnnxError(-2, "sddmm_heads", f"L is {tuple(L.shape)}, the pattern has {n_rows} rows and R {n_heads * D} features")
+    if out is None:
+        out = torch.empty((nnz, n_heads), dtype=torch.float32, device=R.device)
+    ldo = _entry_major(out, nnz, n_heads, "out", "sddmm_heads")
+    capi.call("gnnx_sddmm_csr_heads_f32", n_rows, n_cols, n_heads, D, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(L), _ld(L),
+              _ptr(R), _ld(R), _ptr(out) if nnz else None, ldo, _stream())
+    return out
+
+
+def _edge_terms_heads(t, n, H, what):
+    """(pointer, row stride in elements) of a per-vertex, per-head term: float32 [n, H] with unit stride along the heads (one half of an
+    [n, 2H] matrix is fine)."""
+    if t is None:
+        return None, 0
+    if t.dim() != 2 or tuple(t.shape) != (n, H) or t.dtype != torch.float32 or (H > 1 and t.stride(1) != 1):
+        raise capi.GnnxError(-2, "edge_softmax_heads", f"{what} must be a float32 [{n}, {H}] array, got {tuple(t.shape)} {t.dtype}")
+    return _ptr(t), (int(t.stride(0)) if n > 1 else H)
+
+
+def _edge_softmax_heads_args(rowptr, colidx, n_heads, scores, rowterm, colterm):
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    lds = _entry_major(scores, nnz, n_heads, "scores", "edge_softmax_heads") if scores is not None else n_heads
+    n_cols = int(colterm.shape[0]) if colterm is not None else n_rows
+    rt, rs = _edge_terms_heads(rowterm, n_rows, n_heads, "rowterm")
+    ct, cs = _edge_terms_heads(colterm, n_cols, n_heads, "colterm")
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_edge_softmax_heads_workspace", n_rows, nnz, n_heads, C.byref(wsb))
+    ws = _workspace(wsb.value, rowptr.device, "edge_softmax")
+    return n_rows, n_cols, nnz, lds, rt, rs, ct, cs, ws
+
+
+def edge_softmax_heads(rowptr, colidx, n_heads, scores=None, rowterm=None, colterm=None, negative_slope=1.0, unnormalised=False,
+                       want_stats=False, out=None):
+    """gnnx_edge_softmax_csr_heads_f32: edge_softmax per head -- alpha entry-major float32 [nnz, H]; scores [nnz, H], rowterm [n_rows, H],
+    colterm [n_cols, H] (each optional; the two halves of one [n, 2H] matrix serve as the terms).  want_stats: (alpha, rowmax, rowsum)
+    with the statistics as [n_rows, H].  Head h carries the bits of edge_softmax on column h of every operand."""
+    n_rows, n_cols, nnz, lds, rt, rs, ct, cs, ws = _edge_softmax_heads_args(rowptr, colidx, n_heads, scores, rowterm, colterm)
+    dev = rowptr.device
+    if out is None:
+        out = torch.empty((nnz, n_heads), dtype=torch.float32, device=dev)
+    ldo = _entry_major(out, nnz, n_heads, "out", "edge_softmax_heads")
+    rowmax = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if want_stats else None
+    rowsum = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if want_stats else None
+    capi.call("gnnx_edge_softmax_csr_heads_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, n_heads,
+              _ptr(scores) if nnz else None, lds, rt, rs, ct, cs, float(negative_slope), EDGE_SOFTMAX_UNNORMALISED if unnormalised else 0,
+              _ptr(out) if nnz else None, ldo, _ptr(rowmax), _ptr(rowsum), _ptr(ws), ws.numel(), _stream())
+    return (out, rowmax, rowsum) if want_stats else out
+
+
+def edge_softmax_heads_bwd(rowptr, colidx, n_heads, alpha, dalpha, scores=None, rowterm=None, colterm=None, negative_slope=1.0,
+                           drowterm_out=None, dt_out=None):
+    """gnnx_edge_softmax_bwd_csr_heads_f32: (dt [nnz, H], drowterm [n_rows, H]) from alpha = edge_softmax_heads(...) of the same operands
+    and dalpha = dL/dalpha, all entry-major.  drowterm_out: a float32 [n_rows, H] view with unit stride along the heads, e.g. the left
+    half of an [n, 2H] buffer."""
+    n_rows, n_cols, nnz, lds, rt, rs, ct, cs, ws = _edge_softmax_heads_args(rowptr, colidx, n_heads, scores, rowterm, colterm)
+    lda = _entry_major(alpha, nnz, n_heads, "alpha", "edge_softmax_heads_bwd")
+    ldd = _entry_major(dalpha, nnz, n_heads, "dalpha", "edge_softmax_heads_bwd")
+    dev = rowptr.device
+    dt = torch.empty((nnz, n_heads), dtype=torch.float32, device=dev) if dt_out is None else dt_out
+    ldt = _entry_major(dt, nnz, n_heads, "dt", "edge_softmax_heads_bwd")
+    drow = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if drowterm_out is None else drowterm_out
+    dp, drs = _edge_terms_heads(drow, n_rows, n_heads, "drowterm_out")
+    capi.call("gnnx_edge_softmax_bwd_csr_heads_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, n_heads,
+              _ptr(scores) if nnz else None, lds, rt, rs, ct, cs, float(negative_slope), _ptr(alpha) if nnz else None, lda,
+              _ptr(dalpha) if nnz else None, ldd, _ptr(dt) if nnz else None, ldt, dp, drs, _ptr(ws), ws.numel(), _stream())
+    return dt, drow
+
+
 def transpose(X, out=None):
     """gnnx_transpose_f32: out[c, r] = X[r, c] (materialised)."""
     R, Cn = X.shape
@@ -1339,14 +1460,29 @@ class GatStack:
         rp_t, ci_t, _ = csr_from_coo_weighted(dst, src, w, n, DIAG_FILL)
         g = CsrGraph(n, rp, ci, rp_t, ci_t)                                   # g.make_plans(...) for a power-law graph
     A vertex without entries (only possible without the diagonal) has an empty softmax: its row is the bias alone.
-    One head; several heads would be a loop over column slabs of H (the aggregation takes one value per entry)."""
 
-    def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda"):
+    heads=[h_0 .. h_{L-1}] makes layer l a multi-head layer of h_l heads of width D = dims[l+1] / h_l whose output is the concatenation
+    of the heads (the usual last layer is one head; head averaging and attention dropout are not implemented).  The layer runs on the
+    multi-head calls -- edge_softmax_heads, spmm_heads, sddmm_heads, csr_rowsum_heads -- which read the pattern once for all heads; the
+    attention vectors ride as one [2 h_l, dims[l+1]] matrix A that is zero outside its blocks (row h: a_l of head h in the head's columns,
+    row h_l + h: a_r), so ER = H A^T is [n, 2 h_l] and the two products of the backward work as for one head; dA is masked to the blocks.
+    heads=None is the single-head path above; heads=[1, .., 1] gives its bits."""
+
+    def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda", heads=None):
         self.g = g
         self.dims = list(dims)
         self.negative_slope = float(negative_slope)
         self.map_t = g.attention_map()
         L = len(dims) - 1
+        self.heads = None
+        if heads is not None:
+            heads = list(heads)
+            if len(heads) != L or any(int(k) != k or k < 1 for k in heads):
+                raise ValueError(f"heads must list {L} positive integers, one per layer, got {heads}")
+            bad = [l for l in range(L) if dims[l + 1] % heads[l]]
+            if bad:
+                raise ValueError(f"layer {bad[0]}: {dims[bad[0] + 1]} features do not split into {heads[bad[0]]} heads")
+            self.heads = [int(k) for k in heads]
         self.W = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
         self.A = [uniform_pm1(seed + 2 * l + 1, (2, dims[l + 1]), scale=dims[l + 1] ** -0.5, device=device) for l in range(L)]   # [a_l; a_r]
         self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
@@ -1355,6 +1491,16 @@ class GatStack:
         self.db = [torch.zeros_like(b) for b in self.b]
         self._saved = None
         self._buf = {}
+        if self.heads is not None:   # [a_l; a_r] of every head drawn as before, then laid out in the blocks of the [2 Hh, Hh D] matrix
+            self.A_mask = []
+            for l, Hh in enumerate(self.heads):
+                D = dims[l + 1] // Hh
+                block = torch.kron(torch.eye(Hh, dtype=torch.float32, device=device), torch.ones((1, D), dtype=torch.float32, device=device))
+                mask = torch.cat([block, block]).contiguous()                                   # [2 Hh, Hh D]
+                draw = uniform_pm1(seed + 2 * l + 1, (2, dims[l + 1]), scale=D ** -0.5, device=device)
+                self.A[l] = (torch.cat([draw[0:1].expand(Hh, -1), draw[1:2].expand(Hh, -1)]) * mask).contiguous()
+                self.dA[l] = torch.zeros_like(self.A[l])
+                self.A_mask.append(mask)
 
     def _tmp(self, key, shape, device, zero=False):
         t = self._buf.get(key)
@@ -1373,11 +1519,25 @@ class GatStack:
         alpha = edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=self.negative_slope)
         return ER, alpha
 
+    def attention_heads(self, H, l):
+        """(ER, alpha) of the multi-head layer l: ER = H A^T as [n, 2 Hh] (el of head h in column h, er in column Hh + h), alpha entry-major
+        [nnz, Hh] = edge_softmax_heads(rowterm = ER[:, :Hh], colterm = ER[:, Hh:])."""
+        g, Hh = self.g, self.heads[l]
+        ER = gemm(H, self.A[l], transB=True)
+        alpha = edge_softmax_heads(g.rowptr, g.colidx, Hh, rowterm=ER[:, :Hh], colterm=ER[:, Hh:], negative_slope=self.negative_slope)
+        return ER, alpha
+
     def forward(self, X):
         g, L = self.g, len(self.W)
         saved, h = [], X
         for l in range(L):
             H = linear_fwd(h, self.W[l])
+            if self.heads is not None:
+                ER, alpha = self.attention_heads(H, l)
+                Y = spmm_heads(g.rowptr, g.colidx, H, alpha, self.heads[l], bias=self.b[l], relu_out=l + 1 < L)
+                saved.append((h, H, ER, alpha, Y))
+                h = Y
+                continue
             ER, alpha = self.attention(H, l)
             # the ReLU between layers rides in the aggregation's epilogue: only relu(Z) is stored (its sign is the mask)
             Y = spmm(g.rowptr, g.colidx, H, vals=alpha, bias=self.b[l], plan=g.plan, relu_out=l + 1 < L)
@@ -1396,6 +1556,14 @@ class GatStack:
         for l in reversed(range(L)):
             h, H, ER, alpha, _ = self._saved[l]
             dev = G.device
+            if self.heads is not None:
+                dH = self._backward_heads(l, G, H, ER, alpha)
+                gemm(dH, h, transA=True, out=self.dW[l])
+                if l == 0:
+                    G = gemm(dH, self.W[l]) if input_grad else None
+                else:
+                    G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
+                continue
             dalpha = spmm_vals_grad(g.rowptr, g.colidx, G, H)
             dER_t = self._tmp("dER_t", (2, n), dev)                                   # row 0: del, row 1: der
             dt, _ = edge_softmax_bwd(g.rowptr, g.colidx, alpha, dalpha, rowterm=ER[:, 0], colterm=ER[:, 1],
@@ -1415,9 +1583,26 @@ class GatStack:
                 G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
         return G
 
+    def _backward_heads(self, l, G, H, ER, alpha):
+        """dH of the multi-head layer l from G = dL/dZ (Z the aggregated rows), and dA[l] (masked to its blocks)."""
+        g, n, Hh, dev = self.g, self.g.n, self.heads[l], G.device
+        dalpha = sddmm_heads(g.rowptr, g.colidx, G, H, Hh)                            # dL/dalpha: the aggregation's value gradient
+        dER = self._tmp(("dER", Hh), (n, 2 * Hh), dev)                                # left half: del, right half: der
+        dt, _ = edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, rowterm=ER[:, :Hh], colterm=ER[:, Hh:],
+                                       negative_slope=self.negative_slope, drowterm_out=dER[:, :Hh])
+        vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh), dev)
+        self._to_transposed(dt, vals_t)
+        csr_rowsum_heads(g.rowptr_t, vals_t, out=dER[:, Hh:])                         # der: what flows back to a column's vertex
+        self._to_transposed(alpha, vals_t)
+        dH = spmm_heads(g.rowptr_t, g.colidx_t, G, vals_t, Hh)                        # through the aggregated rows
+        gemm(dER, self.A[l], out=dH, beta=1.0)                                        # + [del der] . A, through ER
+        gemm(dER, H, transA=True, out=self.dA[l])
+        binary("mul", self.dA[l], self.A_mask[l], out=self.dA[l])                     # the entries outside the blocks are not parameters
+        return dH
+
     def _to_transposed(self, vals, out):
         if self.g.nnz:
-            gather_rows(vals.reshape(-1, 1), self.map_t, out=out.reshape(-1, 1))
+            gather_rows(vals.reshape(int(vals.shape[0]), -1), self.map_t, out=out.reshape(int(out.shape[0]), -1))
         return out
 
     def step(self, lr, weight_decay=0.0):

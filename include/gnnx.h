@@ -671,6 +671,72 @@ int gnnx_edge_softmax_bwd_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, c
                                   int64_t colterm_stride, float negative_slope, const float *d_alpha, const float *d_dalpha,
                                   float *d_dt, float *d_drowterm, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ multi-head attention --------- */
+/*
+ * The three calls of a graph-attention layer -- aggregation, edge scores, edge softmax -- for H heads at once.  Feature matrices are
+ * [rows, n_heads * head_dim]; head h owns columns h D .. h D + D - 1 (D = head_dim).  Every per-entry, per-head array is ENTRY-MAJOR:
+ * a[p * ld + h], h < n_heads, ld >= n_heads in elements, so that the H values of one entry are one contiguous piece.
+ *
+ * THE CONTRACT of every call below is one sentence: head h of the result carries the bits that the single-head call above gives on slab
+ * h of the feature matrices and column h of the per-entry arrays.  Every order stays the one already documented: the aggregation's ONE
+ * accumulator per output element in descending column order (gnnx_spmm_csr_f32), the SDDMM lane-group order with F := head_dim
+ * (gnnx_sddmm_csr_f32), the edge softmax's ROW ORDER with S = 4096 (gnnx_edge_softmax_csr_f32).  How heads, entries and rows map to
+ * lanes never shows in the result; tests/heads_ref.py restates the calls in NumPy and the GPU tests hold the kernels to it bit for bit.
+ * What the calls change is the memory traffic: the pattern (colidx) is read once for all heads, and a gathered row is one piece of
+ * H D floats (8 heads of 8 features: one 256-byte row instead of eight 32-byte slices).
+ *
+ * gnnx_spmm_csr_heads_f32 -- the aggregation with one value per entry AND head:
+ *   Y[i, h D + j] = beta * Y[i, h D + j] + ( sum_{p in row i, DESCENDING column} vals[p * ldv + h] * X[c_p, h D + j] ) + bias[h D + j]
+ *   then where(Y > 0, Y, 0) with relu_out != 0.  The product is rounded, then the add; after the row the bias, then beta (0 or 1), then
+ *   the ReLU -- the epilogue order of gnnx_spmm_csr_fused_f32.  There is no colscale / rowscale.  bias: [H D] or NULL.  X: [n_cols, H D]
+ *   ld ldx.  Y: [n_rows, H D] ld ldy; columns of Y beyond H D are not touched.  X and Y must not alias.  Any head_dim >= 1 and n_heads >= 1.
+ *   head_dim % 4 == 0 with 16-byte aligned rows (X, Y, bias, ldx, ldy) takes one 16-byte load per lane, the lane's head being f0 / head_dim;
+ *   everything else (a 4-float piece that would straddle two heads, e.g. D = 6; unaligned pointers or leading dimensions) takes scalar
+ *   lanes with the same bits.  head_dim == 1 over a matrix of ones is the per-head row sum of vals (the gradient of the softmax's column
+ *   term on the transposed pattern).  There is NO PLAN: a row is one lane group's chain of adds, a hub row included (DESIGN.md 5.3:
+ *   4.8 ms on R-MAT 1 M / 10 M whose longest row has 26 763 entries, whatever the width).  The CSR is trusted as in gnnx_spmm_csr_f32.
+ *
+ * gnnx_sddmm_csr_heads_f32 -- a score per entry and head:
+ *   out[p * ldo + h] = <L[i, h D .. h D + D - 1], R[c_p, h D .. h D + D - 1]>      in the SDDMM order for F = head_dim; no scales.
+ *   Work is dealt in the non-zero domain (a hub row spreads over the device); colidx and both rows are read once per entry for all
+ *   heads.  L == R is allowed; out aliases nothing.  nnz == 0 is GNNX_OK with no launch.  Second use: dL/dvals of the heads aggregation
+ *   is gnnx_sddmm_csr_heads_f32(L = G, R = X).
+ *
+ * gnnx_edge_softmax_csr_heads_f32 / gnnx_edge_softmax_bwd_csr_heads_f32 -- the edge softmax per head: scores [nnz, H] ld lds, out ld ldo,
+ *   alpha / dalpha / dt ld lda / ldd / ldt.  Term operand h is rowterm[i * rowterm_stride + h] / colterm[c * colterm_stride + h], strides
+ *   >= n_heads: the two halves of one [N, 2H] matrix serve as the two terms.  rowmax / rowsum are [n_rows, H] contiguous;
+ *   drowterm[i * drowterm_stride + h] (stride >= n_heads) lets the row term's gradient land in the left half of an [N, 2H] buffer.  The
+ *   segment rule and everything else of the single-head contract hold per head; the workspace of gnnx_edge_softmax_heads_workspace
+ *   serves either call.  n_heads == 1 with unit leading dimensions IS the single-head call.
+ *
+ * gnnx_csr_rowsum_heads_f32 -- out[i * ldo + h] = the sum of vals[p * ldv + h] over the entries p of row i, ONE accumulator from +0 in
+ *   ASCENDING p: column h carries the bits of gnnx_csr_rowsum_f32 on column h of vals (the reference's functional::sum walks up, where the
+ *   aggregation walks down: the two orders differ in the last bit).  It is the gradient of the softmax's column term on the transposed
+ *   pattern -- out the right half of the [N, 2H] gradient buffer.  An empty row writes +0.
+ *
+ * All entries: null pointers, negative sizes, n_heads < 1, head_dim < 1, a leading dimension or stride below its minimum and
+ * nnz >= 2^31 are GNNX_ERR_INVALID_ARG before any device call (p * ld + h is formed in 64 bits); a small workspace is GNNX_ERR_WORKSPACE;
+ * nnz == 0 still writes the per-row outputs.  Asynchronous on `stream`; nothing is allocated or synchronised; no atomics on any value.
+ */
+int gnnx_spmm_csr_heads_f32(int32_t n_rows, int32_t n_cols, int32_t n_heads, int32_t head_dim, const int32_t *d_rowptr,
+                            const int32_t *d_colidx, const float *d_vals, int64_t ldv, const float *d_bias, const float *d_X, int64_t ldx,
+                            float beta, int relu_out, float *d_Y, int64_t ldy, void *stream);
+int gnnx_sddmm_csr_heads_f32(int32_t n_rows, int32_t n_cols, int32_t n_heads, int32_t head_dim, int64_t nnz, const int32_t *d_rowptr,
+                             const int32_t *d_colidx, const float *d_L, int64_t ldl, const float *d_R, int64_t ldr, float *d_out, int64_t ldo,
+                             void *stream);
+int gnnx_csr_rowsum_heads_f32(const int32_t *d_rowptr, const float *d_vals, int64_t ldv, int32_t n_rows, int32_t n_heads, float *d_out,
+                              int64_t ldo, void *stream);
+int gnnx_edge_softmax_heads_workspace(int32_t n_rows, int64_t nnz, int32_t n_heads, size_t *bytes);
+int gnnx_edge_softmax_csr_heads_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                    int32_t n_heads, const float *d_scores, int64_t lds, const float *d_rowterm, int64_t rowterm_stride,
+                                    const float *d_colterm, int64_t colterm_stride, float negative_slope, uint32_t flags, float *d_out,
+                                    int64_t ldo, float *d_rowmax, float *d_rowsum, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_edge_softmax_bwd_csr_heads_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                        int32_t n_heads, const float *d_scores, int64_t lds, const float *d_rowterm, int64_t rowterm_stride,
+                                        const float *d_colterm, int64_t colterm_stride, float negative_slope, const float *d_alpha,
+                                        int64_t lda, const float *d_dalpha, int64_t ldd, float *d_dt, int64_t ldt, float *d_drowterm,
+                                        int64_t drowterm_stride, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */

@@ -15,6 +15,11 @@ The graph is NOT relabelled (CsrGraph.attention_map needs ascending rows), so th
 scrambled-order number.  Without --config the script is a driver: it runs every configuration as a child process of its own under a
 time limit and stops at the first one that fails.  --trace N: no timing, N calls of the softmax forward and backward in a row (run
 under `rocprofv3 --kernel-trace --stats -- python scripts/bench_gat_step.py --config rmat1m --trace 5` for the kernel times).
+
+--heads (with --config rmat1m; the driver passes it on): the multi-head calls instead.  For (H, D) = (8, 8), (8, 16), (4, 32), (8, 32) one
+JSON line each with ops.spmm_heads, ops.sddmm_heads, ops.edge_softmax_heads and ops.edge_softmax_heads_bwd against the loop of H
+single-head calls on column slabs (the aggregation planned, as a user of the single-head call would run it; the softmax on contiguous
+per-head copies, the copies in and out timed with it), then one line with a train_step of GatStack([128, 64, 16], heads=[8, 1]).
 """
 import argparse
 import ctypes as C
@@ -35,6 +40,8 @@ CONFIGS = {"rmat1m": dict(nodes=1_000_000, edges=10_000_000, feat=128, step=True
 def driver(args):
     for name in args.configs.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--repeats", str(args.repeats), "--warmup", str(args.warmup)]
+        if args.heads:
+            cmd.append("--heads")
         try:
             r = subprocess.run(cmd, timeout=CONFIGS[name]["limit"])
         except subprocess.TimeoutExpired:
@@ -76,6 +83,8 @@ def measure(args):
     src, dst = ops.rmat_edges(args.seed, n, e, 0.57, 0.19, 0.19, device=dev)
     g = ops.CsrGraph.from_coo(src, dst, n)
     g.make_plans(args.chunk, F)
+    if args.heads:
+        return measure_heads(args, torch, ops, capi, g, timed)
     map_t = g.attention_map()
     deg = (g.rowptr[1:] - g.rowptr[:-1])
     H = ops.uniform_pm1(args.seed + 1, (n, F), device=dev)
@@ -133,6 +142,72 @@ def measure(args):
     return 0
 
 
+HEAD_CELLS = ((8, 8), (8, 16), (4, 32), (8, 32))
+
+
+def measure_heads(args, torch, ops, capi, g, timed):
+    dev, n, nnz = g.rowptr.device, g.n, g.nnz
+    deg = g.rowptr[1:] - g.rowptr[:-1]
+    med = lambda fn: round(statistics.median(timed(fn)), 4)   # noqa: E731
+    for Hh, D in HEAD_CELLS:
+        F = Hh * D
+        H = ops.uniform_pm1(args.seed + 1, (n, F), device=dev)
+        G = ops.uniform_pm1(args.seed + 2, (n, F), device=dev)
+        ER = ops.uniform_pm1(args.seed + 3, (n, 2 * Hh), device=dev)
+        dalpha = ops.uniform_pm1(args.seed + 5, (nnz, Hh), device=dev)
+        alpha = ops.edge_softmax_heads(g.rowptr, g.colidx, Hh, rowterm=ER[:, :Hh], colterm=ER[:, Hh:], negative_slope=0.2)
+        Y = torch.empty((n, F), dtype=torch.float32, device=dev)
+        scores = torch.empty((nnz, Hh), dtype=torch.float32, device=dev)
+        cols = [alpha[:, h].contiguous() for h in range(Hh)]          # the loops' per-head operands, made outside the timed calls
+        outs = [torch.empty(nnz, dtype=torch.float32, device=dev) for _ in range(Hh)]
+        one = torch.empty(nnz, dtype=torch.float32, device=dev)
+        drow = torch.empty((n, Hh), dtype=torch.float32, device=dev)
+
+        def agg_loop():
+            for h in range(Hh):
+                ops.spmm(g.rowptr, g.colidx, H[:, h * D:(h + 1) * D], out=Y[:, h * D:(h + 1) * D], vals=cols[h], plan=g.plan)
+
+        def sddmm_loop():
+            for h in range(Hh):
+                ops.sddmm(g.rowptr, g.colidx, G[:, h * D:(h + 1) * D], H[:, h * D:(h + 1) * D], out=outs[h])
+
+        def softmax_fwd_loop():   # the terms are strided views already; the entry-major result needs a copy per head
+            for h in range(Hh):
+                scores[:, h].copy_(ops.edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, h], colterm=ER[:, Hh + h], negative_slope=0.2))
+
+        def softmax_bwd_loop():   # contiguous copies of alpha and dalpha in, dt out
+            for h in range(Hh):
+                one.copy_(alpha[:, h])
+                dt, dr = ops.edge_softmax_bwd(g.rowptr, g.colidx, one, dalpha[:, h].contiguous(), rowterm=ER[:, h], colterm=ER[:, Hh + h],
+                                              negative_slope=0.2)
+                scores[:, h].copy_(dt)
+                drow[:, h].copy_(dr)
+
+        out = {"config": args.config, "heads": Hh, "head_dim": D, "nnz": nnz, "max_degree": int(deg.max()), "ms_median": {
+            "spmm_heads": med(lambda: ops.spmm_heads(g.rowptr, g.colidx, H, alpha, Hh, out=Y)),
+            "spmm_loop_planned": med(agg_loop),
+            "sddmm_heads": med(lambda: ops.sddmm_heads(g.rowptr, g.colidx, G, H, Hh, out=scores)),
+            "sddmm_loop": med(sddmm_loop),
+            "edge_softmax_heads_fwd": med(lambda: ops.edge_softmax_heads(g.rowptr, g.colidx, Hh, rowterm=ER[:, :Hh], colterm=ER[:, Hh:],
+                                                                         negative_slope=0.2, out=scores)),
+            "edge_softmax_fwd_loop_with_copies": med(softmax_fwd_loop),
+            "edge_softmax_heads_bwd": med(lambda: ops.edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, rowterm=ER[:, :Hh],
+                                                                             colterm=ER[:, Hh:], negative_slope=0.2, drowterm_out=drow)),
+            "edge_softmax_bwd_loop_with_copies": med(softmax_bwd_loop),
+        }, "repeats": args.repeats, "warmup": args.warmup, "device": capi.device_name(0)}
+        print(json.dumps(out), flush=True)
+        del H, G, ER, dalpha, alpha, Y, scores, cols, outs, one, drow
+    dims, heads = [128, 64, 16], [8, 1]
+    net = ops.GatStack(g, dims, seed=args.seed + 100, device=dev, heads=heads)
+    X = ops.uniform_pm1(args.seed + 6, (n, dims[0]), device=dev)
+    target = (torch.arange(n, device=dev) % dims[-1]).to(torch.int32)
+    rows = torch.arange(0, n, 10, device=dev, dtype=torch.int32)
+    t = timed(lambda: net.train_step(X, target, rows, 0.0))
+    print(json.dumps({"config": args.config, "gat_dims": dims, "gat_heads": heads, "train_step_ms": [round(x, 4) for x in t],
+                      "train_step_ms_median": round(statistics.median(t), 4)}), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None, help="measure this configuration in this process")
@@ -142,6 +217,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=1024)
     ap.add_argument("--trace", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--heads", action="store_true", help="measure the multi-head calls against the loops of single-head calls")
     args = ap.parse_args()
     return measure(args) if args.config else driver(args)
 
