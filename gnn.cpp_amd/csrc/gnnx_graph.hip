@@ -311,7 +311,10 @@ __global__ void tail_flags_weighted_kernel(const uint64_t *keys, const int32_t *
     if (keep && (flags & GNNX_CSR_DROP_TRUNCATED_ZERO)) {
         const int32_t e = idx[i];
         const float v = e < n_edges ? w[e] : diag_value;
-        keep = (int)v != 0;  // adj_to_edge_list: `if (int(data[i]) != 0)` (graph.cpp:54) -- |w| < 1 vanishes
+        // adj_to_edge_list: `if (int(data[i]) != 0)` (graph.cpp:54) -- dropped iff -1 < w < 1.  Written as two compares, not as the
+        // cast: the cast is undefined for NaN, +-inf and |w| >= 2^31, and for NaN the device's conversion gives 0 (the entry would
+        // vanish) where the host's gives INT_MIN (it stays).  For every other value the two forms agree.
+        keep = !(v > -1.f && v < 1.f);
     }
     flag[i] = keep ? 1 : 0;
 }

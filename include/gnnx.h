@@ -118,9 +118,12 @@ int gnnx_equal_i32(const int32_t *d_a, const int32_t *d_b, int64_t n, int *equal
  *   GNNX_DIAG_KEEP   self loops stay as given                         (edge_to_adj_mat alone)
  *   GNNX_DIAG_STRIP  self loops are removed                           (add_self_loops(..., fillValue 0), graph.cpp:72)
  *   GNNX_DIAG_FILL   every (i, i) becomes diag_value, given or not    (add_self_loops(..., fillValue v))
- * flags: GNNX_CSR_KEEP_DUPLICATES as above; GNNX_CSR_DROP_TRUNCATED_ZERO drops entries whose value truncates to the integer
- * 0 -- adj_to_edge_list's `int(data[i]) != 0` test (graph.cpp:54), through which |w| < 1 vanishes on the
- * add_self_loops round trip; without it explicit zeros stay as entries (they add +-0 in a product, like the dense matrix).
+ * flags: GNNX_CSR_KEEP_DUPLICATES keeps every entry of a run of equal (r, c) pairs, in list order, each with its own weight;
+ * GNNX_CSR_DROP_TRUNCATED_ZERO drops entries whose value truncates to the integer 0 -- adj_to_edge_list's `int(data[i]) != 0` test
+ * (graph.cpp:54), through which |w| < 1 vanishes on the add_self_loops round trip.  The contract: an entry is dropped iff
+ * -1 < w < 1; NaN, +-inf and every |w| >= 1 stay (the test is two compares, never a float-to-int cast, so host and device agree on
+ * every value).  It applies to the entry that survived its run -- a pair whose LAST weight is dropped vanishes entirely -- and to
+ * diag_value.  Without the flag explicit zeros stay as entries (they add +-0 in a product, like the dense matrix).
  * Output: rowptr[N+1], colidx[nnz], vals[nnz] sorted by (row, column); capacity n_edges (+ n_nodes with GNNX_DIAG_FILL). */
 enum { GNNX_DIAG_KEEP = 0, GNNX_DIAG_STRIP = 1, GNNX_DIAG_FILL = 2 };
 #define GNNX_CSR_DROP_TRUNCATED_ZERO 4u

@@ -86,7 +86,8 @@ API int64_t gcn_oracle_coo_to_csr(const int32_t *src, const int32_t *dst, int64_
  * wins; add_self_loops (graph.cpp:68-75) then overwrites the diagonal with fillValue and adj_to_edge_list (graph.cpp:46-67)
  * scans row-major keeping entries with int(value) != 0.
  *   diag_mode 0: diagonal as given; 1: diagonal removed; 2: every (i,i) = diag_value.
- *   drop_truncated_zero: apply adj_to_edge_list's int() filter (otherwise explicit zeros are kept as entries).
+ *   drop_truncated_zero: apply adj_to_edge_list's int() filter, i.e. drop an entry iff -1 < value < 1 (otherwise explicit zeros are
+ *   kept as entries).
  * Capacity of colidx / vals: E + N.  Returns nnz or -1 on an out-of-range index. */
 typedef struct { uint64_t key; int64_t pos; } key_pos_t;
 static int cmp_key_pos(const void *a, const void *b)
@@ -122,7 +123,7 @@ API int64_t gcn_oracle_coo_to_csr_weighted(const int32_t *src, const int32_t *ds
     for (int64_t i = 0; i < m; i++) {
         if (i + 1 < m && kp[i + 1].key == kp[i].key) continue; /* a later assignment overwrites this one */
         float v = kp[i].pos < E ? w[kp[i].pos] : diag_value;
-        if (drop_truncated_zero && (int)v == 0) continue;
+        if (drop_truncated_zero && v > -1.0f && v < 1.0f) continue; /* (int)v == 0 without the cast: defined for NaN, +-inf, |v| >= 2^31 (all kept) */
         colidx[nnz] = (int32_t)(kp[i].key & 0xffffffffu);
         vals[nnz] = v;
         nnz++;
