@@ -15,8 +15,6 @@ namespace {
 
 constexpr int kMaxBlocks = 2048;  // 256 CUs x 8 blocks/CU
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // ---- colsum: stage 1 -- each workgroup reduces a contiguous slab of rows to one partial row ---------
 // Vector form (F % 4 == 0, 16-B aligned): a row is covered by L = F/4 lanes (16 B each, coalesced); the 256
 // threads form 256/L row groups that walk the slab interleaved, 4 rows in flight per thread; the groups'

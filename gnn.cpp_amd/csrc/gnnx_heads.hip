@@ -11,15 +11,13 @@
 //     requested before the first is added.  A row is ONE lane group's chain whatever its length (no plan).
 //   scores: work is dealt in the non-zero domain as in gnnx_sddmm.hip; GE lanes per entry hold HP = GE / G heads of G lanes each, a
 //     pattern with more heads than that takes several passes over the same entry.
-#include "gnnx_common.h"
+#include "gnnx_edge_dot.h"
 
 #pragma clang fp contract(off)
 
 using namespace gnnx;
 
 namespace {
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---- aggregation ---------------------------------------------------------------------------------------------------------------
 struct AggArgs {
@@ -132,59 +130,7 @@ __global__ __launch_bounds__(256) void rowsum_heads_kernel(const int32_t *__rest
     out[row * ldo + h] = acc;
 }
 
-// ---- scores --------------------------------------------------------------------------------------------------------------------
-constexpr int kEntriesPerGroup = 32;   // consecutive entries of one lane group (a multiple of kInFlight)
-constexpr int kInFlight = 4;           // R pieces requested before the first is consumed (fast path)
-
-// the smallest row r with rowptr[r + 1] > p (p < rowptr[n_rows]): the row that stores entry p, empty rows skipped
-__device__ __forceinline__ int32_t row_of_entry(const int32_t *rowptr, int32_t n_rows, int64_t p)
-{
-    int32_t lo = 0, hi = n_rows - 1;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)rowptr[mid + 1] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// features 4 q .. 4 q + 3 of a head's slab of D features (zero behind the slab's end; the consumer never adds those)
-template <bool VEC>
-__device__ __forceinline__ float4 load_chunk(const float *slab, int32_t q, int32_t D)
-{
-    if constexpr (VEC) {
-        return *reinterpret_cast<const float4 *>(slab + 4 * (int64_t)q);
-    } else {
-        const int32_t f = 4 * q;
-        float4 v;
-        v.x = slab[f];                     // q < Q: the chunk's first feature exists
-        v.y = f + 1 < D ? slab[f + 1] : 0.f;
-        v.z = f + 2 < D ? slab[f + 2] : 0.f;
-        v.w = f + 3 < D ? slab[f + 3] : 0.f;
-        return v;
-    }
-}
-
-// acc = acc + (l * r) over the chunk's features in ascending f: the product is rounded, then the sum
-template <bool VEC>
-__device__ __forceinline__ float add_chunk(float acc, const float4 &l, const float4 &r, int32_t q, int32_t D)
-{
-    const int32_t f = 4 * q;
-    acc = acc + (l.x * r.x);
-    if (VEC || f + 1 < D) acc = acc + (l.y * r.y);
-    if (VEC || f + 2 < D) acc = acc + (l.z * r.z);
-    if (VEC || f + 3 < D) acc = acc + (l.w * r.w);
-    return acc;
-}
-
-template <int G>
-__device__ __forceinline__ float butterfly(float acc)
-{
-#pragma unroll
-    for (int s = 1; s < G; s <<= 1) acc = acc + __shfl_xor(acc, s, 64);   // partners stay inside the aligned group of G lanes
-    return acc;
-}
-
+// ---- scores (the dot product's steps: gnnx_edge_dot.h, with F := D on a head's slab) --------------------------------------------
 struct ScoreArgs {
     int32_t n_rows, H, D;
     int64_t nnz;

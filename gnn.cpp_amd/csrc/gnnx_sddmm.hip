@@ -1,16 +1,14 @@
 // Edge scores on a CSR pattern (SDDMM) and the position map between CSR(A) and CSR(A^T) -- include/gnnx.h "edge scores".
 //   out[p] = (<L[i,:], R[c_p,:]> * rowscale[i]) * colscale[c_p]      for entry p of row i
-// The dot product's ORDER is part of the contract and a function of F alone (the header states it): Q = ceil(F / 4) chunks of four
-// features, a lane group of G = min(64, pow2 >= Q) lanes, lane l owns chunks l, l + G, ... and adds their products in ascending f
-// to ONE accumulator; the G accumulators meet in an xor butterfly (s = 1, 2, .., G / 2).  That is a vec4 lane group: F = 256 is a
-// wavefront per entry with one 16-byte load per lane, F = 128 two entries per wavefront.  Rows that fail the vec4 conditions take
-// scalar loads with the same feature-to-lane assignment: same bits.
+// The dot product's ORDER is part of the contract and a function of F alone: gnnx_edge_dot.h states it and holds its steps.  It is a
+// vec4 lane group: F = 256 is a wavefront per entry with one 16-byte load per lane, F = 128 two entries per wavefront.  Rows that fail
+// the vec4 conditions take scalar loads with the same feature-to-lane assignment: same bits.
 //
 // Work is dealt in the NON-ZERO domain: a lane group owns kEntriesPerGroup consecutive entries and finds
 // the row of its first one by a search in rowptr, so a hub row spreads over the device without a plan.  The L row stays in
 // registers until the row changes; the R rows of four entries are requested before the first of them is used (4 rows in flight
 // per lane group, 16 wavefronts per CU: the gather shape of the aggregation).  The butterfly is register shuffles; no LDS.
-#include "gnnx_common.h"
+#include "gnnx_edge_dot.h"
 
 #pragma clang fp contract(off)
 
@@ -18,67 +16,7 @@ using namespace gnnx;
 
 namespace {
 
-constexpr int kEntriesPerGroup = 32;   // consecutive entries of one lane group (a multiple of kInFlight)
-constexpr int kInFlight = 4;           // R rows requested before the first is consumed
 constexpr int kMaxBlocks = 16384;      // grid cap of the one-thread-per-entry index kernels (grid stride)
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// the smallest row r with rowptr[r + 1] > p (p < rowptr[n_rows]): the row that stores entry p, empty rows skipped
-__device__ __forceinline__ int32_t row_of_entry(const int32_t *rowptr, int32_t n_rows, int64_t p)
-{
-    int32_t lo = 0, hi = n_rows - 1;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)rowptr[mid + 1] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// features 4 q .. 4 q + 3 of a row (zero behind the row's end; the consumer never adds those)
-template <bool VEC>
-__device__ __forceinline__ float4 load_chunk(const float *row, int32_t q, int32_t F)
-{
-    if constexpr (VEC) {
-        return *reinterpret_cast<const float4 *>(row + 4 * (int64_t)q);
-    } else {
-        const int32_t f = 4 * q;
-        float4 v;
-        v.x = row[f];                      // q < Q: the chunk's first feature exists
-        v.y = f + 1 < F ? row[f + 1] : 0.f;
-        v.z = f + 2 < F ? row[f + 2] : 0.f;
-        v.w = f + 3 < F ? row[f + 3] : 0.f;
-        return v;
-    }
-}
-
-// acc = acc + (l * r) over the chunk's features in ascending f: the product is rounded, then the sum
-template <bool VEC>
-__device__ __forceinline__ float add_chunk(float acc, const float4 &l, const float4 &r, int32_t q, int32_t F)
-{
-    if constexpr (VEC) {
-        acc = acc + (l.x * r.x);
-        acc = acc + (l.y * r.y);
-        acc = acc + (l.z * r.z);
-        acc = acc + (l.w * r.w);
-    } else {
-        const int32_t f = 4 * q;
-        acc = acc + (l.x * r.x);
-        if (f + 1 < F) acc = acc + (l.y * r.y);
-        if (f + 2 < F) acc = acc + (l.z * r.z);
-        if (f + 3 < F) acc = acc + (l.w * r.w);
-    }
-    return acc;
-}
-
-template <int G>
-__device__ __forceinline__ float butterfly(float acc)
-{
-#pragma unroll
-    for (int s = 1; s < G; s <<= 1) acc = acc + __shfl_xor(acc, s, 64);   // partners stay inside the aligned group of G lanes
-    return acc;
-}
 
 // G lanes per entry, CPL = ceil(Q / G) chunks per lane (1 unless G == 64), the L row's chunks in registers.
 template <int G, int CPL, bool VEC>

@@ -1444,14 +1444,23 @@ class GcnStack:
 
 
 class GatStack:
-    """L single-head graph-attention layers (GAT, Velickovic et al. 2018) on one graph, the surface of GcnStack:
+    """L graph-attention layers (GAT, Velickovic et al. 2018) on one graph, the surface of GcnStack.  Layer l has heads[l] heads of width
+    D = dims[l+1] / heads[l]; per head
         H = h W^T;   el = H a_l,  er = H a_r;   alpha_ic = softmax over the stored entries c of row i of leaky_relu(el_i + er_c);
-        h' = act( sum_c alpha_ic H_c + b ),  ReLU between layers, none after the last.
-    Row i attends over its STORED columns -- the direction of the project's aggregation.  forward / backward / step / train_step /
-    evaluate; every operation is a C-ABI call: the dense products (the two attention vectors ride as one [2, d] matrix A = [a_l; a_r],
-    so el and er are the columns of ER = H A^T), edge_softmax, the aggregation with vals = alpha, its value gradient (spmm_vals_grad),
-    edge_softmax_bwd, and the transposed pattern with g.attention_map() for everything that flows back to a column's vertex.  No
-    atomics; the same bits every run.
+        h' = act( sum_c alpha_ic H_c + b ),  ReLU between layers, none after the last,
+    and the layer's output is the concatenation of its heads (the usual last layer is one head; head averaging and attention dropout are
+    not implemented).  heads=None means one head in every layer.  Row i attends over its STORED columns -- the direction of the
+    project's aggregation.  forward / backward / step / train_step / evaluate; every operation is a C-ABI call.  No atomics; the same
+    bits every run.
+
+    There is ONE layer path.  The attention vectors ride as one [2 Hh, Hh D] matrix A that is zero outside its blocks (row h: a_l of head
+    h in the head's columns, row Hh + h: a_r; for one head the plain [2, d] matrix [a_l; a_r]), so ER = H A^T is [n, 2 Hh] with el in the
+    left half and er in the right, and the backward's two products with dER = [del der] work for any number of heads; dA is masked to
+    the blocks (A_mask).  The softmax and the row sums are the multi-head calls (edge_softmax_heads, edge_softmax_heads_bwd,
+    csr_rowsum_heads), which write both halves of dER in place; everything that flows back to a column's vertex goes through the
+    transposed pattern with g.attention_map().  Only two steps ask how many heads a layer has (_aggregate, _vals_grad): a one-head layer
+    keeps the planned aggregation (spmm with g.plan / g.plan_t: a hub row is split) and the prefetching edge
+    scores (spmm_vals_grad), a layer of several heads reads the pattern once for all of them (spmm_heads, sddmm_heads).
 
     The stack takes any CsrGraph that has a transposed CSR and is not relabelled.  CsrGraph.from_coo strips the diagonal; the paper's
     self attention wants every vertex in its own row, a pattern with the whole diagonal:
@@ -1459,14 +1468,7 @@ class GatStack:
         rp, ci, _ = csr_from_coo_weighted(src, dst, w, n, DIAG_FILL)          # the values are discarded
         rp_t, ci_t, _ = csr_from_coo_weighted(dst, src, w, n, DIAG_FILL)
         g = CsrGraph(n, rp, ci, rp_t, ci_t)                                   # g.make_plans(...) for a power-law graph
-    A vertex without entries (only possible without the diagonal) has an empty softmax: its row is the bias alone.
-
-    heads=[h_0 .. h_{L-1}] makes layer l a multi-head layer of h_l heads of width D = dims[l+1] / h_l whose output is the concatenation
-    of the heads (the usual last layer is one head; head averaging and attention dropout are not implemented).  The layer runs on the
-    multi-head calls -- edge_softmax_heads, spmm_heads, sddmm_heads, csr_rowsum_heads -- which read the pattern once for all heads; the
-    attention vectors ride as one [2 h_l, dims[l+1]] matrix A that is zero outside its blocks (row h: a_l of head h in the head's columns,
-    row h_l + h: a_r), so ER = H A^T is [n, 2 h_l] and the two products of the backward work as for one head; dA is masked to the blocks.
-    heads=None is the single-head path above; heads=[1, .., 1] gives its bits."""
+    A vertex without entries (only possible without the diagonal) has an empty softmax: its row is the bias alone."""
 
     def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda", heads=None):
         self.g = g
@@ -1474,33 +1476,28 @@ class GatStack:
         self.negative_slope = float(negative_slope)
         self.map_t = g.attention_map()
         L = len(dims) - 1
-        self.heads = None
-        if heads is not None:
-            heads = list(heads)
-            if len(heads) != L or any(int(k) != k or k < 1 for k in heads):
-                raise ValueError(f"heads must list {L} positive integers, one per layer, got {heads}")
-            bad = [l for l in range(L) if dims[l + 1] % heads[l]]
-            if bad:
-                raise ValueError(f"layer {bad[0]}: {dims[bad[0] + 1]} features do not split into {heads[bad[0]]} heads")
-            self.heads = [int(k) for k in heads]
+        heads = [1] * L if heads is None else list(heads)
+        if len(heads) != L or any(int(k) != k or k < 1 for k in heads):
+            raise ValueError(f"heads must list {L} positive integers, one per layer, got {heads}")
+        bad = [l for l in range(L) if dims[l + 1] % heads[l]]
+        if bad:
+            raise ValueError(f"layer {bad[0]}: {dims[bad[0] + 1]} features do not split into {heads[bad[0]]} heads")
+        self.heads = [int(k) for k in heads]
         self.W = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.A = [uniform_pm1(seed + 2 * l + 1, (2, dims[l + 1]), scale=dims[l + 1] ** -0.5, device=device) for l in range(L)]   # [a_l; a_r]
+        self.A, self.A_mask = [], []
+        for l, Hh in enumerate(self.heads):   # [a_l; a_r] drawn as one [2, dims[l+1]] matrix, laid out in the blocks of the [2 Hh, Hh D] one
+            D = dims[l + 1] // Hh
+            block = torch.kron(torch.eye(Hh, dtype=torch.float32, device=device), torch.ones((1, D), dtype=torch.float32, device=device))
+            mask = torch.cat([block, block]).contiguous()
+            draw = uniform_pm1(seed + 2 * l + 1, (2, dims[l + 1]), scale=D ** -0.5, device=device)
+            self.A.append((torch.cat([draw[0:1].expand(Hh, -1), draw[1:2].expand(Hh, -1)]) * mask).contiguous())
+            self.A_mask.append(mask)
         self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
         self.dW = [torch.zeros_like(w) for w in self.W]
         self.dA = [torch.zeros_like(a) for a in self.A]
         self.db = [torch.zeros_like(b) for b in self.b]
         self._saved = None
         self._buf = {}
-        if self.heads is not None:   # [a_l; a_r] of every head drawn as before, then laid out in the blocks of the [2 Hh, Hh D] matrix
-            self.A_mask = []
-            for l, Hh in enumerate(self.heads):
-                D = dims[l + 1] // Hh
-                block = torch.kron(torch.eye(Hh, dtype=torch.float32, device=device), torch.ones((1, D), dtype=torch.float32, device=device))
-                mask = torch.cat([block, block]).contiguous()                                   # [2 Hh, Hh D]
-                draw = uniform_pm1(seed + 2 * l + 1, (2, dims[l + 1]), scale=D ** -0.5, device=device)
-                self.A[l] = (torch.cat([draw[0:1].expand(Hh, -1), draw[1:2].expand(Hh, -1)]) * mask).contiguous()
-                self.dA[l] = torch.zeros_like(self.A[l])
-                self.A_mask.append(mask)
 
     def _tmp(self, key, shape, device, zero=False):
         t = self._buf.get(key)
@@ -1513,41 +1510,44 @@ class GatStack:
         return self._tmp("G", (self.g.n, self.dims[-1]), self.W[0].device)
 
     def attention(self, H, l):
-        """(ER, alpha) of layer l from H = h W_l^T: ER = H [a_l; a_r]^T as [n, 2], alpha = edge_softmax(rowterm = ER[:, 0], colterm = ER[:, 1])."""
-        g = self.g
-        ER = gemm(H, self.A[l], transB=True)
-        alpha = edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=self.negative_slope)
-        return ER, alpha
-
-    def attention_heads(self, H, l):
-        """(ER, alpha) of the multi-head layer l: ER = H A^T as [n, 2 Hh] (el of head h in column h, er in column Hh + h), alpha entry-major
+        """(ER, alpha) of layer l from H = h W_l^T: ER = H A^T as [n, 2 Hh] (el of head h in column h, er in column Hh + h), alpha entry-major
         [nnz, Hh] = edge_softmax_heads(rowterm = ER[:, :Hh], colterm = ER[:, Hh:])."""
         g, Hh = self.g, self.heads[l]
         ER = gemm(H, self.A[l], transB=True)
         alpha = edge_softmax_heads(g.rowptr, g.colidx, Hh, rowterm=ER[:, :Hh], colterm=ER[:, Hh:], negative_slope=self.negative_slope)
         return ER, alpha
 
+    def _aggregate(self, l, X, vals, transposed=False, **epilogue):
+        """sum_p vals[p, h] * X[c_p, slab h] over the rows of the pattern (of the transposed pattern: vals in its order).  One head: the
+        planned kernel, which splits hub rows; several: spmm_heads, which has no plan."""
+        g = self.g
+        rowptr, colidx, plan = (g.rowptr_t, g.colidx_t, g.plan_t) if transposed else (g.rowptr, g.colidx, g.plan)
+        if self.heads[l] == 1:
+            return spmm(rowptr, colidx, X, vals=vals.reshape(-1), plan=plan, **epilogue)
+        return spmm_heads(rowptr, colidx, X, vals, self.heads[l], **epilogue)
+
+    def _vals_grad(self, l, G, H):
+        """dL/dalpha [nnz, Hh], the aggregation's value gradient.  One head: sddmm, which prefetches the next batch of columns."""
+        g = self.g
+        if self.heads[l] == 1:
+            return spmm_vals_grad(g.rowptr, g.colidx, G, H).reshape(-1, 1)
+        return sddmm_heads(g.rowptr, g.colidx, G, H, self.heads[l])
+
     def forward(self, X):
-        g, L = self.g, len(self.W)
+        L = len(self.W)
         saved, h = [], X
         for l in range(L):
             H = linear_fwd(h, self.W[l])
-            if self.heads is not None:
-                ER, alpha = self.attention_heads(H, l)
-                Y = spmm_heads(g.rowptr, g.colidx, H, alpha, self.heads[l], bias=self.b[l], relu_out=l + 1 < L)
-                saved.append((h, H, ER, alpha, Y))
-                h = Y
-                continue
             ER, alpha = self.attention(H, l)
             # the ReLU between layers rides in the aggregation's epilogue: only relu(Z) is stored (its sign is the mask)
-            Y = spmm(g.rowptr, g.colidx, H, vals=alpha, bias=self.b[l], plan=g.plan, relu_out=l + 1 < L)
+            Y = self._aggregate(l, H, alpha, bias=self.b[l], relu_out=l + 1 < L)
             saved.append((h, H, ER, alpha, Y))
             h = Y
         self._saved = saved
         return h
 
     def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
-        """dW, dA ([da_l; da_r]) and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        """dW, dA (masked to its blocks) and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         g, L, n = self.g, len(self.W), self.g.n
         G = dOut
@@ -1555,50 +1555,26 @@ class GatStack:
             colsum(G, out=self.db[L - 1])
         for l in reversed(range(L)):
             h, H, ER, alpha, _ = self._saved[l]
-            dev = G.device
-            if self.heads is not None:
-                dH = self._backward_heads(l, G, H, ER, alpha)
-                gemm(dH, h, transA=True, out=self.dW[l])
-                if l == 0:
-                    G = gemm(dH, self.W[l]) if input_grad else None
-                else:
-                    G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
-                continue
-            dalpha = spmm_vals_grad(g.rowptr, g.colidx, G, H)
-            dER_t = self._tmp("dER_t", (2, n), dev)                                   # row 0: del, row 1: der
-            dt, _ = edge_softmax_bwd(g.rowptr, g.colidx, alpha, dalpha, rowterm=ER[:, 0], colterm=ER[:, 1],
-                                     negative_slope=self.negative_slope, drowterm_out=dER_t[0])
-            vals_t = self._tmp("vals_t", (g.nnz,), dev)
+            Hh, dev = self.heads[l], G.device
+            dalpha = self._vals_grad(l, G, H)
+            dER = self._tmp(("dER", Hh), (n, 2 * Hh), dev)                                # left half: del, right half: der
+            dt, _ = edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, rowterm=ER[:, :Hh], colterm=ER[:, Hh:],
+                                           negative_slope=self.negative_slope, drowterm_out=dER[:, :Hh])
+            vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh), dev)
             self._to_transposed(dt, vals_t)
-            csr_rowsum(g.rowptr_t, vals_t, out=dER_t[1])                              # der: what flows back to a column's vertex
+            csr_rowsum_heads(g.rowptr_t, vals_t, out=dER[:, Hh:])                         # der: what flows back to a column's vertex
             self._to_transposed(alpha, vals_t)
-            dH = spmm(g.rowptr_t, g.colidx_t, G, vals=vals_t, plan=g.plan_t)          # through the aggregated rows
-            dER = transpose(dER_t, out=self._tmp("dER", (n, 2), dev))
-            gemm(dER, self.A[l], out=dH, beta=1.0)                                    # + [del der] . [a_l; a_r], through ER
+            dH = self._aggregate(l, G, vals_t, transposed=True)                           # through the aggregated rows
+            gemm(dER, self.A[l], out=dH, beta=1.0)                                        # + [del der] . A, through ER
             gemm(dER, H, transA=True, out=self.dA[l])
+            if Hh > 1:   # the entries outside the blocks are not parameters (one head: the mask is all ones)
+                binary("mul", self.dA[l], self.A_mask[l], out=self.dA[l])
             gemm(dH, h, transA=True, out=self.dW[l])
             if l == 0:
                 G = gemm(dH, self.W[l]) if input_grad else None
             else:   # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue
                 G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
         return G
-
-    def _backward_heads(self, l, G, H, ER, alpha):
-        """dH of the multi-head layer l from G = dL/dZ (Z the aggregated rows), and dA[l] (masked to its blocks)."""
-        g, n, Hh, dev = self.g, self.g.n, self.heads[l], G.device
-        dalpha = sddmm_heads(g.rowptr, g.colidx, G, H, Hh)                            # dL/dalpha: the aggregation's value gradient
-        dER = self._tmp(("dER", Hh), (n, 2 * Hh), dev)                                # left half: del, right half: der
-        dt, _ = edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, rowterm=ER[:, :Hh], colterm=ER[:, Hh:],
-                                       negative_slope=self.negative_slope, drowterm_out=dER[:, :Hh])
-        vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh), dev)
-        self._to_transposed(dt, vals_t)
-        csr_rowsum_heads(g.rowptr_t, vals_t, out=dER[:, Hh:])                         # der: what flows back to a column's vertex
-        self._to_transposed(alpha, vals_t)
-        dH = spmm_heads(g.rowptr_t, g.colidx_t, G, vals_t, Hh)                        # through the aggregated rows
-        gemm(dER, self.A[l], out=dH, beta=1.0)                                        # + [del der] . A, through ER
-        gemm(dER, H, transA=True, out=self.dA[l])
-        binary("mul", self.dA[l], self.A_mask[l], out=self.dA[l])                     # the entries outside the blocks are not parameters
-        return dH
 
     def _to_transposed(self, vals, out):
         if self.g.nnz:

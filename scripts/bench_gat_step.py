@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Measurement (GPU box): the edge softmax (ops.edge_softmax / ops.edge_softmax_bwd), the three skinny dense products of a
-graph-attention layer, and one GatStack.train_step, with the PLANNED FORWARD AGGREGATION and the edge-score kernel (ops.sddmm) on the
+"""Measurement (GPU box): the calls of a one-head GatStack layer -- the edge softmax and the transposed row sum through the multi-head
+wrappers with H = 1 (ops.edge_softmax_heads / ops.edge_softmax_heads_bwd / ops.csr_rowsum_heads, as the stack makes them), the three
+skinny dense products -- and one GatStack.train_step, with the PLANNED FORWARD AGGREGATION and the edge-score kernel (ops.sddmm) on the
 same CSR and width in the same process as yardsticks (each of those gathers nnz * 4 F bytes of rows; the softmax moves 12 - 20 bytes
 per entry).
 
@@ -96,16 +97,19 @@ def measure(args):
     scores = torch.empty(g.nnz, dtype=torch.float32, device=dev)
     ER = ops.gemm(H, A, transB=True)
     dER = ops.uniform_pm1(args.seed + 4, (n, 2), scale=1e-3, device=dev)
-    alpha = ops.edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2)
-    dalpha = ops.uniform_pm1(args.seed + 5, (g.nnz,), device=dev)
-    vals_t = torch.empty(g.nnz, dtype=torch.float32, device=dev)
+    alpha = ops.edge_softmax_heads(g.rowptr, g.colidx, 1, rowterm=ER[:, :1], colterm=ER[:, 1:], negative_slope=0.2)      # [nnz, 1]
+    dalpha = ops.uniform_pm1(args.seed + 5, (g.nnz, 1), device=dev)
+    vals_t = torch.empty((g.nnz, 1), dtype=torch.float32, device=dev)
+    d_er = torch.empty((n, 2), dtype=torch.float32, device=dev)   # the stack's dER: the softmax writes column 0, the row sum column 1
     kernels = {
-        "aggregation": lambda: ops.spmm(g.rowptr, g.colidx, H, out=Y, vals=alpha, plan=g.plan),
+        "aggregation": lambda: ops.spmm(g.rowptr, g.colidx, H, out=Y, vals=alpha.reshape(-1), plan=g.plan),
         "sddmm": lambda: ops.sddmm(g.rowptr, g.colidx, G, H, out=scores),
-        "edge_softmax_fwd": lambda: ops.edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2),
-        "edge_softmax_bwd": lambda: ops.edge_softmax_bwd(g.rowptr, g.colidx, alpha, dalpha, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2),
-        "to_transposed": lambda: ops.gather_rows(alpha.reshape(-1, 1), map_t, out=vals_t.reshape(-1, 1)),
-        "colterm_grad_rowsum": lambda: ops.csr_rowsum(g.rowptr_t, vals_t),
+        "edge_softmax_fwd": lambda: ops.edge_softmax_heads(g.rowptr, g.colidx, 1, rowterm=ER[:, :1], colterm=ER[:, 1:], negative_slope=0.2),
+        "edge_softmax_bwd": lambda: ops.edge_softmax_heads_bwd(g.rowptr, g.colidx, 1, alpha, dalpha, rowterm=ER[:, :1], colterm=ER[:, 1:],
+                                                               negative_slope=0.2, drowterm_out=d_er[:, :1]),
+        "to_transposed": lambda: ops.gather_rows(alpha, map_t, out=vals_t),
+        "csr_rowsum_heads": lambda: ops.csr_rowsum_heads(g.rowptr_t, vals_t, out=d_er[:, 1:]),
+        "csr_rowsum": lambda: ops.csr_rowsum(g.rowptr_t, vals_t.reshape(-1)),      # the single-head call on the same values: a yardstick
         "gemm_ER": lambda: ops.gemm(H, A, transB=True, out=ER),
         "gemm_dH_K2": lambda: ops.gemm(dER, A, out=dH, beta=1.0),
         "gemm_dA_transA": lambda: ops.gemm(dER, H, transA=True, out=dA),
@@ -128,7 +132,7 @@ def measure(args):
            "edge_softmax_bwd_model_TBps": round(model_bwd / med["edge_softmax_bwd"] / 1e9, 3),
            "repeats": args.repeats, "warmup": args.warmup, "device": capi.device_name(0)}
     if cfg["step"]:
-        del Y, dH, scores, G, dalpha, vals_t
+        del Y, dH, scores, G, dalpha, vals_t, d_er
         net = ops.GatStack(g, [F, F, F], seed=args.seed + 100, device=dev)
         X = ops.uniform_pm1(args.seed + 6, (n, F), device=dev)
         target = (torch.arange(n, device=dev) % F).to(torch.int32)

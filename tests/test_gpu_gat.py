@@ -2,7 +2,9 @@
 tests/test_gpu_link.py, once as CsrGraph.from_coo builds it (the diagonal stripped, isolated vertices: empty softmax rows) and once
 with the whole diagonal filled (the paper's self attention).
 
-Bars (none is new): bit equality of one layer against the chain of restatements -- alpha from the device's own ER and expf through
+Bars (none is new): bit equality of the one-head stack, forward and backward, against the chain of the public single-head calls it
+replaced, and the kernels each layer must run (the planned aggregation and sddmm for one head, the _heads calls for several);
+bit equality of one layer against the chain of restatements -- alpha from the device's own ER and expf through
 tests/edge_softmax_ref.py, then tests/spmm_ref.py with vals = alpha; one whole step against a float64 autograd model at the bounds of
 test_gpu_parity.py::test_two_layer_training_step_vs_float64 -- 1e-5 * max(1, |ref|) for the loss, 2e-5 * max(|ref|_max, 1e-3) for every
 parameter gradient; training goes down and repeats bit for bit."""
@@ -94,7 +96,7 @@ def test_one_layer_forward_bits(env, task):
     z = er.row_sum_in_order(x, rp)
     assert np.array_equal(host(z_d), z)
     alpha_ref = er.edge_softmax_from_x(x, z, rp)
-    assert np.array_equal(host(alpha), alpha_ref)
+    assert np.array_equal(host(alpha.reshape(-1)), alpha_ref)
     assert np.array_equal(host(Y), spmm_ref(rp, ci, host(H), vals=alpha_ref, bias=host(net.b[0])))
     if task["kind"] == "stripped":   # an isolated vertex: the bias alone
         iso = np.nonzero(np.diff(rp) == 0)[0]
@@ -161,6 +163,99 @@ def test_training_goes_down_and_repeats_bit_for_bit(env, task):
         assert torch.equal(p, q)
     loss, correct, count = make_net(env, task).evaluate(X, t, rows)
     assert count == len(task["rows"]) and 0 <= correct <= count and np.isfinite(host(loss)[0])
+
+
+def test_one_head_stack_equals_the_chain_of_single_head_calls_bit_for_bit(env, task, monkeypatch):
+    """GatStack(heads=None) runs its softmax and row sums on the multi-head calls with H = 1 and writes del / der straight into the
+    halves of dER.  Every layer, forward and backward, restated from its saved (h, H, ER, alpha, Y) out of the public single-head
+    wrappers (edge_softmax, the planned spmm, spmm_vals_grad, edge_softmax_bwd, csr_rowsum, the products) must give the same bits."""
+    torch, ops, g = env["torch"], env["ops"], task["g"]
+    for rowptr in (task["rowptr"], host(g.rowptr_t)):   # the planned kernel's split rows run in A and in A^T
+        assert np.diff(rowptr).max() > 64
+    assert g.plan is not None and g.plan_t is not None
+    handed_down = []
+    inner = ops.gemm_relu_colsum
+
+    def recording(*a, **kw):
+        out = inner(*a, **kw)
+        handed_down.append(out[0])
+        return out
+
+    net = make_net(env, task)
+    L = len(net.W)
+    dOut = dev(env, synth.uniform_pm1(97, (N, DIMS[-1])))
+    net.forward(dev(env, task["X"]))
+    monkeypatch.setattr(ops, "gemm_relu_colsum", recording)
+    dX = net.backward(dOut)
+    monkeypatch.setattr(ops, "gemm_relu_colsum", inner)
+    assert len(handed_down) == L - 1
+    map_t = net.map_t.long()
+    G = dOut
+    assert torch.equal(net.db[L - 1], ops.colsum(G))
+    for l in reversed(range(L)):
+        h, H, ER, alpha, Y = net._saved[l]
+        assert tuple(ER.shape) == (N, 2) and tuple(alpha.shape) == (g.nnz, 1)
+        a = ops.edge_softmax(g.rowptr, g.colidx, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2)
+        assert torch.equal(alpha.reshape(-1), a), f"alpha{l}"
+        assert torch.equal(Y, ops.spmm(g.rowptr, g.colidx, H, vals=a, bias=net.b[l], plan=g.plan, relu_out=l + 1 < L)), f"Y{l}"
+        dalpha = ops.spmm_vals_grad(g.rowptr, g.colidx, G, H)
+        dt, d_el = ops.edge_softmax_bwd(g.rowptr, g.colidx, a, dalpha, rowterm=ER[:, 0], colterm=ER[:, 1], negative_slope=0.2)
+        d_er = ops.csr_rowsum(g.rowptr_t, dt[map_t].contiguous())
+        dH = ops.spmm(g.rowptr_t, g.colidx_t, G, vals=a[map_t].contiguous(), plan=g.plan_t)
+        dER = torch.stack([d_el, d_er], dim=1).contiguous()
+        ops.gemm(dER, net.A[l], out=dH, beta=1.0)
+        assert torch.equal(net.dA[l], ops.gemm(dER, H, transA=True)), f"dA{l}"
+        assert torch.equal(net.dW[l], ops.gemm(dH, h, transA=True)), f"dW{l}"
+        if l == 0:
+            G = ops.gemm(dH, net.W[0])
+            assert torch.equal(dX, G), "dX"
+        else:
+            G, db = ops.gemm_relu_colsum(dH, net.W[l], h)
+            assert torch.equal(handed_down[L - 1 - l], G), f"G{l - 1}"
+            assert torch.equal(net.db[l - 1], db), f"db{l - 1}"
+
+
+def test_each_layer_runs_the_kernels_it_should(env, task, monkeypatch):
+    """The speed contract of the one layer path, which bit equality cannot see: a one-head layer aggregates on the PLANNED single-head
+    kernel in both directions and takes its value gradient from sddmm; a layer of several heads runs the _heads calls; nothing is
+    transposed."""
+    ops, g = env["ops"], task["g"]
+    calls = []
+
+    def record(name):
+        inner = getattr(ops, name)
+
+        def wrapper(*a, **kw):
+            calls.append((name, kw.get("plan")))
+            return inner(*a, **kw)
+        monkeypatch.setattr(ops, name, wrapper)
+
+    for name in ("spmm", "spmm_heads", "sddmm", "sddmm_heads", "transpose"):
+        record(name)
+    X, t, rows = dev(env, task["X"]), dev(env, task["target"]), dev(env, task["rows"])
+
+    def step(heads):
+        net = env["ops"].GatStack(g, DIMS, seed=950, heads=heads)
+        del calls[:]
+        net.train_step(X, t, rows, lr=0.0)
+        return list(calls)
+
+    def count(seen, name):
+        return sum(1 for c in seen if c[0] == name)
+
+    seen = step(None)                     # two one-head layers
+    plans = [p for name, p in seen if name == "spmm"]
+    assert len(plans) == 4 and sum(p is g.plan for p in plans) == 2 and sum(p is g.plan_t for p in plans) == 2
+    assert count(seen, "sddmm") == 2
+    assert count(seen, "spmm_heads") == 0 and count(seen, "sddmm_heads") == 0 and count(seen, "transpose") == 0
+    seen = step([4, 1])                   # a 4-head layer under a one-head layer
+    plans = [p for name, p in seen if name == "spmm"]
+    assert len(plans) == 2 and sum(p is g.plan for p in plans) == 1 and sum(p is g.plan_t for p in plans) == 1
+    assert count(seen, "sddmm") == 1
+    assert count(seen, "spmm_heads") == 2 and count(seen, "sddmm_heads") == 1 and count(seen, "transpose") == 0
+    # per layer: forward runs layer 0 then 1, backward 1 then 0 -- the 4-head layer's calls are the first and the last three
+    order = [name for name, _ in seen]
+    assert order == ["spmm_heads", "spmm", "sddmm", "spmm", "sddmm_heads", "spmm_heads"]
 
 
 def test_relabelled_graph_is_refused(env):

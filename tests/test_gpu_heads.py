@@ -20,6 +20,7 @@ import pytest
 
 from tests import edge_softmax_ref as er
 from tests import heads_ref as hr
+from tests import helpers  # noqa: F401  (registers the in-tree package as gnncpp_amd: the file also runs on its own)
 from tests import sddmm_ref as sr
 
 pytestmark = pytest.mark.gpu
