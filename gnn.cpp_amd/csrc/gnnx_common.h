@@ -30,6 +30,11 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }   // a float4 may be loaded from p
 
+// workspace carving: sizes rounded up to 256 bytes, and the first 256-byte boundary at or behind a caller's pointer (a workspace
+// query that counts on it adds 256 bytes of room)
+inline size_t align256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+inline char *aligned_base(void *p) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(p) + 255u) & ~(uintptr_t)255u); }
+
 // Scope guard for a device temporary (hipMalloc): released on EVERY exit path of the enclosing scope (the GNNX_HIP_CHECK /
 // GNNX_REQUIRE early returns included).  Temporaries are only made by build-time calls (CSR, plans, norm), which synchronise their
 // stream before the guard runs; hipFree itself synchronises the device before the memory can be handed out again.

@@ -1,13 +1,12 @@
-// Semi-supervised training: a label mask as a row list, a CSR restricted to the entries a mask keeps, softmax cross-entropy over a
-// row list, per-row argmax and accuracy (reference graph.h: Data::set_mask with train / val / test masks; functional.h:59-61 argmax).
+// Semi-supervised training: a label mask as a row list, a CSR restricted to the entries a mask keeps, per-row argmax and accuracy
+// (reference graph.h: Data::set_mask with train / val / test masks; functional.h:59-61 argmax).  The loss over a row list is
+// gnnx_train.hip's.
 //   mask -> rows      wave-wide ballot compaction: 64 mask bytes per wavefront, counts scanned, lanes write at popcount positions
 //   CSR restriction   works in the NON-ZERO domain, not per row: the entry array is cut into chunks of 64 consecutive entries, one
 //                     wavefront a chunk (coalesced reads of colidx / vals), keep bits by __ballot, positions from a scan over the
 //                     chunk counts + popcount of the lanes below.  Entries of one row are consecutive in the array, so surviving
 //                     entries keep their stored order inside the row, and a hub row of 10^6 entries is simply 15 625 chunks spread
 //                     over the device.  rowptr' comes from the same scan: survivors in front of rowptr[r].
-//   loss over rows    softmax_ce_kernel / softmax_ce_vec_kernel of gnnx_train.hip behind a row list: the same expression per element
-//                     and the same order of the row sum, so listing every row gives the bits of gnnx_softmax_ce_f32's dlogits
 //   argmax            one wavefront per row, (max, lowest index) butterfly
 // No floating-point atomics: every float result has the same bits run to run (integer counters only).
 #include "gnnx_common.h"
@@ -19,8 +18,6 @@
 using namespace gnnx;
 
 namespace {
-
-inline size_t align256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 __device__ __forceinline__ uint64_t lanes_below(int lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
 
@@ -157,199 +154,6 @@ hipError_t restrict_ws(int64_t n_chunks, char *base, RestrictWs &w)
     w.prim_bytes = scan_bytes;
     w.total = off + 256;   // room to align the caller's pointer
     return hipSuccess;
-}
-
-inline char *aligned_base(void *p) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(p) + 255u) & ~(uintptr_t)255u); }
-
-// ---------------------------------------------------------------------------------------------------- loss over a row list
-// softmax_ce_kernel (gnnx_train.hip) behind a row list: wavefront i works on row rows[i]; per-row loss to row_loss[i]
-__global__ __launch_bounds__(256) void ce_rows_kernel(const float *X, int64_t ldx, const int32_t *target, const int32_t *rows, int64_t n_listed,
-                                                       int64_t n_rows, int32_t n_cls, float inv_n, float *row_loss, float *dX, int64_t ldd,
-                                                       int32_t *bad)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n_listed) return;
-    const int64_t row = rows[i];
-    if (row < 0 || row >= n_rows) {
-        if (lane == 0) atomicOr(bad, 2);
-        return;
-    }
-    const float *x = X + row * ldx;
-    float sum = 0.f;
-    for (int32_t c = lane; c < n_cls; c += 64) sum += expf(x[c]);
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-    const int32_t t = target[row];
-    if (t < 0 || t >= n_cls) {
-        if (lane == 0) atomicOr(bad, 1);
-        return;
-    }
-    const float denom = sum + 1e-20f;
-    if (lane == 0 && row_loss) row_loss[i] = -logf(expf(x[t]) / denom);
-    if (dX) {
-        float *d = dX + row * ldd;
-        const float rden = 1.0f / denom;
-        for (int32_t c = lane; c < n_cls; c += 64) d[c] = (expf(x[c]) * rden - (c == t ? 1.f : 0.f)) * inv_n;
-    }
-}
-
-// softmax_ce_vec_kernel (gnnx_train.hip) behind a row list: class counts that are a multiple of 4 and at most 1024, 16-byte aligned
-// rows; a lane holds classes 256 k + 4 lane .. + 3, exp evaluated once per element, two listed rows in flight per wavefront, the
-// column sums of the gradient rows a wavefront wrote kept in registers and stored as row `wave id` of the partials.
-template <int KV>
-__global__ __launch_bounds__(256) void ce_rows_vec_kernel(const float *X, int64_t ldx, const int32_t *target, const int32_t *rows,
-                                                           int64_t n_listed, int64_t n_rows, int32_t n_cls, float inv_n, float *row_loss,
-                                                           float *dX, int64_t ldd, int32_t *bad, float *colsum_partial)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
-    float4 cs[KV];
-#pragma unroll
-    for (int k = 0; k < KV; k++) cs[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t i0 = wave; i0 < n_listed; i0 += 2 * n_waves) {
-        float4 e[2][KV];
-        int32_t t[2];
-        int64_t row[2];
-        bool have[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int64_t i = i0 + u * n_waves;
-            have[u] = i < n_listed;
-            row[u] = have[u] ? (int64_t)rows[i] : 0;
-            if (have[u] && (row[u] < 0 || row[u] >= n_rows)) {   // wave-uniform
-                if (lane == 0) atomicOr(bad, 2);
-                have[u] = false;
-            }
-            t[u] = have[u] ? target[row[u]] : 0;
-#pragma unroll
-            for (int k = 0; k < KV; k++) {
-                const int32_t c = 256 * k + 4 * lane;
-                e[u][k] = (have[u] && c < n_cls) ? *reinterpret_cast<const float4 *>(X + row[u] * ldx + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            if (!have[u]) continue;   // wave-uniform
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < KV; k++) {
-                if (256 * k + 4 * lane < n_cls) {
-                    e[u][k].x = expf(e[u][k].x);
-                    e[u][k].y = expf(e[u][k].y);
-                    e[u][k].z = expf(e[u][k].z);
-                    e[u][k].w = expf(e[u][k].w);
-                    sum += e[u][k].x;
-                    sum += e[u][k].y;
-                    sum += e[u][k].z;
-                    sum += e[u][k].w;
-                }
-            }
-            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-            if (t[u] < 0 || t[u] >= n_cls) {
-                if (lane == 0) atomicOr(bad, 1);
-                continue;
-            }
-            const float denom = sum + 1e-20f;
-            if (lane == 0 && row_loss) row_loss[i0 + u * n_waves] = -logf(expf(X[row[u] * ldx + t[u]]) / denom);
-            if (dX) {
-                const float rden = 1.0f / denom;
-#pragma unroll
-                for (int k = 0; k < KV; k++) {
-                    const int32_t c = 256 * k + 4 * lane;
-                    if (c < n_cls) {
-                        float4 d;
-                        d.x = (e[u][k].x * rden - (c + 0 == t[u] ? 1.f : 0.f)) * inv_n;
-                        d.y = (e[u][k].y * rden - (c + 1 == t[u] ? 1.f : 0.f)) * inv_n;
-                        d.z = (e[u][k].z * rden - (c + 2 == t[u] ? 1.f : 0.f)) * inv_n;
-                        d.w = (e[u][k].w * rden - (c + 3 == t[u] ? 1.f : 0.f)) * inv_n;
-                        *reinterpret_cast<float4 *>(dX + row[u] * ldd + c) = d;
-                        cs[k].x += d.x;
-                        cs[k].y += d.y;
-                        cs[k].z += d.z;
-                        cs[k].w += d.w;
-                    }
-                }
-            }
-        }
-    }
-    if (colsum_partial) {
-#pragma unroll
-        for (int k = 0; k < KV; k++) {
-            const int32_t c = 256 * k + 4 * lane;
-            if (c < n_cls) *reinterpret_cast<float4 *>(colsum_partial + wave * n_cls + c) = cs[k];
-        }
-    }
-}
-
-// generic class counts: column sums of the listed gradient rows, one thread per class over a block of the list (a second pass over
-// O(listed rows))
-__global__ __launch_bounds__(256) void ce_rows_colsum_generic(const float *dX, int64_t ldd, const int32_t *rows, int64_t n_listed, int64_t n_rows,
-                                                               int32_t n_cls, float *partial, int64_t rows_per_block)
-{
-    const int64_t i0 = (int64_t)blockIdx.y * rows_per_block, i1 = i0 + rows_per_block < n_listed ? i0 + rows_per_block : n_listed;
-    const int32_t c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= n_cls) return;
-    float acc = 0.f;
-    for (int64_t i = i0; i < i1; i++) {
-        const int64_t row = rows[i];
-        if (row >= 0 && row < n_rows) acc += dX[row * ldd + c];
-    }
-    partial[(int64_t)blockIdx.y * n_cls + c] = acc;
-}
-
-// out[c] = sum over the partial rows, 4 interleaved parts per column combined in part order (fixed order: deterministic)
-__global__ __launch_bounds__(256) void rows_colsum_reduce(const float *partial, int32_t n_part, int32_t n_cls, float *out)
-{
-    __shared__ float red[256];
-    const int c = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int32_t f = blockIdx.x * 64 + c;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (f < n_cls) {
-        int32_t b = part;
-        for (; b + 12 < n_part; b += 16) {
-            a0 += partial[(int64_t)b * n_cls + f];
-            a1 += partial[(int64_t)(b + 4) * n_cls + f];
-            a2 += partial[(int64_t)(b + 8) * n_cls + f];
-            a3 += partial[(int64_t)(b + 12) * n_cls + f];
-        }
-        for (; b < n_part; b += 4) a0 += partial[(int64_t)b * n_cls + f];
-    }
-    red[threadIdx.x] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (part == 0 && f < n_cls) out[f] = ((red[c] + red[64 + c]) + red[128 + c]) + red[192 + c];
-}
-
-// deterministic two-stage sum of the per-row losses
-__global__ __launch_bounds__(256) void rows_sum_stage1(const float *v, int64_t n, float *partial)
-{
-    __shared__ float red[256];
-    float acc = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) acc += v[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-__global__ void rows_sum_stage2(const float *partial, int n_blocks, float scale, float *out)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        float acc = 0.f;
-        for (int b = 0; b < n_blocks; b++) acc += partial[b];
-        *out = acc * scale;
-    }
-}
-
-constexpr int kSumBlocks = 256;
-constexpr int kCeMaxGroups = 2048;   // as gnnx_train.hip: at most this many workgroups of 4 wavefronts
-constexpr int kCeGenericParts = 256;
-
-inline int ce_groups(int64_t n_listed)
-{
-    int64_t gsz = ceil_div(n_listed, 8);   // 4 wavefronts, 2 rows in flight each
-    return (int)(gsz < 1 ? 1 : (gsz > kCeMaxGroups ? kCeMaxGroups : gsz));
 }
 
 // ---------------------------------------------------------------------------------------------------- argmax / accuracy
@@ -511,85 +315,6 @@ GNNX_API int gnnx_csr_restrict(int32_t n_rows, int32_t n_cols, int64_t nnz, cons
     GNNX_HIP_CHECK(hipStreamSynchronize(st));
     GNNX_REQUIRE(!h_bad, GNNX_ERR_INDEX_RANGE, "column id outside [0, n_cols)");
     *nnz_out = total;
-    return GNNX_OK;
-}
-
-GNNX_API int gnnx_softmax_ce_rows_workspace(int64_t n_listed, int32_t n_classes, size_t *bytes)
-{
-    GNNX_REQUIRE(bytes && n_listed >= 0 && n_classes >= 0, GNNX_ERR_INVALID_ARG, "bad arguments");
-    const size_t parts = (size_t)(4 * ce_groups(n_listed) > kCeGenericParts ? 4 * ce_groups(n_listed) : kCeGenericParts);
-    *bytes = sizeof(float) * ((size_t)n_listed + kSumBlocks + 64 + parts * (size_t)n_classes) + 512;
-    return GNNX_OK;
-}
-
-GNNX_API int gnnx_softmax_ce_rows_f32(const float *d_logits, int64_t ldx, const int32_t *d_target, const int32_t *d_rows, int64_t n_listed,
-                                      int64_t n_rows, int32_t n_classes, int64_t n_total, float *d_loss, float *d_dlogits, int64_t ldd,
-                                      float *d_colsum, void *d_workspace, size_t workspace_bytes, void *stream)
-{
-    GNNX_REQUIRE(n_listed > 0 && n_classes > 0, GNNX_ERR_INVALID_ARG, "empty row list (the mean over no rows is undefined)");
-    GNNX_REQUIRE(n_rows >= n_listed, GNNX_ERR_INVALID_ARG, "more listed rows than rows");
-    GNNX_REQUIRE(n_total >= n_listed, GNNX_ERR_INVALID_ARG, "n_total < n_listed");
-    GNNX_REQUIRE(d_logits && d_target && d_rows && ldx >= n_classes, GNNX_ERR_INVALID_ARG, "null pointer or ld < n_classes");
-    GNNX_REQUIRE(!d_dlogits || ldd >= n_classes, GNNX_ERR_INVALID_ARG, "ldd < n_classes");
-    GNNX_REQUIRE(!d_colsum || d_dlogits, GNNX_ERR_INVALID_ARG, "column sums are those of dlogits: dlogits is null");
-    size_t need = 0;
-    gnnx_softmax_ce_rows_workspace(n_listed, n_classes, &need);
-    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
-    float *row_loss = reinterpret_cast<float *>(aligned_base(d_workspace));
-    float *partial = row_loss + n_listed;
-    int32_t *bad = reinterpret_cast<int32_t *>(partial + kSumBlocks);
-    float *cpart = reinterpret_cast<float *>(aligned_base(bad + 4));
-    GNNX_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-    const float inv_n = 1.0f / (float)n_total;
-    // the same choice of form as gnnx_softmax_ce_partial_f32 makes for the same matrix: listing every row gives its dlogits bits
-    const bool vec = n_classes % 4 == 0 && n_classes <= 1024 && ldx % 4 == 0 && (!d_dlogits || ldd % 4 == 0) &&
-                     (reinterpret_cast<uintptr_t>(d_logits) & 15u) == 0 && (reinterpret_cast<uintptr_t>(d_dlogits) & 15u) == 0;
-    float *rl = d_loss ? row_loss : nullptr;
-    if (vec) {
-        const int groups = ce_groups(n_listed);
-        float *cp = d_colsum ? cpart : nullptr;
-        const int kv = (n_classes + 255) / 256;
-#define GNNX_CE_ROWS_LAUNCH(KV)                                                                                                     \
-    hipLaunchKernelGGL(ce_rows_vec_kernel<KV>, dim3((uint32_t)groups), dim3(256), 0, st, d_logits, ldx, d_target, d_rows, n_listed, n_rows, \
-                       n_classes, inv_n, rl, d_dlogits, ldd, bad, cp)
-        if (kv == 1) GNNX_CE_ROWS_LAUNCH(1);
-        else if (kv == 2) GNNX_CE_ROWS_LAUNCH(2);
-        else if (kv == 3) GNNX_CE_ROWS_LAUNCH(3);
-        else GNNX_CE_ROWS_LAUNCH(4);
-#undef GNNX_CE_ROWS_LAUNCH
-        GNNX_LAUNCH_CHECK();
-        if (d_colsum) {
-            hipLaunchKernelGGL(rows_colsum_reduce, dim3((uint32_t)ceil_div(n_classes, 64)), dim3(256), 0, st, cpart, 4 * groups, n_classes,
-                               d_colsum);
-            GNNX_LAUNCH_CHECK();
-        }
-    } else {
-        hipLaunchKernelGGL(ce_rows_kernel, dim3((uint32_t)ceil_div(n_listed, 4)), dim3(256), 0, st, d_logits, ldx, d_target, d_rows, n_listed,
-                           n_rows, n_classes, inv_n, rl, d_dlogits, ldd, bad);
-        GNNX_LAUNCH_CHECK();
-        if (d_colsum) {
-            const int parts = (int)(n_listed < kCeGenericParts ? n_listed : kCeGenericParts);
-            const int64_t rpb = ceil_div(n_listed, parts);
-            hipLaunchKernelGGL(ce_rows_colsum_generic, dim3((uint32_t)ceil_div(n_classes, 256), (uint32_t)ceil_div(n_listed, rpb)), dim3(256), 0,
-                               st, d_dlogits, ldd, d_rows, n_listed, n_rows, n_classes, cpart, rpb);
-            GNNX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(rows_colsum_reduce, dim3((uint32_t)ceil_div(n_classes, 64)), dim3(256), 0, st, cpart,
-                               (int32_t)ceil_div(n_listed, rpb), n_classes, d_colsum);
-            GNNX_LAUNCH_CHECK();
-        }
-    }
-    if (d_loss) {
-        hipLaunchKernelGGL(rows_sum_stage1, dim3(kSumBlocks), dim3(256), 0, st, row_loss, n_listed, partial);
-        GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(rows_sum_stage2, dim3(1), dim3(64), 0, st, partial, kSumBlocks, 1.0f / (float)n_total, d_loss);
-        GNNX_LAUNCH_CHECK();
-    }
-    int32_t h_bad = 0;
-    GNNX_HIP_CHECK(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GNNX_HIP_CHECK(hipStreamSynchronize(st));
-    GNNX_REQUIRE(!(h_bad & 2), GNNX_ERR_INDEX_RANGE, "listed row outside [0, n_rows)");
-    GNNX_REQUIRE(!h_bad, GNNX_ERR_INDEX_RANGE, "target class out of range at a listed row");
     return GNNX_OK;
 }
 

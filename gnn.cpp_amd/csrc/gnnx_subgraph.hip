@@ -18,9 +18,6 @@ using namespace gnnx;
 
 namespace {
 
-inline size_t align256(size_t v) { return (v + 255u) & ~(size_t)255u; }
-inline char *aligned_base(void *p) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(p) + 255u) & ~(uintptr_t)255u); }
-
 constexpr int32_t kBadColumn = 1, kBadRowList = 2;
 
 // len[k] = entries of row rows[k] (0 for a row the list should not hold); len[n_listed] = 0 (its scanned value is the total).

@@ -6,20 +6,46 @@
 //   SGD    (textbook; the reference's step() reads an empty velocity vector, nn.cpp:414):  p -= lr * (g + wd * p)
 #include "gnnx_common.h"
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 using namespace gnnx;
 
 namespace {
 
-// one wavefront per row: lanes stride the classes; per-row loss to a buffer, gradient written in place
-__global__ __launch_bounds__(256) void softmax_ce_kernel(const float *X, int64_t ldx, const int32_t *target, int64_t n_rows,
+// Which rows a loss kernel works on: all n of them (work item i is row i), or the n entries of a row list (work item i is row
+// rows[i], held against [0, n_rows)).  The plain form carries the count alone: its kernels have no list operand and no check.
+template <bool LISTED>
+struct RowSel;
+template <>
+struct RowSel<false> {
+    int64_t n;
+};
+template <>
+struct RowSel<true> {
+    int64_t n;
+    const int32_t *rows;
+    int64_t n_rows;
+};
+
+// one wavefront per work item: lanes stride the classes; per-item loss to slot i of a buffer, gradient written in place
+template <bool LISTED>
+__global__ __launch_bounds__(256) void softmax_ce_kernel(const float *X, int64_t ldx, const int32_t *target, RowSel<LISTED> sel,
                                                           int32_t n_cls, float inv_n, float *row_loss, float *dX, int64_t ldd,
                                                           int32_t *bad)
 {
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= sel.n) return;
+    int64_t row = i;
+    if constexpr (LISTED) {
+        row = sel.rows[i];
+        if (row < 0 || row >= sel.n_rows) {   // wave-uniform
+            if (lane == 0) atomicOr(bad, 2);
+            return;
+        }
+    }
     const float *x = X + row * ldx;
     float sum = 0.f;
     for (int32_t c = lane; c < n_cls; c += 64) sum += expf(x[c]);
@@ -30,7 +56,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float *X, int64_t
         return;
     }
     const float denom = sum + 1e-20f;
-    if (lane == 0 && row_loss) row_loss[row] = -logf(expf(x[t]) / denom);
+    if (lane == 0 && row_loss) row_loss[i] = -logf(expf(x[t]) / denom);
     if (dX) {
         float *d = dX + row * ldd;
         const float rden = 1.0f / denom;
@@ -40,13 +66,13 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float *X, int64_t
 
 // Vector form for class counts that are a multiple of 4 and at most 1024 (row stride a multiple of 4, 16-byte aligned): one
 // wavefront per row, a lane holds classes 256 k + 4 lane .. + 3 (one 16-byte load per k: a 256-class row is ONE 1-KiB
-// wave-instruction), exp evaluated once per element and kept in registers, two rows in flight per wavefront.  Waves walk the rows
-// with a grid stride; with `colsum_partial` a wavefront also keeps the column sums of the gradient rows it wrote -- the last
+// wave-instruction), exp evaluated once per element and kept in registers, two rows in flight per wavefront.  Waves walk the work
+// items with a grid stride; with `colsum_partial` a wavefront also keeps the column sums of the gradient rows it wrote -- the last
 // layer's bias gradient, which otherwise is one more 4 N C-byte pass -- and stores them as row `wave id` of the partials (summed
-// by ce_colsum_reduce in a fixed order: deterministic).  Same expressions per element as the generic kernel below
+// by ce_colsum_reduce in a fixed order: deterministic).  Same expressions per element as the generic kernel above
 // (expf(x) * (1 / (sum + 1e-20)), then - onehot, then * 1/N); only the ORDER of the row sum differs (tolerance-level, as documented).
-template <int KV>
-__global__ __launch_bounds__(256) void softmax_ce_vec_kernel(const float *X, int64_t ldx, const int32_t *target, int64_t n_rows,
+template <int KV, bool LISTED>
+__global__ __launch_bounds__(256) void softmax_ce_vec_kernel(const float *X, int64_t ldx, const int32_t *target, RowSel<LISTED> sel,
                                                               int32_t n_cls, float inv_n, float *row_loss, float *dX, int64_t ldd,
                                                               int32_t *bad, float *colsum_partial)
 {
@@ -55,14 +81,24 @@ __global__ __launch_bounds__(256) void softmax_ce_vec_kernel(const float *X, int
     float4 cs[KV];
 #pragma unroll
     for (int k = 0; k < KV; k++) cs[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t r0 = wave; r0 < n_rows; r0 += 2 * n_waves) {
+    for (int64_t i0 = wave; i0 < sel.n; i0 += 2 * n_waves) {
         float4 e[2][KV];
         int32_t t[2];
+        int64_t listed[2];   // LISTED: rows[i], loaded once
         bool have[2];
 #pragma unroll
         for (int u = 0; u < 2; u++) {
-            const int64_t row = r0 + u * n_waves;
-            have[u] = row < n_rows;
+            const int64_t i = i0 + u * n_waves;
+            have[u] = i < sel.n;
+            int64_t row = i;
+            if constexpr (LISTED) {
+                row = have[u] ? (int64_t)sel.rows[i] : 0;
+                if (have[u] && (row < 0 || row >= sel.n_rows)) {   // wave-uniform
+                    if (lane == 0) atomicOr(bad, 2);
+                    have[u] = false;
+                }
+                listed[u] = row;
+            }
             t[u] = have[u] ? target[row] : 0;
 #pragma unroll
             for (int k = 0; k < KV; k++) {
@@ -73,7 +109,7 @@ __global__ __launch_bounds__(256) void softmax_ce_vec_kernel(const float *X, int
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             if (!have[u]) continue;   // wave-uniform
-            const int64_t row = r0 + u * n_waves;
+            const int64_t row = LISTED ? listed[u] : i0 + u * n_waves;
             float sum = 0.f;
 #pragma unroll
             for (int k = 0; k < KV; k++) {
@@ -94,7 +130,7 @@ __global__ __launch_bounds__(256) void softmax_ce_vec_kernel(const float *X, int
                 continue;
             }
             const float denom = sum + 1e-20f;
-            if (lane == 0 && row_loss) row_loss[row] = -logf(expf(X[row * ldx + t[u]]) / denom);
+            if (lane == 0 && row_loss) row_loss[i0 + u * n_waves] = -logf(expf(X[row * ldx + t[u]]) / denom);
             if (dX) {
                 const float rden = 1.0f / denom;   // the gradient has no reference arithmetic to follow (its backward throws): one
                                                    // division per row, a multiplication per element
@@ -149,15 +185,24 @@ __global__ __launch_bounds__(256) void ce_colsum_reduce(const float *partial, in
 }
 
 // generic class counts: a lane walks the classes with stride 64; the column sums (when asked for) by one thread per class
-// over the finished gradient (a second pass; only for shapes off the vector form)
-__global__ __launch_bounds__(256) void ce_colsum_generic(const float *dX, int64_t ldd, int64_t n_rows, int32_t n_cls, float *partial,
+// over the finished gradient rows of a block of the work items (a second pass; only for shapes off the vector form).  A listed
+// row outside the matrix was refused by the loss kernel and is skipped here.
+template <bool LISTED>
+__global__ __launch_bounds__(256) void ce_colsum_generic(const float *dX, int64_t ldd, RowSel<LISTED> sel, int32_t n_cls, float *partial,
                                                           int64_t rows_per_block)
 {
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < n_rows ? r0 + rows_per_block : n_rows;
+    const int64_t i0 = (int64_t)blockIdx.y * rows_per_block, i1 = i0 + rows_per_block < sel.n ? i0 + rows_per_block : sel.n;
     const int32_t c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n_cls) return;
     float acc = 0.f;
-    for (int64_t r = r0; r < r1; r++) acc += dX[r * ldd + c];
+    for (int64_t i = i0; i < i1; i++) {
+        int64_t row = i;
+        if constexpr (LISTED) {
+            row = sel.rows[i];
+            if (row < 0 || row >= sel.n_rows) continue;
+        }
+        acc += dX[row * ldd + c];
+    }
     partial[(int64_t)blockIdx.y * n_cls + c] = acc;
 }
 
@@ -203,21 +248,125 @@ inline int ce_groups(int64_t n_rows)
     return (int)(gsz < 1 ? 1 : (gsz > kCeMaxGroups ? kCeMaxGroups : gsz));
 }
 
+// the caller's workspace, carved: row_loss[n_listed] | partial[kSumBlocks] | bad | column-sum partials (256-byte aligned; only with
+// want_colsum: a row per wavefront of the vector form or per block of the generic pass)
+struct CeWs {
+    float *row_loss, *partial, *cpart;
+    int32_t *bad;
+};
+
+// bytes the loss needs; with `base` (any alignment) also the layout in *out
+size_t carve(int64_t n_listed, int32_t n_classes, bool want_colsum, void *base, CeWs *out)
+{
+    char *p = base ? aligned_base(base) : nullptr;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char *q = p ? p + off : nullptr;
+        off += bytes;
+        return q;
+    };
+    CeWs w{};
+    w.row_loss = reinterpret_cast<float *>(take(sizeof(float) * (size_t)n_listed));
+    w.partial = reinterpret_cast<float *>(take(sizeof(float) * kSumBlocks));
+    w.bad = reinterpret_cast<int32_t *>(take(sizeof(int32_t)));
+    off = align256(off);
+    const size_t parts = (size_t)(4 * ce_groups(n_listed) > kCeGenericParts ? 4 * ce_groups(n_listed) : kCeGenericParts);
+    if (want_colsum) w.cpart = reinterpret_cast<float *>(take(sizeof(float) * parts * (size_t)n_classes));
+    if (out) *out = w;
+    return off + 256;   // room to align the caller's pointer
+}
+
+// The loss over every row of the matrix (rows == nullptr: n_listed == n_rows) or over the listed rows, divisor n_total: the same
+// kernels, grids and summation orders either way, so listing every row gives the bits of the plain call.
+int softmax_ce(const float *logits, int64_t ldx, const int32_t *target, const int32_t *rows /* null: every row */, int64_t n_listed,
+               int64_t n_rows, int32_t n_classes, int64_t n_total, float *loss, float *dlogits, int64_t ldd, float *colsum, void *workspace,
+               size_t bytes, void *stream)
+{
+    GNNX_REQUIRE(n_listed > 0 && n_classes > 0, GNNX_ERR_INVALID_ARG, "empty batch");
+    GNNX_REQUIRE(n_rows >= n_listed, GNNX_ERR_INVALID_ARG, "more listed rows than rows");
+    GNNX_REQUIRE(n_total >= n_listed, GNNX_ERR_INVALID_ARG, "n_total < number of rows in the loss");
+    GNNX_REQUIRE(logits && target && ldx >= n_classes, GNNX_ERR_INVALID_ARG, "null pointer or ld < n_classes");
+    GNNX_REQUIRE(!dlogits || ldd >= n_classes, GNNX_ERR_INVALID_ARG, "ldd < n_classes");
+    GNNX_REQUIRE(!colsum || dlogits, GNNX_ERR_INVALID_ARG, "column sums are those of dlogits: dlogits is null");
+    CeWs w;
+    const size_t need = carve(n_listed, n_classes, colsum != nullptr, workspace, &w);
+    GNNX_REQUIRE(workspace && bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", bytes, need);
+    hipStream_t st = as_stream(stream);
+    GNNX_HIP_CHECK(hipMemsetAsync(w.bad, 0, sizeof(int32_t), st));
+    const float inv_n = 1.0f / (float)n_total;
+    float *rl = loss ? w.row_loss : nullptr;
+    const bool vec = n_classes % 4 == 0 && n_classes <= 1024 && ldx % 4 == 0 && (!dlogits || ldd % 4 == 0) && aligned16(logits) &&
+                     aligned16(dlogits);
+    auto launch = [&](auto sel) -> int {
+        constexpr bool LISTED = std::is_same_v<decltype(sel), RowSel<true>>;
+        int32_t n_part;   // rows of the column-sum partials
+        if (vec) {
+            const int groups = ce_groups(n_listed);
+            n_part = 4 * groups;
+#define GNNX_CE_LAUNCH(KV)                                                                                                              \
+    hipLaunchKernelGGL((softmax_ce_vec_kernel<KV, LISTED>), dim3((uint32_t)groups), dim3(256), 0, st, logits, ldx, target, sel, n_classes, \
+                       inv_n, rl, dlogits, ldd, w.bad, w.cpart)
+            const int kv = (n_classes + 255) / 256;
+            if (kv == 1) GNNX_CE_LAUNCH(1);
+            else if (kv == 2) GNNX_CE_LAUNCH(2);
+            else if (kv == 3) GNNX_CE_LAUNCH(3);
+            else GNNX_CE_LAUNCH(4);
+#undef GNNX_CE_LAUNCH
+            GNNX_LAUNCH_CHECK();
+        } else {
+            hipLaunchKernelGGL(softmax_ce_kernel<LISTED>, dim3((uint32_t)ceil_div(n_listed, 4)), dim3(256), 0, st, logits, ldx, target, sel,
+                               n_classes, inv_n, rl, dlogits, ldd, w.bad);
+            GNNX_LAUNCH_CHECK();
+            const int parts = (int)(n_listed < kCeGenericParts ? n_listed : kCeGenericParts);
+            const int64_t rpb = ceil_div(n_listed, parts);
+            n_part = (int32_t)ceil_div(n_listed, rpb);
+            if (colsum) {
+                hipLaunchKernelGGL(ce_colsum_generic<LISTED>, dim3((uint32_t)ceil_div(n_classes, 256), (uint32_t)n_part), dim3(256), 0, st,
+                                   dlogits, ldd, sel, n_classes, w.cpart, rpb);
+                GNNX_LAUNCH_CHECK();
+            }
+        }
+        if (colsum) {
+            hipLaunchKernelGGL(ce_colsum_reduce, dim3((uint32_t)ceil_div(n_classes, 64)), dim3(256), 0, st, w.cpart, n_part, n_classes, colsum);
+            GNNX_LAUNCH_CHECK();
+        }
+        return GNNX_OK;
+    };
+    const int status = rows ? launch(RowSel<true>{n_listed, rows, n_rows}) : launch(RowSel<false>{n_listed});
+    if (status != GNNX_OK) return status;
+    if (loss) {
+        hipLaunchKernelGGL(sum_stage1, dim3(kSumBlocks), dim3(256), 0, st, w.row_loss, n_listed, w.partial);
+        GNNX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(sum_stage2, dim3(1), dim3(64), 0, st, w.partial, kSumBlocks, 1.0f / (float)n_total, loss);
+        GNNX_LAUNCH_CHECK();
+    }
+    int32_t h_bad = 0;
+    GNNX_HIP_CHECK(hipMemcpyAsync(&h_bad, w.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GNNX_HIP_CHECK(hipStreamSynchronize(st));
+    GNNX_REQUIRE(!(h_bad & 2), GNNX_ERR_INDEX_RANGE, "listed row outside [0, n_rows)");
+    GNNX_REQUIRE(!h_bad, GNNX_ERR_INDEX_RANGE, "target class out of range");
+    return GNNX_OK;
+}
+
 }  // namespace
 
 GNNX_API int gnnx_softmax_ce_colsum_workspace(int64_t n_rows, int32_t n_classes, size_t *bytes)
 {
     GNNX_REQUIRE(bytes && n_rows >= 0 && n_classes >= 0, GNNX_ERR_INVALID_ARG, "bad arguments");
-    const size_t parts = (size_t)(4 * ce_groups(n_rows) > kCeGenericParts ? 4 * ce_groups(n_rows) : kCeGenericParts);
-    *bytes = sizeof(float) * ((size_t)n_rows + kSumBlocks + 64 + parts * (size_t)n_classes) + 256;
+    *bytes = carve(n_rows, n_classes, true, nullptr, nullptr);
     return GNNX_OK;
 }
 
 GNNX_API int gnnx_softmax_ce_workspace(int64_t n_rows, size_t *bytes)
 {
     GNNX_REQUIRE(bytes && n_rows >= 0, GNNX_ERR_INVALID_ARG, "bad arguments");
-    *bytes = sizeof(float) * ((size_t)n_rows + kSumBlocks) + 256;
+    *bytes = carve(n_rows, 0, false, nullptr, nullptr);
     return GNNX_OK;
+}
+
+GNNX_API int gnnx_softmax_ce_rows_workspace(int64_t n_listed, int32_t n_classes, size_t *bytes)
+{
+    return gnnx_softmax_ce_colsum_workspace(n_listed, n_classes, bytes);
 }
 
 // A shard's share of the loss over n_total rows: the mean's divisor is n_total (>= n_rows), so d_loss is THIS rank's term of the
@@ -227,70 +376,8 @@ GNNX_API int gnnx_softmax_ce_partial_f32(const float *d_logits, int64_t ldx, con
                                          int64_t n_total, float *d_loss, float *d_dlogits, int64_t ldd, float *d_colsum,
                                          void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    GNNX_REQUIRE(n_rows > 0 && n_classes > 0, GNNX_ERR_INVALID_ARG, "empty batch");
-    GNNX_REQUIRE(n_total >= n_rows, GNNX_ERR_INVALID_ARG, "n_total < n_rows");
-    GNNX_REQUIRE(d_logits && d_target && ldx >= n_classes, GNNX_ERR_INVALID_ARG, "null pointer or ld < n_classes");
-    GNNX_REQUIRE(!d_dlogits || ldd >= n_classes, GNNX_ERR_INVALID_ARG, "ldd < n_classes");
-    GNNX_REQUIRE(!d_colsum || d_dlogits, GNNX_ERR_INVALID_ARG, "column sums are those of dlogits: dlogits is null");
-    size_t need = 0;
-    if (d_colsum) gnnx_softmax_ce_colsum_workspace(n_rows, n_classes, &need);
-    else gnnx_softmax_ce_workspace(n_rows, &need);
-    GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
-    float *row_loss = static_cast<float *>(d_workspace);
-    float *partial = row_loss + n_rows;
-    int32_t *bad = reinterpret_cast<int32_t *>(partial + kSumBlocks);
-    // column-sum partials: 16-byte aligned, behind the flag
-    float *cpart = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(bad + 4) + 255u) & ~(uintptr_t)255u);
-    GNNX_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-    const float inv_n = 1.0f / (float)n_total;
-    const bool vec = n_classes % 4 == 0 && n_classes <= 1024 && ldx % 4 == 0 && (!d_dlogits || ldd % 4 == 0) &&
-                     (reinterpret_cast<uintptr_t>(d_logits) & 15u) == 0 && (reinterpret_cast<uintptr_t>(d_dlogits) & 15u) == 0;
-    if (vec) {
-        const int groups = ce_groups(n_rows);
-        float *cp = d_colsum ? cpart : nullptr;
-        float *rl = d_loss ? row_loss : nullptr;
-        const int kv = (n_classes + 255) / 256;
-#define GNNX_CE_LAUNCH(KV)                                                                                                       \
-    hipLaunchKernelGGL(softmax_ce_vec_kernel<KV>, dim3((uint32_t)groups), dim3(256), 0, st, d_logits, ldx, d_target, n_rows, n_classes, \
-                       inv_n, rl, d_dlogits, ldd, bad, cp)
-        if (kv == 1) GNNX_CE_LAUNCH(1);
-        else if (kv == 2) GNNX_CE_LAUNCH(2);
-        else if (kv == 3) GNNX_CE_LAUNCH(3);
-        else GNNX_CE_LAUNCH(4);
-#undef GNNX_CE_LAUNCH
-        GNNX_LAUNCH_CHECK();
-        if (d_colsum) {
-            hipLaunchKernelGGL(ce_colsum_reduce, dim3((uint32_t)ceil_div(n_classes, 64)), dim3(256), 0, st, cpart, 4 * groups, n_classes,
-                               d_colsum);
-            GNNX_LAUNCH_CHECK();
-        }
-    } else {
-        hipLaunchKernelGGL(softmax_ce_kernel, dim3((uint32_t)ceil_div(n_rows, 4)), dim3(256), 0, st, d_logits, ldx, d_target, n_rows,
-                           n_classes, inv_n, d_loss ? row_loss : nullptr, d_dlogits, ldd, bad);
-        GNNX_LAUNCH_CHECK();
-        if (d_colsum) {
-            const int parts = (int)(n_rows < kCeGenericParts ? n_rows : kCeGenericParts);
-            const int64_t rpb = ceil_div(n_rows, parts);
-            hipLaunchKernelGGL(ce_colsum_generic, dim3((uint32_t)ceil_div(n_classes, 256), (uint32_t)ceil_div(n_rows, rpb)), dim3(256), 0, st,
-                               d_dlogits, ldd, n_rows, n_classes, cpart, rpb);
-            GNNX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(ce_colsum_reduce, dim3((uint32_t)ceil_div(n_classes, 64)), dim3(256), 0, st, cpart,
-                               (int32_t)ceil_div(n_rows, rpb), n_classes, d_colsum);
-            GNNX_LAUNCH_CHECK();
-        }
-    }
-    if (d_loss) {
-        hipLaunchKernelGGL(sum_stage1, dim3(kSumBlocks), dim3(256), 0, st, row_loss, n_rows, partial);
-        GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sum_stage2, dim3(1), dim3(64), 0, st, partial, kSumBlocks, 1.0f / (float)n_total, d_loss);
-        GNNX_LAUNCH_CHECK();
-    }
-    int32_t h_bad = 0;
-    GNNX_HIP_CHECK(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GNNX_HIP_CHECK(hipStreamSynchronize(st));
-    GNNX_REQUIRE(!h_bad, GNNX_ERR_INDEX_RANGE, "target class out of range");
-    return GNNX_OK;
+    return softmax_ce(d_logits, ldx, d_target, nullptr, n_rows, n_rows, n_classes, n_total, d_loss, d_dlogits, ldd, d_colsum, d_workspace,
+                      workspace_bytes, stream);
 }
 
 GNNX_API int gnnx_softmax_ce_colsum_f32(const float *d_logits, int64_t ldx, const int32_t *d_target, int64_t n_rows, int32_t n_classes,
@@ -306,6 +393,18 @@ GNNX_API int gnnx_softmax_ce_f32(const float *d_logits, int64_t ldx, const int32
 {
     return gnnx_softmax_ce_colsum_f32(d_logits, ldx, d_target, n_rows, n_classes, d_loss, d_dlogits, ldd, nullptr, d_workspace,
                                       workspace_bytes, stream);
+}
+
+// The same loss over the rows a list names (semi-supervised training, include/gnnx.h): work item i is row d_rows[i], only listed
+// rows of dlogits are written, d_target is read at listed rows only; cost O(n_listed).
+GNNX_API int gnnx_softmax_ce_rows_f32(const float *d_logits, int64_t ldx, const int32_t *d_target, const int32_t *d_rows, int64_t n_listed,
+                                      int64_t n_rows, int32_t n_classes, int64_t n_total, float *d_loss, float *d_dlogits, int64_t ldd,
+                                      float *d_colsum, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    GNNX_REQUIRE(n_listed > 0, GNNX_ERR_INVALID_ARG, "empty row list (the mean over no rows is undefined)");
+    GNNX_REQUIRE(d_rows, GNNX_ERR_INVALID_ARG, "null row list");
+    return softmax_ce(d_logits, ldx, d_target, d_rows, n_listed, n_rows, n_classes, n_total, d_loss, d_dlogits, ldd, d_colsum, d_workspace,
+                      workspace_bytes, stream);
 }
 
 GNNX_API int gnnx_sgd_step_f32(float *d_param, const float *d_grad, int64_t n, float lr, float weight_decay, void *stream)

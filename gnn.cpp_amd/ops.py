@@ -1128,43 +1128,44 @@ def gcn_layer_bwd(g, X, W, G):
 
 
 # ---- whole training step: multi-layer GCN + softmax cross-entropy + SGD ----------
+def _softmax_ce(logits, target, rows, d, colsum_out, n_total):
+    """The one call behind softmax_ce (rows is None: every row) and softmax_ce_rows; d: the gradient buffer or None."""
+    N, Cn = logits.shape
+    n = N if rows is None else int(rows.numel())
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    assert colsum_out is None or (d is not None and colsum_out.numel() == Cn and colsum_out.is_contiguous())
+    wsb = C.c_size_t(0)
+    if rows is not None:
+        capi.call("gnnx_softmax_ce_rows_workspace", n, Cn, C.byref(wsb))
+    elif colsum_out is not None:
+        capi.call("gnnx_softmax_ce_colsum_workspace", n, Cn, C.byref(wsb))
+    else:
+        capi.call("gnnx_softmax_ce_workspace", n, C.byref(wsb))
+    ws = _workspace(wsb.value, logits.device, "ce")
+    tail = (int(n if n_total is None else n_total), _ptr(loss), _ptr(d), 0 if d is None else _ld(d), _ptr(colsum_out), _ptr(ws), ws.numel(),
+            _stream())
+    if rows is None:
+        capi.call("gnnx_softmax_ce_partial_f32", _ptr(logits), _ld(logits), _ptr(target), N, Cn, *tail)
+    else:
+        capi.call("gnnx_softmax_ce_rows_f32", _ptr(logits), _ld(logits), _ptr(target), _ptr(rows) if n else None, n, N, Cn, *tail)
+    return loss, d
+
+
 def softmax_ce(logits, target, want_grad=True, colsum_out=None, n_total=None, grad_out=None):
     """(mean loss as a 1-element device tensor, dlogits or None): gnnx_softmax_ce_f32 (reference forward nn.cpp:442-453).
     colsum_out [C]: also the column sums of dlogits (the last layer's bias gradient), from the kernel that writes dlogits.
     n_total: the rows are one shard of a batch of n_total (gnnx_softmax_ce_partial_f32: loss = this rank's term of the mean).
     grad_out: where dlogits goes (e.g. the [:n_local] rows of a [local | halo] buffer)."""
-    N, Cn = logits.shape
-    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     d = (torch.empty_like(logits) if grad_out is None else grad_out) if want_grad else None
-    wsb = C.c_size_t(0)
-    if colsum_out is not None:
-        assert want_grad and colsum_out.numel() == Cn and colsum_out.is_contiguous()
-        capi.call("gnnx_softmax_ce_colsum_workspace", N, Cn, C.byref(wsb))
-    else:
-        capi.call("gnnx_softmax_ce_workspace", N, C.byref(wsb))
-    ws = _workspace(wsb.value, logits.device, "ce")
-    capi.call("gnnx_softmax_ce_partial_f32", _ptr(logits), _ld(logits), _ptr(target), N, Cn, int(N if n_total is None else n_total), _ptr(loss),
-              _ptr(d), _ld(d) if want_grad else 0, _ptr(colsum_out), _ptr(ws), wsb.value, _stream())
-    return loss, d
+    return _softmax_ce(logits, target, None, d, colsum_out, n_total)
 
 
 def softmax_ce_rows(logits, target, rows, colsum_out=None, grad_out=None, n_total=None, want_grad=True):
     """gnnx_softmax_ce_rows_f32: (loss over the listed rows / n_total as a 1-element device tensor, dlogits or None).  Only the listed
     rows of the gradient buffer are written: pass a zeroed grad_out (without one a zero-filled buffer is made).  target is read at
     listed rows only.  colsum_out [C]: the column sums of the listed gradient rows.  n_total: the divisor (default: len(rows))."""
-    N, Cn = logits.shape
-    nl = int(rows.numel())
-    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     d = (torch.zeros_like(logits) if grad_out is None else grad_out) if want_grad else None
-    if colsum_out is not None:
-        assert want_grad and colsum_out.numel() == Cn and colsum_out.is_contiguous()
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_softmax_ce_rows_workspace", nl, Cn, C.byref(wsb))
-    ws = _workspace(wsb.value, logits.device, "ce")
-    capi.call("gnnx_softmax_ce_rows_f32", _ptr(logits), _ld(logits), _ptr(target), _ptr(rows) if nl else None, nl, N, Cn,
-              int(nl if n_total is None else n_total), _ptr(loss), _ptr(d), _ld(d) if want_grad else 0, _ptr(colsum_out), _ptr(ws),
-              ws.numel(), _stream())
-    return loss, d
+    return _softmax_ce(logits, target, rows, d, colsum_out, n_total)
 
 
 def argmax_rows(logits):
@@ -1186,6 +1187,23 @@ def accuracy(logits, target, rows=None):
     capi.call("gnnx_accuracy_rows_f32", _ptr(logits), _ld(logits), _ptr(target), _ptr(rows) if (rows is not None and nl) else None, nl, N, Cn,
               None, C.byref(correct), _ptr(ws), ws.numel(), _stream())
     return correct.value, nl
+
+
+def _zeroed_grad_buffer(net, key_obj):
+    """net.grad_buffer() zero everywhere outside the rows softmax_ce_rows writes for key_obj (a labelled set, a row list): zeroed when
+    first used and whenever a different object arrives (the rows the previous one wrote must become zero again)."""
+    G = net.grad_buffer()
+    key = (id(key_obj), G.data_ptr())
+    if getattr(net, "_grad_zeroed_for", None) != key:
+        G.zero_()
+        net._grad_zeroed_for = key
+        net._grad_set = key_obj   # keeps the object alive: id() stays unique
+    return G
+
+
+def _loss_and_accuracy(logits, target, rows):
+    """(loss over `rows` as a 1-element tensor, correct predictions among them, len(rows)) of a forward's logits."""
+    return (softmax_ce_rows(logits, target, rows, want_grad=False)[0], *accuracy(logits, target, rows))
 
 
 def sgd_step(param, grad, lr, weight_decay=0.0):
@@ -1334,15 +1352,8 @@ class GcnStack:
             sgd_step(p, gr, lr, weight_decay)
 
     def masked_grad_buffer(self, labelled):
-        """grad_buffer() zero everywhere outside the rows softmax_ce_rows writes: zeroed when first used and whenever a different
-        labelled set arrives (the rows the previous set wrote must become zero again)."""
-        G = self.grad_buffer()
-        key = (id(labelled), G.data_ptr())
-        if getattr(self, "_grad_zeroed_for", None) != key:
-            G.zero_()
-            self._grad_zeroed_for = key
-            self._grad_set = labelled   # keeps the set alive: id() stays unique
-        return G
+        """grad_buffer() zero everywhere outside the rows softmax_ce_rows writes for this labelled set."""
+        return _zeroed_grad_buffer(self, labelled)
 
     def train_step(self, X, target, labelled, lr, weight_decay=0.0):
         """One semi-supervised SGD step: forward with the pruned last layer -> softmax_ce_rows over labelled.rows (db[-1] from the loss
@@ -1384,10 +1395,7 @@ class GcnStack:
     def evaluate(self, X, target, rows):
         """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows)).  rows: ascending
         int32 rows of the graph (g.rows_of(mask) for a vertex-order validation / test mask)."""
-        logits = self.forward(X)
-        loss, _ = softmax_ce_rows(logits, target, rows, want_grad=False)
-        correct, count = accuracy(logits, target, rows)
-        return loss, correct, count
+        return _loss_and_accuracy(self.forward(X), target, rows)
 
     def _field_logits(self, X, field):
         """[len(field.rows[L]), C] logits of the field's unique query rows (compact row k = graph row field.rows[L][k]), each layer a
@@ -1438,9 +1446,7 @@ class GcnStack:
         logits = self._field_logits(X, field)
         rows = field.rows[len(self.W)]
         t = target.reshape(-1)[rows.long()].to(torch.int32).contiguous()
-        loss, _ = softmax_ce_rows(logits, t, field.compact_rows, want_grad=False)
-        correct, count = accuracy(logits, t, field.compact_rows)
-        return loss, correct, count
+        return _loss_and_accuracy(logits, t, field.compact_rows)
 
 
 class GatStack:
@@ -1590,19 +1596,11 @@ class GatStack:
         input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)); target is read at listed rows only.  No layer is
         pruned to the listed rows.  Returns the loss tensor."""
         logits = self.forward(X)
-        G = self.grad_buffer()
-        key = (id(rows), G.data_ptr())
-        if getattr(self, "_grad_zeroed_for", None) != key:   # softmax_ce_rows writes the listed rows only: the rest must be zero
-            G.zero_()
-            self._grad_zeroed_for, self._grad_rows = key, rows
-        loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=G)
+        loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=_zeroed_grad_buffer(self, rows))
         self.backward(G, input_grad=False, have_last_bias_grad=True)
         self.step(lr, weight_decay)
         return loss
 
     def evaluate(self, X, target, rows):
         """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows))."""
-        logits = self.forward(X)
-        loss, _ = softmax_ce_rows(logits, target, rows, want_grad=False)
-        correct, count = accuracy(logits, target, rows)
-        return loss, correct, count
+        return _loss_and_accuracy(self.forward(X), target, rows)

@@ -448,6 +448,8 @@ int gnnx_bn_relu_bwd_apply_f32(const float *d_X, int64_t ldx, const float *d_Y, 
  *             (no max-subtraction, like the reference); d_loss: one float on the device (may be NULL)
  *   dlogits = (softmax(x_i) - onehot(t_i)) / N                             textbook (the reference's backward throws);
  *             may be NULL.  Synchronises `stream` (validates the targets: GNNX_ERR_INDEX_RANGE).
+ *   One kernel set serves these calls and gnnx_softmax_ce_rows_f32 below (the loss over a row list); each *_workspace query is the
+ *   layout its call then uses, and the workspace pointer may have any alignment.
  *   sgd     : p -= lr * (g + weight_decay * p)                             textbook (nn.cpp:395-421 indexes an empty vector)
  */
 int gnnx_softmax_ce_workspace(int64_t n_rows, size_t *bytes);
@@ -502,8 +504,9 @@ int gnnx_bce_logits_f32(const float *d_scores, const float *d_target, int64_t n,
  *                       is left as it is (the caller zeroes it once); d_colsum [n_classes] (may be NULL) = column sums of those
  *                       gradient rows, fixed order.  n_total >= n_listed is the divisor (n_listed on one GPU; the labelled count of
  *                       the whole batch on a shard).  d_rows: ascending, no repeats, each in [0, n_rows).  Targets are read at listed
- *                       rows only (-1 elsewhere is fine).  Same expression per element and the same row-sum order as
- *                       gnnx_softmax_ce_f32: listing every row gives its dlogits bits.  Cost O(n_listed), not O(n_rows).
+ *                       rows only (-1 elsewhere is fine).  The kernels, grids and summation orders of gnnx_softmax_ce_colsum_f32
+ *                       behind the list: listing every row gives its loss, dlogits and column-sum bits.  Cost O(n_listed), not
+ *                       O(n_rows).
  *                       Synchronises.  GNNX_ERR_INDEX_RANGE: a target outside [0, n_classes) at a listed row, or a listed row
  *                       outside [0, n_rows); GNNX_ERR_INVALID_ARG: n_listed == 0 (never a NaN loss).
  *   gnnx_argmax_rows_f32      d_pred[i] = the FIRST index of the maximum of row i (functional.h:59-61), every row.

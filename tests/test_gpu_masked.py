@@ -112,7 +112,7 @@ def test_csr_restrict_equals_numpy_filter(env, relabel):
 
 
 # ------------------------------------------------------------------ 3. loss over a row list
-@pytest.mark.parametrize("n,c", [(20001, 256), (777, 48), (5000, 1000), (3001, 1028), (100, 7), (9, 4)])
+@pytest.mark.parametrize("n,c", [(20001, 256), (777, 48), (5000, 1000), (3001, 1028), (100, 7), (9, 4), (301, 300), (301, 600)])
 def test_softmax_ce_rows_shapes_masks_and_column_sums(env, n, c):
     ops, torch, capi = env["ops"], env["torch"], env["capi"]
     X = synth.uniform_pm1(900 + c, (n, c)) * 3.0
@@ -164,14 +164,16 @@ def test_softmax_ce_rows_shapes_masks_and_column_sums(env, n, c):
         with pytest.raises(capi.GnnxError) as ei:
             ops.softmax_ce_rows(dev(env, X), dev(env, tb), rows)
         assert ei.value.status == -3
-    # every row listed: the gradient bits of ops.softmax_ce, the loss within the bound
+    # every row listed: the bits of ops.softmax_ce (gradient, column sums and loss), the loss within the bound
     all_rows = torch.arange(n, dtype=torch.int32, device="cuda")
     for pad in (0, 4):
         Xd = torch.zeros((n, c + pad), dtype=torch.float32, device="cuda")
         Xd[:, :c] = dev(env, X)
-        loss_f, d_f = ops.softmax_ce(Xd[:, :c], dev(env, t_all))
-        loss_r, d_r = ops.softmax_ce_rows(Xd[:, :c], dev(env, t_all), all_rows)
-        assert torch.equal(d_f, d_r)
+        db_f = torch.full((c,), 7.0, dtype=torch.float32, device="cuda")
+        db_r = torch.full((c,), -7.0, dtype=torch.float32, device="cuda")
+        loss_f, d_f = ops.softmax_ce(Xd[:, :c], dev(env, t_all), colsum_out=db_f)
+        loss_r, d_r = ops.softmax_ce_rows(Xd[:, :c], dev(env, t_all), all_rows, colsum_out=db_r)
+        assert torch.equal(d_f, d_r) and torch.equal(loss_f, loss_r) and torch.equal(db_f, db_r)
         ref = oracle.cross_entropy(X, t_all)
         assert abs(float(host(loss_r)[0]) - ref) <= 1e-5 * max(1.0, abs(ref))
     with pytest.raises(capi.GnnxError) as ei:   # an empty list: an error, never a NaN loss

@@ -1260,7 +1260,7 @@ def test_softmax_cross_entropy_vs_oracle_and_float64(env):
         ops.softmax_ce(dev(env, X), dev(env, np.full(n, c, dtype=np.int32)))
 
 
-@pytest.mark.parametrize("n,c", [(20001, 256), (777, 48), (5000, 1000), (3001, 1028), (100, 7), (9, 4)])
+@pytest.mark.parametrize("n,c", [(20001, 256), (777, 48), (5000, 1000), (3001, 1028), (100, 7), (9, 4), (301, 300), (301, 600)])
 def test_softmax_cross_entropy_shapes_and_fused_bias_gradient(env, n, c):
     """Both kernels of gnnx_softmax_ce_colsum_f32 (the one-16-byte-load-per-lane form for class counts that are multiples of 4 up
     to 1024 -- the bench's 256 is one 1-KiB wave-instruction per row -- and the generic walk) against float64, an odd number of
