@@ -762,6 +762,59 @@ def edge_softmax_heads_bwd(rowptr, colidx, n_heads, alpha, dalpha, scores=None, 
     return dt, drow
 
 
+REDUCE_OPS = {"max": 0, "min": 1}   # GNNX_REDUCE_MAX / GNNX_REDUCE_MIN
+
+
+def _reduce_workspace(n_rows, nnz, F, device):
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, F, C.byref(wsb))
+    return _workspace(wsb.value, device, "reduce")
+
+
+def spmm_reduce(rowptr, colidx, X, op="max", vals=None, out=None, arg_out=None, want_arg=True):
+    """gnnx_spmm_csr_reduce_f32: (Y, arg) with Y[i, f] = max (op="min": min) over the stored entries p of row i of vals[p] * X[c_p, f]
+    (X[c_p, f] itself without vals) and arg[i, f] = the first position p that attains it -- int32, absolute in colidx; an empty row
+    gives +0 and -1.  want_arg=False: arg is None and not computed.  The bits are a function of the inputs alone (include/gnnx.h
+    "neighbourhood reductions")."""
+    if op not in REDUCE_OPS:
+        raise capi.GnnxError(-1, "spmm_reduce", f"op must be 'max' or 'min', got {op!r}")
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    n_cols, F = X.shape
+    if vals is not None and (int(vals.numel()) != nnz or not vals.is_contiguous() or vals.dtype != torch.float32):
+        raise capi.GnnxError(-2, "spmm_reduce", f"vals must be a contiguous float32 vector of {nnz} entries")
+    if out is None:
+        out = torch.empty((n_rows, F), dtype=torch.float32, device=X.device)
+    arg = (torch.empty((n_rows, F), dtype=torch.int32, device=X.device) if arg_out is None else arg_out) if want_arg else None
+    assert tuple(out.shape) == (n_rows, F) and (arg is None or (tuple(arg.shape) == (n_rows, F) and arg.dtype == torch.int32))
+    ws = _reduce_workspace(n_rows, nnz, F, X.device)
+    capi.call("gnnx_spmm_csr_reduce_f32", REDUCE_OPS[op], n_rows, n_cols, F, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None,
+              _ptr(vals) if nnz else None, _ptr(X) if X.numel() else None, _ld(X), _ptr(out), _ld(out), _ptr(arg),
+              _ld(arg) if arg is not None else 0, _ptr(ws), ws.numel(), _stream())
+    return out, arg
+
+
+def spmm_reduce_bwd(rowptr_t, colidx_t, map_t, arg, G, vals=None, out=None, beta=0.0):
+    """gnnx_spmm_csr_reduce_bwd_f32: dX = beta * dX + the gradient of spmm_reduce with respect to X, on the TRANSPOSED pattern: entry q
+    of row c of CSR(A^T) adds vals[map_t[q]] * G[i, f] (i = colidx_t[q]) where arg[i, f] == map_t[q].  map_t: csr_transpose_map; vals in
+    the order of CSR(A).  No atomics: a documented order (include/gnnx.h), the same bits every run."""
+    n_rows_t, nnz = int(rowptr_t.numel() - 1), int(colidx_t.numel())
+    n_cols_t, F = G.shape
+    if tuple(arg.shape) != (n_cols_t, F) or arg.dtype != torch.int32 or int(map_t.numel()) != nnz:
+        raise capi.GnnxError(-2, "spmm_reduce_bwd", f"arg must be int32 {(n_cols_t, F)} and map_t have {nnz} entries")
+    if vals is not None and (int(vals.numel()) != nnz or not vals.is_contiguous() or vals.dtype != torch.float32):
+        raise capi.GnnxError(-2, "spmm_reduce_bwd", f"vals must be a contiguous float32 vector of {nnz} entries")
+    if out is None:
+        if beta != 0.0:
+            raise capi.GnnxError(-1, "spmm_reduce_bwd", "beta = 1 needs the matrix to add to (out)")
+        out = torch.empty((n_rows_t, F), dtype=torch.float32, device=G.device)
+    assert tuple(out.shape) == (n_rows_t, F)
+    ws = _reduce_workspace(n_rows_t, nnz, F, G.device)
+    capi.call("gnnx_spmm_csr_reduce_bwd_f32", n_rows_t, n_cols_t, F, nnz, _ptr(rowptr_t), _ptr(colidx_t) if nnz else None,
+              _ptr(map_t) if nnz else None, _ptr(vals) if nnz else None, _ptr(arg) if arg.numel() else None, _ld(arg),
+              _ptr(G) if G.numel() else None, _ld(G), float(beta), _ptr(out), _ld(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
 def transpose(X, out=None):
     """gnnx_transpose_f32: out[c, r] = X[r, c] (materialised)."""
     R, Cn = X.shape
@@ -1595,6 +1648,132 @@ class GatStack:
         """One SGD step on the listed rows: forward -> softmax_ce_rows over `rows` (db[-1] from the loss kernel) -> backward without an
         input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)); target is read at listed rows only.  No layer is
         pruned to the listed rows.  Returns the loss tensor."""
+        logits = self.forward(X)
+        loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=_zeroed_grad_buffer(self, rows))
+        self.backward(G, input_grad=False, have_last_bias_grad=True)
+        self.step(lr, weight_decay)
+        return loss
+
+    def evaluate(self, X, target, rows):
+        """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows))."""
+        return _loss_and_accuracy(self.forward(X), target, rows)
+
+
+def relu_mask(Y, dY, out=None):
+    """out = dY where Y > 0, else 0 -- ReLU's backward from its stored output (gnnx_bn_relu_bwd_f32 without statistics)."""
+    N, F = Y.shape
+    out = torch.empty_like(dY) if out is None else out
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_bn_workspace", N, F, C.byref(wsb))
+    ws = _workspace(wsb.value, Y.device, "bn")
+    capi.call("gnnx_bn_relu_bwd_f32", _ptr(Y), _ld(Y), _ptr(Y), _ld(Y), _ptr(dY), _ld(dY), N, F, None, None, 0.0, None, None, 1, _ptr(out), _ld(out),
+              None, None, _ptr(ws), wsb.value, _stream())
+    return out
+
+
+class SageStack:
+    """L GraphSAGE layers (Hamilton et al. 2017) on one graph, the surface of GatStack: the vertex keeps a weight of its own,
+        M = agg_j h_j over the STORED columns j of row i;   h' = act( h W_s^T + M W_n^T + b ),  ReLU between layers, none after the last.
+    aggr="mean": M = inv_deg (.) (A . h) with inv_deg[i] = 1 / deg_i (one correctly rounded division; 0 for an empty row) -- the planned
+    aggregation (spmm with rowscale, g.plan) forward, and spmm on CSR(A^T) with colscale = inv_deg (g.plan_t) backward: existing
+    kernels with existing bits, so a relabelled graph is fine.  aggr="max": M, arg = spmm_reduce(h) forward with arg kept per layer, and
+    spmm_reduce_bwd through g.attention_map() backward -- which refuses a relabelled graph and one without a transposed CSR, with
+    GatStack's GnnxError.  An empty row aggregates to zero: its output is h W_s^T + b.
+    forward / backward / step / train_step / evaluate / grad_buffer; every operation of forward and backward is a C-ABI call (the
+    aggregation, the dense products, the bias add, the ReLU and its mask).  No atomics on any value; the same bits every run."""
+
+    def __init__(self, g, dims, aggr="mean", seed=0, device="cuda"):
+        if aggr not in ("mean", "max"):
+            raise ValueError(f"aggr must be 'mean' or 'max', got {aggr!r}")
+        self.g, self.dims, self.aggr = g, list(dims), aggr
+        L = len(dims) - 1
+        if aggr == "max":
+            self.map_t = g.attention_map()
+        else:
+            deg = (g.rowptr[1:] - g.rowptr[:-1]).cpu().to(torch.float32)      # the division on the host: IEEE, rounded once
+            self.inv_deg = torch.where(deg > 0, 1.0 / deg, torch.zeros_like(deg)).to(g.rowptr.device)
+        self.W_s = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.W_n = [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
+        self.dW_s = [torch.zeros_like(w) for w in self.W_s]
+        self.dW_n = [torch.zeros_like(w) for w in self.W_n]
+        self.db = [torch.zeros_like(b) for b in self.b]
+        self._saved = None
+        self._buf = {}
+
+    def _tmp(self, key, shape, device, dtype=torch.float32):
+        t = self._buf.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._buf[key] = torch.empty(shape, dtype=dtype, device=device)
+        return t
+
+    def grad_buffer(self):
+        """Where the loss should write dlogits ([n, dims[-1]])."""
+        return self._tmp("G", (self.g.n, self.dims[-1]), self.W_s[0].device)
+
+    def _aggregate(self, l, h):
+        """(M, arg) of layer l: the neighbourhood's mean (arg None) or its maximum with the winning entries."""
+        g = self.g
+        M = self._tmp(("M", l), (g.n, self.dims[l]), h.device)
+        if self.aggr == "mean":
+            return spmm(g.rowptr, g.colidx, h, out=M, rowscale=self.inv_deg, plan=g.plan), None
+        return spmm_reduce(g.rowptr, g.colidx, h, op="max", out=M, arg_out=self._tmp(("arg", l), (g.n, self.dims[l]), h.device, torch.int32))
+
+    def _aggregate_bwd(self, l, dM, arg, out):
+        """out += the aggregation's gradient with respect to h."""
+        g = self.g
+        if self.aggr == "mean":
+            if g.rowptr_t is None:
+                raise capi.GnnxError(-1, "SageStack", "the graph has no transposed CSR (from_coo(..., transpose=True))")
+            return spmm(g.rowptr_t, g.colidx_t, dM, out=out, colscale=self.inv_deg, beta=1.0, plan=g.plan_t)
+        return spmm_reduce_bwd(g.rowptr_t, g.colidx_t, self.map_t, arg, dM, out=out, beta=1.0)
+
+    def forward(self, X):
+        L, n = len(self.W_s), self.g.n
+        saved, h = [], X
+        for l in range(L):
+            M, arg = self._aggregate(l, h)
+            Z = gemm(h, self.W_s[l], transB=True, out=self._tmp(("Z", l), (n, self.dims[l + 1]), X.device))
+            gemm(M, self.W_n[l], transB=True, out=Z, beta=1.0)
+            Y = self._tmp(("Y", l), (n, self.dims[l + 1]), X.device)
+            bias_add(Z, self.b[l], out=Y)
+            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
+                bn_relu_fwd(Y, relu=True, out=Y)
+            saved.append((h, M, arg, Y))
+            h = Y
+        self._saved = saved
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """dW_s, dW_n and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        L, n = len(self.W_s), self.g.n
+        G = dOut
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            h, M, arg, _ = self._saved[l]
+            gemm(G, h, transA=True, out=self.dW_s[l])
+            gemm(G, M, transA=True, out=self.dW_n[l])
+            if l == 0 and not input_grad:
+                return None
+            dM = gemm(G, self.W_n[l], out=self._tmp(("dM", l), (n, self.dims[l]), G.device))
+            dh = gemm(G, self.W_s[l], out=self._tmp(("dh", l), (n, self.dims[l]), G.device))     # through the vertex itself
+            self._aggregate_bwd(l, dM, arg, dh)                                                  # + through its neighbourhood
+            if l == 0:
+                return dh
+            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l]), G.device))           # h = relu output of the layer below
+            colsum(G, out=self.db[l - 1])
+        return G
+
+    def step(self, lr, weight_decay=0.0):
+        for p, gr in zip(self.W_s + self.W_n + self.b, self.dW_s + self.dW_n + self.db):
+            sgd_step(p, gr, lr, weight_decay)
+
+    def train_step(self, X, target, rows, lr, weight_decay=0.0):
+        """One SGD step on the listed rows: forward -> softmax_ce_rows over `rows` (db[-1] from the loss kernel) -> backward without an
+        input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)); target is read at listed rows only.  Returns the
+        loss tensor."""
         logits = self.forward(X)
         loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=_zeroed_grad_buffer(self, rows))
         self.backward(G, input_grad=False, have_last_bias_grad=True)

@@ -743,6 +743,65 @@ int gnnx_edge_softmax_bwd_csr_heads_f32(int32_t n_rows, int32_t n_cols, int64_t 
                                         int64_t lda, const float *d_dalpha, int64_t ldd, float *d_dt, int64_t ldt, float *d_drowterm,
                                         int64_t drowterm_stride, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ neighbourhood reductions ---- */
+/*
+ * The reduce operators of message passing that are not a sum: an element-wise MAX / MIN over the stored entries of each row of a CSR
+ * pattern, with its arg, and the backward that routes every gradient element to the one entry that won -- what a GraphSAGE pooling
+ * layer, PNA or a graph max-pool needs.  The reference's MessagePassing base declares the hook (message / aggregate_and_update,
+ * reference graph.h:114-115) and implements only GCN's sum; the contract is this comment, restated in NumPy by tests/reduce_ref.py.
+ *
+ * Forward, gnnx_spmm_csr_reduce_f32, for entry p of row i with column c_p = colidx[p]:
+ *   t_p,f     = vals[p] * X[c_p, f]        ONE rounded fp32 multiply; with vals == NULL t_p,f = X[c_p, f] with its own bits.
+ *   arg[i, f] = the SMALLEST position p of row i such that no entry q of the row has t_q,f > t_p,f  (GNNX_REDUCE_MIN: <): an ABSOLUTE
+ *               entry position in [rowptr[i], rowptr[i+1]).
+ *   Y[i, f]   = t_arg,f with that entry's bits: where +0 and -0 tie the earlier entry wins and keeps its sign.
+ * An empty row writes Y = +0 and arg = -1.  A non-empty row ALWAYS gets a valid position, also when every t is -inf (MIN: +inf): there
+ * is no sentinel that a strict compare can never beat.  With a NaN among the t the value and the arg are unspecified; no out-of-range
+ * access ever happens.  d_arg may be NULL.  X: [n_cols, n_feat] ld ldx; Y (float) ld ldy and arg (int32) ld lda: [n_rows, n_feat];
+ * columns beyond n_feat are not touched.  X aliases no output.  A maximum has no order: the result is a function of the inputs alone,
+ * however a row is split or mapped to lanes.
+ *
+ * Backward, gnnx_spmm_csr_reduce_bwd_f32: the gradient with respect to X (vals are constants; their gradient is not this call's job).
+ * It runs on the TRANSPOSED pattern, as every backward here does: entry q of row c of CSR(A^T) is the stored entry (i, c) of A with
+ * i = colidx_t[q] and p = map_t[q] its position in CSR(A) (gnnx_csr_transpose_map).  Entry q contributes vals[p] * G[i, f] (the product
+ * rounded first; G[i, f] with vals == NULL) iff arg[i, f] == p, and nothing otherwise.
+ *   ORDER of the sum, with S = 4096: row c is cut into segments of S consecutive entries (the last may be short); a segment is summed
+ *   by ONE accumulator per feature starting from +0 and walking the segment from its LAST entry to its FIRST; the row sum is
+ *   ((seg_0 + seg_1) + seg_2) + ... in ascending segment order.  A row of at most S entries is therefore the aggregation's own
+ *   descending one-accumulator chain (gnnx_spmm_csr_f32 with the 0/1 match folded into the values); a hub column of 10^4 .. 10^6
+ *   entries spreads over d / S lane groups instead of one.
+ *   dX[c, f] = acc with beta == 0 (dX is never read), dX[c, f] + acc with beta == 1.
+ * d_dX: [n_rows_t, n_feat] ld ldx; d_G (float, ld ldg) and d_arg (int32, ld lda): [n_cols_t, n_feat].  d_vals is indexed by the
+ * positions of CSR(A).  No atomics on any value: the bits are the same on every run.
+ *
+ * Both calls are asynchronous on `stream` (a chain of launches on that one stream); they allocate nothing and synchronise nothing and
+ * TRUST the CSR and nnz (= rowptr[n_rows]).  Negative sizes, a leading dimension < n_feat, an op outside the enum, a beta other than 0
+ * or 1 and nnz >= 2^31 are GNNX_ERR_INVALID_ARG before any device call, and so is a null pointer (d_vals and the forward's d_arg may be
+ * NULL; d_colidx / d_colidx_t / d_map_t may be NULL with nnz == 0).  n_feat == 0 or n_rows == 0 returns GNNX_OK and writes nothing;
+ * nnz == 0 still writes the per-row outputs.  A workspace that is NULL or smaller than gnnx_spmm_csr_reduce_workspace() bytes is
+ * GNNX_ERR_WORKSPACE with nothing written.  The workspace serves either call (the backward passes n_rows_t), holds nothing between
+ * calls and may sit at any address.  Its size is a function of (n_rows, nnz, n_feat) alone:
+ *   hubs = min(nnz / (S + 1), n_rows)   rows can be longer than S;   segs = nnz / S + hubs   bounds the sum of their ceil(d / S);
+ *   bytes = 256 + round_up_256( 4 * (16 + 2 * hubs + segs + 2 * segs * n_feat) )
+ * -- 16 counter words, the hub list with each hub's first segment slot, the hub of each slot, and per (slot, feature) the segment's
+ * value and position (forward) or its sum (backward).
+ *
+ * Kernels (gnnx_reduce.hip): rows of at most S entries take the lane-group shape of gnnx_spmm_csr_heads_f32 (4 .. 64 lanes per row, one
+ * 16-byte piece per lane, feature tiles in the grid's y); n_feat % 4 != 0, or an X / Y / arg / G / dX pointer or leading dimension
+ * that is not 16-byte aligned, takes scalar lanes with the same bits.  Longer rows are listed in the workspace by the row kernel (a
+ * counter atomic reserves slots, never an atomic on a value), a fixed grid strides over their segments and a combine kernel finishes
+ * each row: the better value wins and on equal values the smaller position (forward); ascending segment order (backward).
+ */
+enum { GNNX_REDUCE_MAX = 0, GNNX_REDUCE_MIN = 1 };
+int gnnx_spmm_csr_reduce_workspace(int32_t n_rows, int64_t nnz, int32_t n_feat, size_t *bytes);
+int gnnx_spmm_csr_reduce_f32(int op, int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t nnz, const int32_t *d_rowptr,
+                             const int32_t *d_colidx, const float *d_vals, const float *d_X, int64_t ldx, float *d_Y, int64_t ldy,
+                             int32_t *d_arg, int64_t lda, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_spmm_csr_reduce_bwd_f32(int32_t n_rows_t, int32_t n_cols_t, int32_t n_feat, int64_t nnz, const int32_t *d_rowptr_t,
+                                 const int32_t *d_colidx_t, const int32_t *d_map_t, const float *d_vals, const int32_t *d_arg,
+                                 int64_t lda, const float *d_G, int64_t ldg, float beta, float *d_dX, int64_t ldx, void *d_workspace,
+                                 size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */
