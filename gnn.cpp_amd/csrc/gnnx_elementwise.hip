@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void colsum_stage2(const float *partial, int32
     __syncthreads();
     if (part == 0 && f < n_feat) {
         float acc = ((red[c] + red[64 + c]) + red[128 + c]) + red[192 + c];
-        out[f] = beta != 0.f ? out[f] + acc : acc;
+        out[f] = beta != 0.f ? beta * out[f] + acc : acc;   // beta == 0 never reads out; beta == 1: the bits of out[f] + acc
     }
 }
 
@@ -306,10 +306,12 @@ __global__ __launch_bounds__(256) void csr_rowsum_kernel(const int32_t *rowptr, 
     }
 }
 
-__global__ __launch_bounds__(256) void transpose_kernel(const float *X, int64_t ldx, int64_t R, int64_t Cc, float *Y, int64_t ldy)
+__global__ __launch_bounds__(256) void transpose_kernel(const float *X, int64_t ldx, int64_t R, int64_t Cc, float *Y, int64_t ldy,
+                                                         uint32_t col_tiles)
 {
     __shared__ float tile[32][33];
-    int64_t c0 = (int64_t)blockIdx.x * 32, r0 = (int64_t)blockIdx.y * 32;
+    // all tiles on grid.x (up to 2^31 - 1 of them, row-major): neither a tall nor a wide matrix meets grid.y's limit of 65535
+    int64_t c0 = (int64_t)(blockIdx.x % col_tiles) * 32, r0 = (int64_t)(blockIdx.x / col_tiles) * 32;
     int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
     for (int k = ty; k < 32; k += 8)
         if (r0 + k < R && c0 + tx < Cc) tile[k][tx] = X[(r0 + k) * ldx + c0 + tx];
@@ -797,8 +799,10 @@ GNNX_API int gnnx_transpose_f32(const float *d_X, int64_t ldx, int64_t n_rows, i
     GNNX_REQUIRE(n_rows >= 0 && n_cols >= 0, GNNX_ERR_INVALID_ARG, "negative size");
     if (n_rows == 0 || n_cols == 0) return GNNX_OK;
     GNNX_REQUIRE(d_X && d_Y && d_X != d_Y && ldx >= n_cols && ldy >= n_rows, GNNX_ERR_INVALID_ARG, "bad pointers or ld");
-    dim3 grid((uint32_t)ceil_div(n_cols, 32), (uint32_t)ceil_div(n_rows, 32));
-    hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, as_stream(stream), d_X, ldx, n_rows, n_cols, d_Y, ldy);
+    const int64_t row_tiles = ceil_div(n_rows, 32), col_tiles = ceil_div(n_cols, 32);
+    GNNX_REQUIRE(row_tiles <= 2147483647 / col_tiles, GNNX_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles of 32 x 32");   // > 8 TB of floats
+    hipLaunchKernelGGL(transpose_kernel, dim3((uint32_t)(row_tiles * col_tiles)), dim3(256), 0, as_stream(stream), d_X, ldx, n_rows, n_cols,
+                       d_Y, ldy, (uint32_t)col_tiles);
     GNNX_LAUNCH_CHECK();
     return GNNX_OK;
 }

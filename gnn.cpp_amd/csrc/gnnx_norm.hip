@@ -558,12 +558,13 @@ GNNX_API int gnnx_bn_relu_bwd_quirk_f32(const float *d_X, int64_t ldx, const flo
                                         float *d_dbeta, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     GNNX_REQUIRE(d_mean && d_var, GNNX_ERR_INVALID_ARG, "the quirk form is about BatchNorm: statistics are required");
-    int rc = gnnx_bn_relu_bwd_sums_f32(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, eps, d_gamma, d_beta, relu, d_dgamma,
-                                       d_dbeta, d_workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    rc = bn_bwd_check(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, d_workspace, workspace_bytes);
+    // every refusal comes before the sums half writes dgamma / dbeta: a refused call leaves all outputs alone
+    int rc = bn_bwd_check(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, d_workspace, workspace_bytes);
     if (rc) return rc;
     GNNX_REQUIRE(d_dX && ldo >= n_feat, GNNX_ERR_INVALID_ARG, "null pointer or ld");
+    rc = gnnx_bn_relu_bwd_sums_f32(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, eps, d_gamma, d_beta, relu, d_dgamma,
+                                       d_dbeta, d_workspace, workspace_bytes, stream);
+    if (rc) return rc;
     if (bn_vec_ok(n_feat, d_X, ldx, d_Y, ldy, d_dY, ldd, d_dX, ldo))
         return launch_bn_apply_vec(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, eps, d_gamma, d_beta, relu, d_dgamma, d_dbeta,
                                    0.f, 1, d_dX, ldo, as_stream(stream));
@@ -581,9 +582,13 @@ GNNX_API int gnnx_bn_relu_bwd_f32(const float *d_X, int64_t ldx, const float *d_
                                   const float *d_gamma, const float *d_beta, int relu, float *d_dX, int64_t ldo, float *d_dgamma,
                                   float *d_dbeta, void *d_workspace, size_t workspace_bytes, void *stream)
 {
+    // the apply half's refusals first: the sums half writes dgamma / dbeta, and a refused call leaves all outputs alone
+    int rc = bn_bwd_check(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, d_workspace, workspace_bytes);
+    if (rc) return rc;
+    GNNX_REQUIRE(d_dX && ldo >= n_feat, GNNX_ERR_INVALID_ARG, "null pointer or ld");
     if (d_mean) {
-        int rc = gnnx_bn_relu_bwd_sums_f32(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, eps, d_gamma, d_beta, relu, d_dgamma,
-                                           d_dbeta, d_workspace, workspace_bytes, stream);
+        rc = gnnx_bn_relu_bwd_sums_f32(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, eps, d_gamma, d_beta, relu, d_dgamma,
+                                       d_dbeta, d_workspace, workspace_bytes, stream);
         if (rc) return rc;
     }
     return gnnx_bn_relu_bwd_apply_f32(d_X, ldx, d_Y, ldy, d_dY, ldd, n_rows, n_feat, d_mean, d_var, eps, d_gamma, d_beta, relu, d_dgamma,

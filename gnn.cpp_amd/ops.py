@@ -1057,11 +1057,11 @@ def bn_relu_fwd(X, mean=None, var=None, gamma=None, beta=None, eps=1e-5, relu=Tr
     return out
 
 
-def bn_relu_bwd(X, Y, dY, mean=None, var=None, gamma=None, eps=1e-5, relu=True, beta=None, reference_quirk=False):
+def bn_relu_bwd(X, Y, dY, mean=None, var=None, gamma=None, eps=1e-5, relu=True, beta=None, reference_quirk=False, out=None):
     """Y=None with relu: the forward output was never stored (fused forward); its sign is recomputed from X.
     reference_quirk: gnnx_bn_relu_bwd_quirk_f32, the gradient the REFERENCE's traversal delivers (statistics as constants)."""
     N, F = X.shape
-    dX = torch.empty_like(X)
+    dX = torch.empty_like(X) if out is None else out
     dgamma = torch.empty(F, dtype=torch.float32, device=X.device) if mean is not None else None
     dbeta = torch.empty(F, dtype=torch.float32, device=X.device) if mean is not None else None
     wsb = C.c_size_t(0)
@@ -1072,6 +1072,43 @@ def bn_relu_bwd(X, Y, dY, mean=None, var=None, gamma=None, eps=1e-5, relu=True, 
               _ptr(var), float(eps), _ptr(gamma), _ptr(beta), int(relu), _ptr(dX), _ld(dX), _ptr(dgamma), _ptr(dbeta), _ptr(ws),
               wsb.value, _stream())
     return dX, dgamma, dbeta
+
+
+def _bn_workspace(N, F, device):
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_bn_workspace", N, F, C.byref(wsb))
+    return _workspace(wsb.value, device, "bn"), wsb.value
+
+
+def bn_relu_bwd_sums(X, Y, dY, mean, var, gamma=None, eps=1e-5, relu=True, beta=None):
+    """gnnx_bn_relu_bwd_sums_f32: (dgamma, dbeta) over THIS call's rows -- the first half of bn_relu_bwd, which a sharded BatchNorm
+    all-reduces before the apply half."""
+    N, F = X.shape
+    dgamma = torch.empty(F, dtype=torch.float32, device=X.device)
+    dbeta = torch.empty(F, dtype=torch.float32, device=X.device)
+    ws, wsb = _bn_workspace(N, F, X.device)
+    capi.call("gnnx_bn_relu_bwd_sums_f32", _ptr(X), _ld(X), _ptr(Y), _ld(Y) if Y is not None else 0, _ptr(dY), _ld(dY), N, F, _ptr(mean),
+              _ptr(var), float(eps), _ptr(gamma), _ptr(beta), int(relu), _ptr(dgamma), _ptr(dbeta), _ptr(ws), wsb, _stream())
+    return dgamma, dbeta
+
+
+def bn_relu_bwd_apply(X, Y, dY, mean=None, var=None, gamma=None, dgamma=None, dbeta=None, n_total=None, eps=1e-5, relu=True, beta=None,
+                      out=None):
+    """gnnx_bn_relu_bwd_apply_f32: dX of this call's rows from the (global) sums and the (global) row count n_total."""
+    N, F = X.shape
+    dX = torch.empty((N, F), dtype=torch.float32, device=X.device) if out is None else out
+    ws, wsb = _bn_workspace(N, F, X.device)
+    capi.call("gnnx_bn_relu_bwd_apply_f32", _ptr(X), _ld(X), _ptr(Y), _ld(Y) if Y is not None else 0, _ptr(dY), _ld(dY), N, F, _ptr(mean),
+              _ptr(var), float(eps), _ptr(gamma), _ptr(beta), int(relu), _ptr(dgamma), _ptr(dbeta), int(N if n_total is None else n_total),
+              _ptr(dX), _ld(dX), _ptr(ws), wsb, _stream())
+    return dX
+
+
+def fill(x, value):
+    """gnnx_fill_f32 on a contiguous tensor."""
+    assert x.is_contiguous()
+    capi.call("gnnx_fill_f32", _ptr(x), x.numel(), float(value), _stream())
+    return x
 
 
 def rmat_edges(seed, n_nodes, n_edges, a=0.57, b=0.19, c=0.19, device="cuda", first_edge=0):

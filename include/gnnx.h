@@ -385,7 +385,8 @@ int gnnx_rowsum_f32(const float *d_X, int64_t ldx, int64_t n_rows, int32_t n_col
  *   csr_rowsum: out[i] = sum_j A_ij = rowptr[i+1]-rowptr[i] (vals == NULL) -- adj_mat->sum(-1,true), reference
  *               graph.cpp:178 -> functional.h:267-296, without the dense N x N matrix
  *   transpose : Y[c,r] = X[r,c]  (materialises a 2-D transpose only when a caller insists on the data;
- *               the GEMM never needs it).  X and Y must not alias. */
+ *               the GEMM never needs it).  X and Y must not alias.  Tall and wide matrices alike: all 32 x 32 tiles ride on grid.x;
+ *               more than 2^31 - 1 tiles (over 8 TB of floats) is GNNX_ERR_UNSUPPORTED. */
 int gnnx_fill_f32(float *d_x, int64_t n, float value, void *stream);
 int gnnx_pow_f32(const float *d_x, int64_t n, float exponent, float *d_y, void *stream);
 int gnnx_csr_rowsum_f32(const int32_t *d_rowptr, const float *d_vals, int32_t n_rows, float *d_out, void *stream);

@@ -177,3 +177,32 @@ def chunked_sum(fn, n, step=CHUNK):
         v = fn(r0, r1)
         acc = v if acc is None else acc + v
     return acc
+
+
+# ------------------------------------------------------------------ outputs between sentinels
+SENTINEL = -12345.0
+
+
+class Pitched:
+    """An [n, F] float32 device view on the leading dimension F + pad, `off` elements into its buffer, with two rows behind it;
+    everything that is not the view holds SENTINEL.  data None: the view holds the sentinel too (an output).  The checks run on the
+    device: the buffers can be large."""
+
+    def __init__(self, device, n, F, pad=0, off=0, data=None):
+        import torch
+        self.n, self.F, self.ld, self.off = n, F, F + pad, off
+        self.buf = torch.full((off + (n + 2) * self.ld,), SENTINEL, dtype=torch.float32, device=device)
+        self.view = self.buf[off:].view(n + 2, self.ld)[:n, :F]
+        if data is not None and n:
+            self.view.copy_(torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)).to(device))
+
+    def get(self):
+        return self.view.detach().cpu().numpy()
+
+    def assert_untouched_outside(self, what):
+        body = self.buf[self.off:].view(self.n + 2, self.ld)
+        ok = (self.buf[:self.off] == SENTINEL).all() & (body[:self.n, self.F:] == SENTINEL).all() & (body[self.n:] == SENTINEL).all()
+        assert bool(ok), f"{what}: wrote outside its [n, F] elements"
+
+    def assert_untouched(self, what):
+        assert bool((self.buf == SENTINEL).all()), f"{what}: the output was written"

@@ -970,6 +970,14 @@ def test_batchnorm_backward_vector_kernels_equal_the_scalar_ones(env, n, F):
                 assert torch.equal(a[0], b[0])   # no sums in the element formula
             else:           # same element formula on sums that differ by rounding
                 torch.testing.assert_close(a[0], b[0], rtol=1e-4, atol=1e-5 * max(1.0, float(b[0].abs().max())))
+    # Y = NULL redoes the forward's arithmetic for the sign (div_by_const in the 16-byte kernels, the IEEE division in the scalar
+    # ones): the same dX, dgamma and dbeta, bit for bit, as with the stored forward output, on either path
+    for quirk in (False, True):
+        for Xv, Yv, dYv in ((X, Y, dY), (odd(X), odd(Y), odd(dY))):
+            a = ops.bn_relu_bwd(Xv, Yv, dYv, mean, var, gamma, relu=True, beta=beta, reference_quirk=quirk)
+            b = ops.bn_relu_bwd(Xv, None, dYv, mean, var, gamma, relu=True, beta=beta, reference_quirk=quirk)
+            for k in range(3):
+                assert torch.equal(a[k], b[k]), (quirk, Xv.stride(0), ("dX", "dgamma", "dbeta")[k])
     # given the SAME sums the apply pass is bit-identical: the sharded halves take the sums as inputs
     shard_sums = ops.bn_relu_bwd(odd(X), None, odd(dY), mean, var, gamma, relu=True, beta=beta)
     import ctypes as C
