@@ -285,7 +285,8 @@ int gnnx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, float
                   void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* The backward GEMM of a stacked layer with its two followers fused into the epilogue:
- *   C[M,N] = (A[M,K] . B[K,N]) masked by the ReLU of the layer below: C[m][n] = 0 where Ymask[m][n] <= 0   (Mask::_backward,
+ *   C[M,N] = (A[M,K] . B[K,N]) masked by the ReLU of the layer below: C[m][n] is kept where Ymask[m][n] > 0 (IEEE: NaN drops, as
+ *            -0 and -inf do; a positive denormal and +inf keep) and is +0 elsewhere, whatever the product   (Mask::_backward,
  *            reference operation.h:557-562; Ymask = that layer's stored forward output)
  *   colsum[n] = sum_m C[m][n]                                                 (its bias gradient: Add::_backward -> sum_to_size,
  *            operation.h:114-128, tensor.h:618-638)

@@ -4,7 +4,10 @@ parity tests, and the chunked comparison helpers of the large-offset tests (test
 
 The chunked helpers work on torch tensors of any device and never index a tensor past CHUNK rows in one torch call: the
 EXPECTED side of a comparison is always built from row slices of at most CHUNK rows, whose element offsets stay far below
-2^31, so a reference does not depend on how torch itself indexes a tensor of more than 2^31 elements."""
+2^31, so a reference does not depend on how torch itself indexes a tensor of more than 2^31 elements.
+
+`embed` / `holds_fill` put an operand as a view inside a poisoned buffer (the contract tests of the dense products and of their fused
+epilogues)."""
 import os
 import sys
 
@@ -206,3 +209,30 @@ class Pitched:
 
     def assert_untouched(self, what):
         assert bool((self.buf == SENTINEL).all()), f"{what}: the output was written"
+
+
+# ------------------------------------------------------------------ operands inside poisoned buffers
+ROWS_BEFORE, ROWS_AFTER = 3, 2
+
+
+def embed(env, rows, cols, mode, fill):
+    """(buffer, view): a [rows, cols] view inside a buffer full of `fill`.  mode "a": column offset 4, pitch a multiple of 4 (the view
+    starts on the 16-byte grid); "o": odd pitch and a first element off the grid (column offset 1, or 2 where 1 would land on it): ld % 4 != 0 and a misaligned
+    base, the two conditions that switch every vector access off."""
+    torch = env["torch"]
+    if mode == "a":
+        left, pitch = 4, (cols + 8 + 3) // 4 * 4
+    else:
+        pitch = cols + 3 + (cols % 2)
+        left = 1 if (ROWS_BEFORE * pitch + 1) % 4 else 2         # the first element off the 16-byte grid as well as the pitch
+    buf = torch.full((rows + ROWS_BEFORE + ROWS_AFTER, pitch), fill, dtype=torch.float32, device=env["dev"])
+    view = buf[ROWS_BEFORE:ROWS_BEFORE + rows, left:left + cols]
+    assert pitch > cols + left and view.stride(0) == pitch
+    assert (pitch % 4 == 0) == (mode == "a")
+    if view.numel():
+        assert (view.data_ptr() % 16 == 0) == (mode == "a")
+    return buf, view
+
+
+def holds_fill(buf, fill):
+    return bool(buf.isnan().all()) if fill != fill else bool((buf == fill).all())

@@ -23,11 +23,10 @@ import numpy as np
 import pytest
 
 from tests import gemm_ref as gr
-from tests.helpers import assert_rows_close, fill_small_ints
+from tests.helpers import ROWS_AFTER, ROWS_BEFORE, assert_rows_close, embed, fill_small_ints, holds_fill  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROWS_BEFORE, ROWS_AFTER = 3, 2
 FILLS = {"nan": float("nan"), "inf": float("inf")}
 
 
@@ -40,30 +39,6 @@ def env():
     capi = importlib.import_module("gnncpp_amd.capi")
     assert capi.device_count() >= 1
     return dict(torch=torch, ops=ops, capi=capi, dev=torch.device("cuda:0"))
-
-
-# ------------------------------------------------------------------ operands inside poisoned buffers
-def embed(env, rows, cols, mode, fill):
-    """(buffer, view): a [rows, cols] view inside a buffer full of `fill`.  mode "a": column offset 4, pitch a multiple of 4 (the view
-    starts on the 16-byte grid); "o": odd pitch and a first element off the grid (column offset 1, or 2 where 1 would land on it): ld % 4 != 0 and a misaligned
-    base, the two conditions that switch every vector access off."""
-    torch = env["torch"]
-    if mode == "a":
-        left, pitch = 4, (cols + 8 + 3) // 4 * 4
-    else:
-        pitch = cols + 3 + (cols % 2)
-        left = 1 if (ROWS_BEFORE * pitch + 1) % 4 else 2         # the first element off the 16-byte grid as well as the pitch
-    buf = torch.full((rows + ROWS_BEFORE + ROWS_AFTER, pitch), fill, dtype=torch.float32, device=env["dev"])
-    view = buf[ROWS_BEFORE:ROWS_BEFORE + rows, left:left + cols]
-    assert pitch > cols + left and view.stride(0) == pitch
-    assert (pitch % 4 == 0) == (mode == "a")
-    if view.numel():
-        assert (view.data_ptr() % 16 == 0) == (mode == "a")
-    return buf, view
-
-
-def holds_fill(buf, fill):
-    return bool(buf.isnan().all()) if fill != fill else bool((buf == fill).all())
 
 
 def operand_shapes(case):
