@@ -208,6 +208,25 @@ class CsrGraph:
             self._map_t = csr_transpose_map(self.rowptr, self.colidx, self.rowptr_t, self.colidx_t)
         return self._map_t
 
+    def sample_neighbors(self, k, seed, transpose=True, norm=True):
+        """A new CsrGraph on the same vertices whose forward CSR keeps at most k stored neighbours per row (gnnx_csr_sample_neighbors:
+        uniform without replacement from `seed`, stored order kept; one seed per epoch).  The transposed CSR is built from the sampled
+        COO (column, row) with self loops and duplicates kept -- exactly the sampled entries; s / norm are computed on the sample; plans
+        are made the way this graph's were.  GnnxError on a relabelled graph, with attention_map's reasoning: its rows are not
+        ascending, and the transposed build would reorder them."""
+        if self.nid is not None:
+            raise capi.GnnxError(-7, "sample_neighbors", "a relabelled graph keeps each row in original-id order, not ascending: the "
+                                 "transposed CSR of a sample cannot be built on it (build the graph without relabel)")
+        rowptr, colidx, _, rowid = sample_neighbors(self.rowptr, self.colidx, k, seed, want_rowid=transpose)
+        g = CsrGraph(self.n, rowptr, colidx)
+        if transpose:
+            g.rowptr_t, g.colidx_t = self.csr_from_coo(colidx, rowid, self.n, flags=3)   # keep self loops and duplicates
+        if norm:
+            g.compute_norm()
+        if self.plan is not None:
+            g.make_plans(*self._plan_args)
+        return g
+
     def mask_in_row_order(self, mask):
         """A vertex-order mask ([n] bool / uint8, vertex v at position v) as uint8 in this graph's row order (vertex v at nid[v])."""
         if int(mask.numel()) != self.n:
@@ -364,6 +383,30 @@ def csr_extract_rows(rowptr, colidx, rows, vals=None, col_pos=None, n_cols=None,
     # (an empty result stays a view of its 1-element buffer, as csr_restrict's: the aggregation wants a device pointer)
     shrink = lambda t: None if t is None else (t[:m] if m else t[:0])  # noqa: E731
     return rowptr_o, shrink(colidx_o), shrink(vals_o)
+
+
+def sample_neighbors(rowptr, colidx, k, seed, want_pos=False, want_rowid=False):
+    """gnnx_csr_sample_neighbors: at most k entries per row, uniformly without replacement from `seed`, kept in stored order.
+    -> (rowptr', colidx', pos or None, rowid or None): pos[q] is the absolute position of kept entry q in the input CSR (a per-entry
+    array follows the sample as vals[pos]), rowid[q] its row ((colidx', rowid') is the COO of the transposed sample).  The same
+    (seed, k) gives the same sample on every run; use one seed per epoch or layer."""
+    n_rows, nnz, dev = int(rowptr.numel() - 1), int(colidx.numel()), rowptr.device
+    k = int(k)
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_csr_sample_workspace", n_rows, nnz, k, C.byref(wsb))     # refuses k < 1 and k > 64 before anything is sized
+    cap = int((rowptr[1:] - rowptr[:-1]).clamp(max=k).sum()) if n_rows else 0   # min(deg, k): the capacity is exact
+    rowptr_o = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
+    colidx_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    pos_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_pos else None
+    rowid_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_rowid else None
+    ws = _workspace(wsb.value, dev, "sample")
+    out_nnz = C.c_int64(0)
+    capi.call("gnnx_csr_sample_neighbors", n_rows, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, k, int(seed) & (2 ** 64 - 1), _ptr(rowptr_o),
+              _ptr(colidx_o), _ptr(pos_o), _ptr(rowid_o), cap, C.byref(out_nnz), _ptr(ws), ws.numel(), _stream())
+    m = out_nnz.value
+    # (an empty result stays a view of its 1-element buffer, as csr_restrict's: the aggregation wants a device pointer)
+    shrink = lambda t: None if t is None else (t[:m] if m else t[:0])  # noqa: E731
+    return rowptr_o, shrink(colidx_o), shrink(pos_o), shrink(rowid_o)
 
 
 class ReceptiveField:
@@ -1716,19 +1759,15 @@ class SageStack:
     kernels with existing bits, so a relabelled graph is fine.  aggr="max": M, arg = spmm_reduce(h) forward with arg kept per layer, and
     spmm_reduce_bwd through g.attention_map() backward -- which refuses a relabelled graph and one without a transposed CSR, with
     GatStack's GnnxError.  An empty row aggregates to zero: its output is h W_s^T + b.
-    forward / backward / step / train_step / evaluate / grad_buffer; every operation of forward and backward is a C-ABI call (the
+    forward / backward / step / train_step / evaluate / grad_buffer, and on_graph for steps on a sampled graph; every operation of forward and backward is a C-ABI call (the
     aggregation, the dense products, the bias add, the ReLU and its mask).  No atomics on any value; the same bits every run."""
 
     def __init__(self, g, dims, aggr="mean", seed=0, device="cuda"):
         if aggr not in ("mean", "max"):
             raise ValueError(f"aggr must be 'mean' or 'max', got {aggr!r}")
-        self.g, self.dims, self.aggr = g, list(dims), aggr
+        self.dims, self.aggr = list(dims), aggr
         L = len(dims) - 1
-        if aggr == "max":
-            self.map_t = g.attention_map()
-        else:
-            deg = (g.rowptr[1:] - g.rowptr[:-1]).cpu().to(torch.float32)      # the division on the host: IEEE, rounded once
-            self.inv_deg = torch.where(deg > 0, 1.0 / deg, torch.zeros_like(deg)).to(g.rowptr.device)
+        self._bind(g)
         self.W_s = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
         self.W_n = [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
         self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
@@ -1738,11 +1777,39 @@ class SageStack:
         self._saved = None
         self._buf = {}
 
+    def _bind(self, g):
+        """What the stack holds of the graph itself: the transpose map (max) or 1 / deg (mean)."""
+        self.g = g
+        if self.aggr == "max":
+            self.map_t = g.attention_map()
+        else:
+            deg = (g.rowptr[1:] - g.rowptr[:-1]).cpu().to(torch.float32)      # the division on the host: IEEE, rounded once
+            self.inv_deg = torch.where(deg > 0, 1.0 / deg, torch.zeros_like(deg)).to(g.rowptr.device)
+
+    def on_graph(self, g):
+        """This stack on another graph over the same vertices -- a sample of its neighbourhoods: a SageStack that SHARES this one's
+        parameters, gradients and scratch buffers (the same tensors: a step through either is a step of both) and has its own
+        inv_deg / map_t.  The training surface of neighbour sampling:
+            net.on_graph(g.sample_neighbors(k, seed=epoch)).train_step(X, target, rows, lr)
+        while net.evaluate(...) keeps running on the full graph."""
+        if g.n != self.g.n:
+            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
+        view = object.__new__(SageStack)
+        view.__dict__.update(self.__dict__)   # the parameter lists and the buffer table themselves, not copies
+        view._saved = None
+        view._bind(g)
+        return view
+
     def _tmp(self, key, shape, device, dtype=torch.float32):
         t = self._buf.get(key)
         if t is None or tuple(t.shape) != tuple(shape):
             t = self._buf[key] = torch.empty(shape, dtype=dtype, device=device)
         return t
+
+    # for which row list the gradient buffer is zero outside the rows the loss writes (_zeroed_grad_buffer): kept WITH the buffer, so
+    # that this stack and its on_graph views, which share the buffer, share that knowledge too
+    _grad_zeroed_for = property(lambda self: self._buf.get("zeroed_for"), lambda self, v: self._buf.__setitem__("zeroed_for", v))
+    _grad_set = property(lambda self: self._buf.get("zeroed_set"), lambda self, v: self._buf.__setitem__("zeroed_set", v))
 
     def grad_buffer(self):
         """Where the loss should write dlogits ([n, dims[-1]])."""

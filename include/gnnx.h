@@ -804,6 +804,64 @@ int gnnx_spmm_csr_reduce_bwd_f32(int32_t n_rows_t, int32_t n_cols_t, int32_t n_f
                                  int64_t lda, const float *d_G, int64_t ldg, float beta, float *d_dX, int64_t ldx, void *d_workspace,
                                  size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ neighbour sampling ---------- */
+/*
+ * A fixed fanout of k neighbours per vertex, drawn afresh from a seed: the other half of GraphSAGE (Hamilton et al. 2017).  The sample
+ * of a CSR is a CSR on the same rows and columns; everything downstream (gnnx_csr_from_coo for the transpose, gnnx_degree_norm_f32, the
+ * plans, gnnx_csr_transpose_map, every aggregation) takes it as it takes any other.  The contract is this comment, restated in NumPy by
+ * tests/sample_ref.py.
+ *
+ * Selection: uniformly without replacement.  Take row i with d = rowptr[i+1] - rowptr[i] entries, numbered j = 0 .. d-1 in stored order.
+ *   h_j = splitmix64( splitmix64(seed) ^ (((uint64)i << 32 | (uint64)j) * 0x9E3779B97F4A7C15) )   the finaliser of gnnx_rmat_edges /
+ *                                                                                                 gnnx_uniform_pm1_f32; the product
+ *                                                                                                 wraps in 64 bits
+ *   u_j = (h_j >> 32) << 32 | j                                                                   a 32-bit random key above the
+ *                                                                                                 entry's own offset
+ * The u_j of a row are pairwise different by construction: there is no tie and no tie rule; u is compared as ONE 64-bit value.  A row
+ * with d <= k keeps all its entries; a longer row keeps the k entries with the smallest u_j.  Kept entries stay in STORED ORDER
+ * (ascending j), the order every aggregation here sums in.  The key depends on the offset j, never on the column id: the selection
+ * reads no colidx.  A selection of the k smallest has no order: the result is a function of (seed, i, d, k) alone, however rows,
+ * segments and lanes are mapped.  A different seed gives an independent draw; a caller uses one seed per epoch or layer.
+ *
+ * Outputs:
+ *   d_rowptr_out    n_rows + 1 values, the exclusive scan of min(d_i, k).
+ *   d_colidx_out[q] the column of kept entry q.
+ *   d_pos_out[q]    (may be NULL) the ABSOLUTE position of kept entry q in the input CSR: a per-entry array (edge weights, attention
+ *                   values) follows the sample by a gather through it.
+ *   d_rowid_out[q]  (may be NULL) the row of kept entry q: with d_colidx_out the COO that gnnx_csr_from_coo takes to build the
+ *                   transposed CSR.
+ *   *nnz_out        (HOST) = rowptr_out[n_rows], valid on return: the call synchronises `stream`, as gnnx_csr_extract_rows does.
+ *
+ * Statuses.  GNNX_ERR_INVALID_ARG before any device call: negative sizes, k < 1, nnz >= 2^31, a null rowptr / rowptr_out / colidx_out /
+ * nnz_out, a null colidx with nnz > 0.  GNNX_ERR_UNSUPPORTED: k > 64 (one wavefront holds a row's running selection; fanouts in use
+ * are 5 to 50).  GNNX_ERR_WORKSPACE with nothing written: a workspace that is NULL or smaller than the query.  GNNX_ERR_INVALID_ARG
+ * with nothing written and *nnz_out still set: nnz_capacity (the capacity of d_colidx_out / d_pos_out / d_rowid_out in entries) is
+ * smaller than the result -- never a truncated CSR, the convention of gnnx_csr_extract_rows.  n_rows == 0 is a valid result:
+ * rowptr_out = [0].
+ *
+ * The CSR and nnz (= rowptr[n_rows]) are TRUSTED, as everywhere else.  The workspace holds nothing between calls, may sit at any
+ * address, and its size is a function of (n_rows, nnz, k) alone, with S = 4096:
+ *   tiles = n_rows / 1024 + 1          the scan of min(d, k) works on tiles of 1024 rows;
+ *   hubs = min(nnz / (S + 1), n_rows)  rows can be longer than S;   segs = nnz / S + hubs   bounds the sum of their ceil(d / S);
+ *   longs = min(nnz / 257, n_rows)     rows can be longer than 256;
+ *   bytes = 256 + round_up_256( 4 * (16 + tiles + 2 * hubs + segs + segs * k + longs) )
+ * -- 16 counter words, a sum per tile, the hub list with each hub's first segment slot, the hub of each slot, per slot the k
+ * candidates of the segment, and the list of long rows.  A counter atomic reserves a listed row's slots; no other atomic is used: the same bits on every run.
+ *
+ * Kernels (gnnx_sample.hip): min(d, k) is scanned into rowptr_out and the total copied to the host.  Rows of at most 256 entries take a
+ * lane group (4 .. 64 lanes by the mean row length, several short rows per wavefront): d <= k is a copy; otherwise a radix select on
+ * the 64-bit key from the top bit down, which stops as soon as as many candidates are left as are still needed (keys are recomputed
+ * per pass, never stored), and a ballot-prefix compaction that writes the kept entries in ascending j.  Longer rows are listed in the
+ * workspace by the row kernel: a row of at most S entries gets a wavefront of its own from a fixed grid that strides over the list (on a
+ * power-law graph these rows sit next to each other and would otherwise keep a few narrow lane groups busy long after the rest is
+ * done); for a row of more than S entries a fixed grid strides over its segments of S consecutive entries, each segment writes the offsets of
+ * its min(k, len) smallest keys to its slot, and a combine step per hub row picks the k smallest of the candidates and writes the row.
+ */
+int gnnx_csr_sample_workspace(int32_t n_rows, int64_t nnz, int32_t k, size_t *bytes);
+int gnnx_csr_sample_neighbors(int32_t n_rows, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, int32_t k, uint64_t seed,
+                              int32_t *d_rowptr_out, int32_t *d_colidx_out, int32_t *d_pos_out, int32_t *d_rowid_out,
+                              int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */
