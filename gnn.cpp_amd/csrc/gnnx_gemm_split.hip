@@ -6,9 +6,16 @@
 // x2 = bf16(x - x0 - x1); the two subtractions are exact in f32), and the product is accumulated in f32 from the six piece
 // products with i + j <= 2, smallest first:  a.b ~= a2.b0 + a1.b1 + a0.b2 + a1.b0 + a0.b1 + a0.b0  (each piece product is
 // exact in f32: 8 x 8 bits).  The three dropped terms are <= 3 * 2^-24 |a||b| per product, the size of one f32 rounding.
-// Measured against float64 (tests/test_gpu_parity.py::test_split_gemm_*) the error is within 2-3x of the f32 FMA chain's and
-// two orders of magnitude inside the 1e-5 parity bar -- but it is not the same arithmetic as the reference's f32 products,
-// so it stays behind its own entry point (gnnx_gemm_split_bf16_f32) and bench.py --split-gemm.
+// Measured against float64 on uniform data (tests/test_gpu_gemm_split.py, per element, in units of 2^-24 * sum_k |a_ik||b_kj|,
+// where the worst case of an f32 chain of K roundings is K): worst 1.16 at 129 x 128 x 16, 2.55 at 300 x 256 x 64, 3.32 at
+// 257 x 384 x 256, 2.45 at 130 x 512 x 1024 (rms 0.18 .. 0.34).  On integer operands whose piece products and partial sums are
+// all exact the result EQUALS the integer product, one family of operands per group of the six terms, at every tile geometry
+// (same file).  It is not the same arithmetic as the reference's f32 products, so it stays behind its own entry point
+// (gnnx_gemm_split_bf16_f32) and bench.py --split-gemm.
+//
+// Non-finite operands: split3 of +-Inf is (Inf, NaN, NaN) (x - x0 = Inf - Inf), of NaN three NaNs, so such an entry of A makes
+// its row of C non-finite and one of B its column, and nothing else (rows and columns never mix in an MFMA; lanes past M
+// compute on the clamped row M - 1 and never store).  A finite |x| >= 2^127 (2 - 2^-8) rounds to a bf16 Inf and behaves like one.
 //
 // Kernel: C[M,N] = A[M,K] . B  with A row-major f32 (K contiguous), B pre-split once into bf16 pieces [3][N][K]
 // (split_b_kernel; W is small).  128 x (64 NB) output tile per 256-thread workgroup (4 wavefronts as 2 x 2, each

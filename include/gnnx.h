@@ -311,10 +311,25 @@ int gnnx_gemm_bn_stats_f32(int64_t M, int64_t N, int64_t K, const float *d_X, in
 
 /* OPT-IN split-precision GEMM -- never the default, not used by any parity-graded call.  C[M,N] = A[M,K] . op(B)
  * (transB: B is [N,K], else [K,N]) on the bf16 matrix cores: every f32 operand is split exactly into three bf16 pieces
- * (8 + 8 + 8 significand bits) and the six piece products with i + j <= 2 are accumulated in f32, smallest first -- f32-level
- * accuracy (error within a small factor of the f32 FMA chain's, far inside the 1e-5 bar; tests compare both with float64) at
- * several times the f32 MFMA rate, but not the reference's arithmetic.  Needs K % 16 == 0, N % 128 == 0, A 16-byte aligned
- * with lda % 4 == 0; workspace gnnx_gemm_split_workspace() bytes (the split copy of B). */
+ * (8 + 8 + 8 significand bits: x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1), round to nearest even, subtractions in
+ * f32) and the six piece products with i + j <= 2 are accumulated in f32, smallest first, at several times the f32 MFMA rate.
+ * Not the reference's arithmetic.  What holds (tests/test_gpu_gemm_split.py):
+ *   - accuracy: per element |C - A.op(B)| <= K * 2^-24 * sum_k |a_ik||b_kj| against float64, the worst case of an f32 chain of
+ *     K roundings (measured worst: 1.2 .. 3.3 times 2^-24 * sum_k |a_ik||b_kj| for K = 16 .. 1024).  When every piece product
+ *     and every partial sum of them is exact in f32 (integers with sum_k |a_ik||b_kj| < 2^24) the result is the exact product.
+ *     A power-of-two scale of A or B scales C by the same factor, bit for bit, while operands, pieces, piece products and sums
+ *     stay in the normal range.  transB = 0 and transB = 1 on the transposed B give the same bits.
+ *   - range: finite operands below 2^127 * (2 - 2^-8).  A larger finite operand rounds to a bf16 infinity and behaves like one.
+ *     An Inf or NaN in A makes exactly its row of C non-finite, one in B exactly its column (the split of an Inf has NaN pieces:
+ *     whether such an element is NaN or Inf is unspecified); every other element is what it would be with that entry zero.
+ *     An operand below 2^-103 in magnitude can have a subnormal second or third piece and may lose it: whether the bf16 matrix
+ *     cores keep subnormal inputs has not been measured, and nothing is asserted about it.
+ *   - status, checked in this order: a negative size GNNX_ERR_INVALID_ARG; M == 0 or N == 0 GNNX_OK with nothing read or written
+ *     (null operands allowed); a null A, B or C GNNX_ERR_INVALID_ARG; K == 0, K % 16 != 0, N % 128 != 0, N or K >= 2^31, lda < K,
+ *     lda % 4 != 0 or A not 16-byte aligned GNNX_ERR_UNSUPPORTED; ldb < K (transB) / ldb < N (else) or ldc < N GNNX_ERR_SHAPE; a
+ *     workspace that is null, below gnnx_gemm_split_workspace() bytes (6 N K: the split copy of B) or not 16-byte aligned
+ *     GNNX_ERR_WORKSPACE.  A refused call writes nothing.  B and C need no more than their 4-byte alignment, ldb and ldc may
+ *     exceed their minimum by any amount; pad elements are neither read (A, B) nor written (C), nor are rows of C behind M. */
 int gnnx_gemm_split_workspace(int64_t M, int64_t N, int64_t K, size_t *bytes);
 int gnnx_gemm_split_bf16_f32(int transB, int64_t M, int64_t N, int64_t K, const float *d_A, int64_t lda, const float *d_B,
                              int64_t ldb, float *d_C, int64_t ldc, void *d_workspace, size_t workspace_bytes, void *stream);
