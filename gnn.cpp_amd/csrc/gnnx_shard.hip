@@ -1,7 +1,8 @@
 // 1-D vertex partition of the graph over the GPUs of one node and the halo plan of a shard, on the device
 // (SURVEY.md section 8(b) `gnnx_halo_plan`, 8(e)).  Integer streaming work, HBM-bound, deterministic; rocPRIM supplies
 // the sort / scan primitives.  The same logic, as torch index ops, is gnn.cpp_amd/shard.py (the two are compared array for
-// array in tests/test_gpu_sharded_loopback.py); the reference has no counterpart (single process, dense N x N).
+// array in tests/test_gpu_sharded_loopback.py, and every call here is held to the plain restatement tests/shard_ref.py by
+// tests/test_gpu_shard_plan.py); the reference has no counterpart (single process, dense N x N).
 //
 //   gnnx_vertex_weights      w[v] = out-degree + in-degree + row_weight          (cost model of a vertex)
 //   gnnx_partition_deal      stable sort by descending weight, snake deal to the ranks, rank-contiguous new ids
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(256) void scramble_nid_kernel(const int32_t *owner,
 GNNX_API int gnnx_partition_scramble(const int32_t *d_owner, int32_t n_nodes, int world, const int64_t *cuts, int32_t *d_nid, void *stream)
 {
     GNNX_REQUIRE(n_nodes >= 0 && world >= 1 && cuts && (n_nodes == 0 || d_nid), GNNX_ERR_INVALID_ARG, "bad arguments");
-    GNNX_REQUIRE(world == 1 || d_owner, GNNX_ERR_INVALID_ARG, "owner is required for more than one rank");
+    GNNX_REQUIRE(world == 1 || n_nodes == 0 || d_owner, GNNX_ERR_INVALID_ARG, "owner is required for more than one rank");
     if (n_nodes == 0) return GNNX_OK;
     for (int p = 0; p < world; p++)
         GNNX_REQUIRE(cuts[p] <= cuts[p + 1] && cuts[0] == 0 && cuts[world] == n_nodes, GNNX_ERR_INVALID_ARG, "cuts are not a partition of [0, n)");
@@ -491,7 +492,8 @@ GNNX_API int gnnx_halo_exchange_rows_f32(const gnnx_halo_plan *plan, gnnx_comm *
     GNNX_REQUIRE(d_buf && (plan->n_send == 0 || d_send_buf), GNNX_ERR_INVALID_ARG, "null buffer");
     if (plan->n_send) {
         // rows of 16-byte pieces: the pack from the producer's side (every local row read once); else the gather by the send list
-        const bool vec = plan->d_slots && n_feat % 4 == 0 && ldb % 4 == 0 && n_feat / 4 <= 256 && 256 % (n_feat / 4) == 0 &&
+        // (n_feat == 0: nothing to pack, and no n_feat / 4 to divide by; the call still joins the collective with zero bytes)
+        const bool vec = n_feat > 0 && plan->d_slots && n_feat % 4 == 0 && ldb % 4 == 0 && n_feat / 4 <= 256 && 256 % (n_feat / 4) == 0 &&
                          (reinterpret_cast<uintptr_t>(d_buf) & 15u) == 0 && (reinterpret_cast<uintptr_t>(d_send_buf) & 15u) == 0;
         int st = vec ? gnnx_rows_to_slots_f32(d_buf, ldb, plan->n_local, n_feat, plan->d_slots, d_send_buf, n_feat, nullptr, 0.f, nullptr, 0, stream)
                      : gnnx_gather_rows_f32(d_buf, ldb, plan->d_send_idx, plan->n_send, n_feat, d_send_buf, n_feat, stream);
@@ -501,8 +503,8 @@ GNNX_API int gnnx_halo_exchange_rows_f32(const gnnx_halo_plan *plan, gnnx_comm *
                                   stream);
 }
 
-// The plan's slot table (gnnx_rows_to_slots_f32's [n_local][8] inverse of the send list; NULL: a world of more than 8 ranks, or no send
-// list yet) for producers that pack while they produce (gnnx_gemm_nt_rows_to_slots_f32), and the exchange of a send buffer such a
+// The plan's slot table (gnnx_rows_to_slots_f32's [n_local][8] inverse of the send list; NULL: some local row has more than 7 slots,
+// i.e. more than 7 peers read it, or there is no send list yet, or it is empty) for producers that pack while they produce (gnnx_gemm_nt_rows_to_slots_f32), and the exchange of a send buffer such a
 // producer has filled.
 GNNX_API int gnnx_halo_plan_slot_table(const gnnx_halo_plan *plan, const int32_t **d_slots)
 {

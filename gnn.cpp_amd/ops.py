@@ -944,7 +944,7 @@ SLOTS_PER_ROW = 8   # gnnx_rows_to_slots_f32: a row goes to at most world - 1 <=
 
 def slot_table(send_idx, n_rows):
     """[n_rows, 8] int32 for rows_to_slots: row r's positions in the send buffer (send_idx[slot] == r), ascending, packed to the
-    front, -1 behind.  None when some row has more than 7 slots (a world of more than 8 ranks: use the gather pack)."""
+    front, -1 behind.  None when some row has more than 7 slots (more than 7 peers read it: use the gather pack)."""
     dev = send_idx.device
     table = torch.full((max(int(n_rows), 1), SLOTS_PER_ROW), -1, dtype=torch.int32, device=dev)
     if int(send_idx.numel()) == 0:

@@ -20,6 +20,31 @@ def comm_destroy(h):
     capi.lib().gnnx_comm_destroy(h)
 
 
+def vertex_weights(src, dst, n_nodes, row_weight=1):
+    """gnnx_vertex_weights: int32 [n_nodes], out-degree + in-degree + row_weight."""
+    w = torch.empty(n_nodes, dtype=torch.int32, device=src.device)
+    capi.call("gnnx_vertex_weights", ops._ptr(src), ops._ptr(dst), int(src.numel()), n_nodes, int(row_weight), ops._ptr(w), ops._stream())
+    return w
+
+
+def partition_deal(weight, world):
+    """gnnx_partition_deal: (owner int32 [n], nid int32 [n] in ascending original id inside a rank, cuts list [world + 1])."""
+    n_nodes = int(weight.numel())
+    owner = torch.empty(n_nodes, dtype=torch.int32, device=weight.device)
+    nid = torch.empty(n_nodes, dtype=torch.int32, device=weight.device)
+    ccuts = (C.c_int64 * (world + 1))()
+    capi.call("gnnx_partition_deal", ops._ptr(weight), n_nodes, world, ops._ptr(owner), ops._ptr(nid), ccuts, ops._stream())
+    return owner, nid, list(ccuts)
+
+
+def partition_scramble(owner, nid, cuts):
+    """gnnx_partition_scramble, in place on nid (returned)."""
+    world = len(cuts) - 1
+    ccuts = (C.c_int64 * (world + 1))(*cuts)
+    capi.call("gnnx_partition_scramble", ops._ptr(owner), int(nid.numel()), world, ccuts, ops._ptr(nid), ops._stream())
+    return nid
+
+
 class NativeHaloSide:
     """One direction of the exchange behind the C-ABI: shard CSR ([local | halo] columns) + gnnx_halo_plan."""
 
@@ -75,6 +100,15 @@ class NativeHaloSide:
         capi.call("gnnx_halo_plan_exchange_requests", self.h, comm, ops._stream())
         self.refresh()
 
+    def set_send_list(self, want, counts):
+        """gnnx_halo_plan_set_send_list from ids the caller moved itself: want = the peers' requests (int32 new ids on the device,
+        peer-major), counts = rows per peer."""
+        cc = (C.c_int64 * self.world)(*counts)
+        try:
+            capi.call("gnnx_halo_plan_set_send_list", self.h, ops._ptr(want), cc, ops._stream())
+        finally:
+            self.refresh()   # a refused list may have replaced the old one already
+
     def exchange_rows(self, comm, buf, send_buf):
         capi.call("gnnx_halo_exchange_rows_f32", self.h, comm, ops._ptr(buf), buf.stride(0), buf.shape[1], ops._ptr(send_buf), ops._stream())
 
@@ -101,16 +135,9 @@ class NativeShardPlan:
     """Partition + both halo plans of rank `rank`, every step a C-ABI call."""
 
     def __init__(self, src, dst, n_nodes, rank, world, comm, row_weight=1):
-        dev = src.device
-        E = int(src.numel())
-        w = torch.empty(n_nodes, dtype=torch.int32, device=dev)
-        capi.call("gnnx_vertex_weights", ops._ptr(src), ops._ptr(dst), E, n_nodes, int(row_weight), ops._ptr(w), ops._stream())
-        self.owner = torch.empty(n_nodes, dtype=torch.int32, device=dev)
-        self.nid = torch.empty(n_nodes, dtype=torch.int32, device=dev)
-        ccuts = (C.c_int64 * (world + 1))()
-        capi.call("gnnx_partition_deal", ops._ptr(w), n_nodes, world, ops._ptr(self.owner), ops._ptr(self.nid), ccuts, ops._stream())
-        capi.call("gnnx_partition_scramble", ops._ptr(self.owner), n_nodes, world, ccuts, ops._ptr(self.nid), ops._stream())
-        self.cuts = list(ccuts)
+        w = vertex_weights(src, dst, n_nodes, row_weight)
+        self.owner, self.nid, self.cuts = partition_deal(w, world)
+        partition_scramble(self.owner, self.nid, self.cuts)
         self.rank, self.world = rank, world
         self.lo, self.hi = self.cuts[rank], self.cuts[rank + 1]
         self.n_local = self.hi - self.lo

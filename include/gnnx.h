@@ -930,7 +930,8 @@ int gnnx_allreduce_sum_f32(gnnx_comm *comm, float *d_buf, int64_t n, void *strea
  *                           generators (R-MAT) put the hubs on the ids with few one-bits, i.e. feature rows whose addresses have few
  *                           one-bits: the address bits that select the memory channel / cache slice are mostly zero and the hottest rows pile onto a few
  *                           (10 M / 100 M, F = 256: aggregation 19.0 -> 13.7 ms once the labels are scrambled).  world == 1 with
- *                           d_nid = 0..n-1 gives the single-GPU relabelling.  Row contents and summation order are untouched
+ *                           d_nid = 0..n-1 gives the single-GPU relabelling (d_owner may be NULL for one rank, and every
+ *                           device pointer when n_nodes == 0).  Row contents and summation order are untouched
  *                           (see above): every vertex's result has the same bits, stored at row nid[v].  Synchronises.
  *   gnnx_shard_select_edges the edges rank `rank` owns (owner[src] == rank; transpose != 0: owner[dst] == rank, roles swapped),
  *                           self loops dropped on ORIGINAL ids: d_rows = local row id (nid - lo), d_cols = ORIGINAL column id;
@@ -967,8 +968,9 @@ int gnnx_halo_plan_exchange_requests(gnnx_halo_plan *plan, gnnx_comm *comm, void
 int gnnx_halo_exchange_rows_f32(const gnnx_halo_plan *plan, gnnx_comm *comm, float *d_buf, int64_t ldb, int32_t n_feat,
                                 float *d_send_buf, void *stream);
 /* A producer that packs while it produces (gnnx_gemm_nt_rows_to_slots_f32: the transform's epilogue; gnnx_rows_to_slots_f32 with the
- * column sums: the upstream gradient's dbias pass) takes the plan's slot table ([n_local][8]; NULL when the plan has none: more than
- * 8 ranks, or no rows to send) and hands the filled send buffer ([n_send][n_feat], dense) to gnnx_halo_exchange_packed_f32 -- the
+ * column sums: the upstream gradient's dbias pass) takes the plan's slot table ([n_local][8]: a row's slots ascending, packed to the front,
+ * -1 behind them; NULL when the plan has none: some local row has more than 7 slots, i.e. more than 7 peers read it -- whatever the
+ * number of ranks --, or no send list yet, or no rows to send) and hands the filled send buffer ([n_send][n_feat], dense) to gnnx_halo_exchange_packed_f32 -- the
  * exchange step of gnnx_halo_exchange_rows_f32 without its pack. */
 int gnnx_halo_plan_slot_table(const gnnx_halo_plan *plan, const int32_t **d_slots);
 int gnnx_halo_exchange_packed_f32(const gnnx_halo_plan *plan, gnnx_comm *comm, float *d_buf, int64_t ldb, int32_t n_feat,

@@ -190,6 +190,7 @@ def test_cabi_plan_equals_shard_py_plan_and_drives_a_step(world):
     ops = importlib.import_module("gnncpp_amd.ops")
     shard = importlib.import_module("gnncpp_amd.shard")
     sn = importlib.import_module("gnncpp_amd.shard_native")
+    capi = importlib.import_module("gnncpp_amd.capi")
     dev = torch.device("cuda:0")
     n, e, F, seed = 60_000, 700_000, 32, 9
     src, dst = ops.rmat_edges(seed, n, e, device=dev)
@@ -231,6 +232,13 @@ def test_cabi_plan_equals_shard_py_plan_and_drives_a_step(world):
             assert torch.equal(Hext[nl:], H[pt.orig_ids(pt.fwd.halo)])
             out = ops.spmm(pn.fwd.rowptr, pn.fwd.colidx, Hext, rowscale=norm, n_rows=nl)
             assert torch.equal(out, out_ref[v]), "forward aggregation over the C-ABI plan is not bit-identical"
+            # a zero-width exchange (n_feat = 0 on ldb = 0, which the call accepts; a torch (N, 0) tensor reports stride 1, hence the
+            # plain call) joins the collective with zero bytes and writes nothing -- with a slot table in the plan it used to divide by
+            # n_feat / 4 on the host
+            kept = Hext.clone()
+            capi.call("gnnx_halo_exchange_rows_f32", pn.fwd.h, comms[rank], ops._ptr(Hext), 0, 0, ops._ptr(sbuf), ops._stream())
+            torch.cuda.synchronize()
+            assert torch.equal(Hext, kept), "a zero-width exchange wrote to the [local | halo] buffer"
             # the plan's own slot table is the inverse of its send list, and a transform that packs in its epilogue + the exchange of
             # the packed buffer (gnnx_halo_plan_slot_table / gnnx_gemm_nt_rows_to_slots_f32 / gnnx_halo_exchange_packed_f32: what
             # GCNConv::forward_sharded runs) fills the same [local | halo] buffer as product -> exchange with its own pack
@@ -260,7 +268,6 @@ def test_cabi_plan_equals_shard_py_plan_and_drives_a_step(world):
             assert torch.equal(dH, dH_ref[v]), "backward aggregation over the C-ABI plan is not bit-identical"
             # the small all-reduce of the local transport: every rank ends with the same rank-ordered sum
             t = torch.full((1000,), float(rank + 1), dtype=torch.float32, device=dev)
-            capi = importlib.import_module("gnncpp_amd.capi")
             capi.call("gnnx_allreduce_sum_f32", comms[rank], ops._ptr(t), t.numel(), ops._stream())
             assert bool((t == world * (world + 1) / 2).all())
             torch.cuda.synchronize()
