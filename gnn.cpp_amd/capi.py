@@ -156,6 +156,9 @@ _SIGS = {
     "gnnx_spmm_csr_reduce_workspace": [_i32, _i64, _i32, C.POINTER(_sz)],
     "gnnx_spmm_csr_reduce_f32": [C.c_int, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
     "gnnx_spmm_csr_reduce_bwd_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_segment_pool_workspace": [_i32, _i32, _i32, C.POINTER(_sz)],
+    "gnnx_segment_pool_f32": [C.c_int, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_segment_pool_bwd_f32": [C.c_int, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp],
     "gnnx_mask_to_rows_workspace": [_i64, C.POINTER(_sz)],
     "gnnx_mask_to_rows": [_vp, _i64, _vp, C.POINTER(_i32), _vp, _sz, _vp],
     "gnnx_csr_restrict_workspace": [_i32, _i64, C.POINTER(_sz)],

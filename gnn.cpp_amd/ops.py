@@ -1887,3 +1887,255 @@ class SageStack:
     def evaluate(self, X, target, rows):
         """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows))."""
         return _loss_and_accuracy(self.forward(X), target, rows)
+
+
+# ---- graph readout: segment pooling, graph batches, a classifier head (include/gnnx.h "graph readout") ----------------------------------
+POOL_OPS = {"sum": 0, "mean": 1, "max": 2}   # GNNX_POOL_SUM / GNNX_POOL_MEAN / GNNX_POOL_MAX
+POOL_CHUNK = 256                             # GNNX_POOL_CHUNK
+
+
+def _pool_sizes(segptr, where):
+    if segptr.dtype != torch.int32 or segptr.dim() != 1 or not segptr.is_contiguous() or segptr.numel() < 1:
+        raise capi.GnnxError(-2, where, "segptr must be a contiguous int32 vector of n_seg + 1 entries")
+    return int(segptr.numel()) - 1
+
+
+def _pool_matrix(t, shape, dtype, what, where):
+    """t must be a 2-D `dtype` matrix of `shape` (None: any) whose rows are contiguous: its pointer and row stride go to the kernel as
+    they are."""
+    if t.dim() != 2 or t.dtype != dtype or t.stride(1) != 1 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "" if shape is None else f" {tuple(shape)}"
+        raise capi.GnnxError(-2, where, f"{what} must be a 2-D {dtype} matrix{want} with unit inner stride, got {t.dtype} "
+                                        f"{tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def segment_pool(segptr, X, op="sum", out=None, arg_out=None, want_arg=True):
+    """gnnx_segment_pool_f32: (Y, arg) with Y[b] the sum / mean / max of the rows [segptr[b], segptr[b+1]) of X and, for op="max" with
+    want_arg, arg[b, f] = the first row of the segment that attains the maximum (int32, an absolute row of X; -1 for an empty segment);
+    arg is None otherwise.  An empty segment gives +0.  The sum has the order of include/gnnx.h "graph readout": a segment's bits depend on
+    its own rows alone.  X, out and arg_out may be strided views."""
+    if op not in POOL_OPS:
+        raise capi.GnnxError(-1, "segment_pool", f"op must be 'sum', 'mean' or 'max', got {op!r}")
+    n_seg = _pool_sizes(segptr, "segment_pool")
+    n_rows, F = _pool_matrix(X, None, torch.float32, "X", "segment_pool").shape
+    if out is None:
+        out = torch.empty((n_seg, F), dtype=torch.float32, device=X.device)
+    arg = None
+    if op == "max" and want_arg:
+        arg = torch.empty((n_seg, F), dtype=torch.int32, device=X.device) if arg_out is None else arg_out
+        _pool_matrix(arg, (n_seg, F), torch.int32, "arg_out", "segment_pool")
+    _pool_matrix(out, (n_seg, F), torch.float32, "out", "segment_pool")
+    wsb = C.c_size_t(0)
+    capi.call("gnnx_segment_pool_workspace", n_seg, n_rows, F, C.byref(wsb))
+    ws = _workspace(wsb.value, X.device, "pool")
+    capi.call("gnnx_segment_pool_f32", POOL_OPS[op], n_seg, n_rows, F, _ptr(segptr), _ptr(X) if X.numel() else None, _ld(X), _ptr(out), _ld(out),
+              _ptr(arg), _ld(arg) if arg is not None else 0, _ptr(ws), wsb.value, _stream())
+    return out, arg
+
+
+def segment_pool_bwd(segptr, G, op, arg=None, out=None, beta=0.0, n_rows=None):
+    """gnnx_segment_pool_bwd_f32: dX = beta * dX + the gradient of segment_pool with respect to X: row i of segment b receives G[b] (sum),
+    G[b] / len (mean) or G[b, f] where arg[b, f] == i (max; arg from the forward).  Every row of dX is written; beta = 0 never reads it.
+    n_rows (an addition to the call's documented arguments, only read without `out`): the rows of the dX to allocate; without it they
+    are segptr's last entry, which costs a device read and a synchronisation."""
+    if op not in POOL_OPS:
+        raise capi.GnnxError(-1, "segment_pool_bwd", f"op must be 'sum', 'mean' or 'max', got {op!r}")
+    n_seg = _pool_sizes(segptr, "segment_pool_bwd")
+    if G.dim() != 2 or int(G.shape[0]) != n_seg:
+        raise capi.GnnxError(-2, "segment_pool_bwd", f"G must be [{n_seg}, F], got {tuple(G.shape)}")
+    F = int(_pool_matrix(G, None, torch.float32, "G", "segment_pool_bwd").shape[1])
+    if op == "max":
+        if arg is None:
+            raise capi.GnnxError(-2, "segment_pool_bwd", f"op 'max' needs the forward's int32 arg {(n_seg, F)}")
+        _pool_matrix(arg, (n_seg, F), torch.int32, "arg", "segment_pool_bwd")
+    if out is None:
+        if beta != 0.0:
+            raise capi.GnnxError(-1, "segment_pool_bwd", "beta = 1 needs the matrix to add to (out)")
+        if n_rows is None:
+            n_rows = int(segptr[-1])
+        out = torch.empty((n_rows, F), dtype=torch.float32, device=G.device)
+    _pool_matrix(out, None, torch.float32, "out", "segment_pool_bwd")
+    n_rows = int(out.shape[0])
+    if int(out.shape[1]) != F:
+        raise capi.GnnxError(-2, "segment_pool_bwd", f"out must be [n_rows, {F}], got {tuple(out.shape)}")
+    use_arg = arg if op == "max" else None
+    capi.call("gnnx_segment_pool_bwd_f32", POOL_OPS[op], n_seg, n_rows, F, _ptr(segptr), _ptr(use_arg), _ld(use_arg) if use_arg is not None else 0,
+              _ptr(G), _ld(G), float(beta), _ptr(out) if out.numel() else None, _ld(out), _stream())
+    return out
+
+
+class GraphBatch(CsrGraph):
+    """A batch of B small graphs as ONE block-diagonal CsrGraph that every stack takes unchanged: graph k owns the consecutive vertices
+    graph_ptr[k] .. graph_ptr[k+1] - 1 and no edge joins two graphs.  graph_ptr: device int32 [B + 1] (segment_pool's segptr); n_graphs;
+    batch: int32 [n], the graph of each vertex (built when first asked for).  There is no relabelling: it would break the contiguity of
+    a graph's vertices that the readout rests on."""
+
+    graph_ptr = None
+    n_graphs = 0
+    _batch = None
+
+    @classmethod
+    def from_graphs(cls, graphs, transpose=True, norm=True):
+        """graphs: [(src, dst, n_i), ...] with device int32 edge lists on the graph's own vertex ids 0 .. n_i - 1."""
+        if not graphs:
+            raise ValueError("a batch needs at least one graph")
+        ptr = [0]
+        for _, _, n_i in graphs:
+            if int(n_i) < 0:
+                raise ValueError("negative vertex count")
+            ptr.append(ptr[-1] + int(n_i))
+        if ptr[-1] >= 2 ** 31:
+            raise ValueError("the batch does not fit int32 vertex ids")
+        src = torch.cat([s.to(torch.int32) + off for (s, _, _), off in zip(graphs, ptr)])
+        dst = torch.cat([d.to(torch.int32) + off for (_, d, _), off in zip(graphs, ptr)])
+        # ONE check of the concatenated list: both endpoints of every edge lie in the vertex range of the graph that listed the edge
+        dev = src.device
+        graph_ptr = torch.tensor(ptr, dtype=torch.int64, device=dev)
+        owner = torch.repeat_interleave(torch.arange(len(graphs), device=dev), torch.tensor([int(s.numel()) for s, _, _ in graphs], device=dev))
+        lo, hi = graph_ptr[owner], graph_ptr[owner + 1]
+        if src.numel() != dst.numel() or bool(((src < lo) | (src >= hi) | (dst < lo) | (dst >= hi)).any()):
+            raise ValueError("an edge names a vertex outside its graph")
+        return cls._build(src, dst, graph_ptr.to(torch.int32), ptr[-1], transpose, norm)
+
+    @classmethod
+    def from_coo_batched(cls, src, dst, graph_ptr, transpose=True, norm=True):
+        """An already concatenated edge list on the batch's vertex ids.  ValueError if graph_ptr is not non-decreasing from 0, if an edge
+        names a vertex outside the batch or if an edge joins two graphs."""
+        ptr = torch.as_tensor(graph_ptr).to(torch.int64).cpu().reshape(-1)
+        if ptr.numel() < 2 or int(ptr[0]) != 0 or bool((ptr[1:] < ptr[:-1]).any()):
+            raise ValueError("graph_ptr must be non-decreasing from 0, with one entry more than there are graphs")
+        n = int(ptr[-1])
+        if n >= 2 ** 31:
+            raise ValueError("the batch does not fit int32 vertex ids")
+        if src.numel():
+            if int(min(src.min(), dst.min())) < 0 or int(max(src.max(), dst.max())) >= n:
+                raise ValueError("an edge names a vertex outside the batch")
+            ends = ptr[1:].to(src.device)
+            if bool((torch.bucketize(src.long(), ends, right=True) != torch.bucketize(dst.long(), ends, right=True)).any()):
+                raise ValueError("an edge joins two graphs of the batch")
+        return cls._build(src.to(torch.int32), dst.to(torch.int32), ptr.to(torch.int32).to(src.device), n, transpose, norm)
+
+    @classmethod
+    def _build(cls, src, dst, graph_ptr, n, transpose, norm):
+        g = cls.from_coo(src, dst, n, transpose=transpose, norm=norm, relabel=None)
+        g.graph_ptr = graph_ptr.contiguous()
+        g.n_graphs = int(graph_ptr.numel()) - 1
+        return g
+
+    @property
+    def batch(self):
+        if self._batch is None:
+            counts = (self.graph_ptr[1:] - self.graph_ptr[:-1]).long()
+            ids = torch.arange(self.n_graphs, dtype=torch.int32, device=self.graph_ptr.device)
+            self._batch = torch.repeat_interleave(ids, counts)
+        return self._batch
+
+
+def _stack_on_graph(net, g):
+    """`net` (GcnStack, GatStack or SageStack) on ANOTHER graph, of any vertex count: a stack of the same class that SHARES the
+    parameter and gradient tensors (a step through either is a step of both) and derives from g what the class's __init__ / _bind
+    derives from its graph -- g itself, SageStack's inv_deg / map_t, GatStack's map_t, GcnStack's gather_pitch -- with no saved
+    activations, no checked input and scratch buffers of its own (they are shaped by the vertex count)."""
+    view = object.__new__(type(net))
+    view.__dict__.update(net.__dict__)
+    view._saved = None
+    view._buf = {}
+    if isinstance(net, SageStack):
+        view._bind(g)
+    elif isinstance(net, GatStack):
+        view.g = g
+        view.map_t = g.attention_map()
+    elif isinstance(net, GcnStack):
+        view.g = g
+        view.gather_pitch = bool(g.plan is not None and g.plan_t is not None and (g.plan.hub_ids_structured() or g.plan_t.hub_ids_structured()))
+        view._checked_input = None
+        view._grad_zeroed_for = view._grad_set = None
+    else:
+        raise TypeError(f"GcnStack, GatStack or SageStack expected, got {type(net).__name__}")
+    return view
+
+
+class GraphClassifier:
+    """One answer per GRAPH of a GraphBatch: a readout and a linear head over any of the three stacks,
+        Z = segment_pool(net.forward(X), pool) [B, dims[-1]];   logits = Z W_c^T + b_c   [B, n_classes],
+    trained through the readout.  The surface of the stacks: forward / backward / step / train_step / evaluate, and on_batch for an epoch
+    over mini-batches of any size.  Every operation is a C-ABI call: the stack's own, segment_pool, gemm, bias_add, softmax_ce (db_c from
+    the loss kernel), segment_pool_bwd into net.grad_buffer(), sgd_step.  No atomics on any value; the same bits every run."""
+
+    def __init__(self, net, batch, n_classes, pool="mean", seed=0):
+        if pool not in POOL_OPS:
+            raise ValueError(f"pool must be 'sum', 'mean' or 'max', got {pool!r}")
+        if not isinstance(batch, GraphBatch):
+            raise TypeError("batch must be a GraphBatch")
+        self.net = net if net.g is batch else _stack_on_graph(net, batch)
+        self.batch, self.pool, self.n_classes = batch, pool, int(n_classes)
+        d = self.net.dims[-1]
+        dev = batch.graph_ptr.device
+        self.W_c = uniform_pm1(seed + 1000, (self.n_classes, d), scale=d ** -0.5, device=dev)
+        self.b_c = torch.zeros(self.n_classes, dtype=torch.float32, device=dev)
+        self.dW_c = torch.zeros_like(self.W_c)
+        self.db_c = torch.zeros_like(self.b_c)
+        self._saved = None
+        self._buf = {}
+
+    def on_batch(self, batch):
+        """This classifier on another GraphBatch, of ANY vertex and graph count: it shares W_c, b_c, their gradients and the stack's
+        parameters and gradients (the same tensors), and binds the stack to the new graph:
+            for b in batches: clf.on_batch(b).train_step(X_b, target_b, lr)"""
+        if not isinstance(batch, GraphBatch):
+            raise TypeError("batch must be a GraphBatch")
+        view = object.__new__(GraphClassifier)
+        view.__dict__.update(self.__dict__)
+        view.net = _stack_on_graph(self.net, batch)
+        view.batch = batch
+        view._saved = None
+        view._buf = {}
+        return view
+
+    def _tmp(self, key, shape, dtype=torch.float32):
+        t = self._buf.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._buf[key] = torch.empty(shape, dtype=dtype, device=self.W_c.device)
+        return t
+
+    def forward(self, X):
+        """logits [B, n_classes]; the pooled Z [B, dims[-1]] is kept (self.Z) with the readout's arg for backward."""
+        B, d = self.batch.n_graphs, self.net.dims[-1]
+        H = self.net.forward(X)
+        Z, arg = segment_pool(self.batch.graph_ptr, H, self.pool, out=self._tmp("Z", (B, d)),
+                              arg_out=self._tmp("arg", (B, d), torch.int32) if self.pool == "max" else None)
+        logits = bias_add(gemm(Z, self.W_c, transB=True, out=self._tmp("ZW", (B, self.n_classes))), self.b_c, out=self._tmp("logits", (B, self.n_classes)))
+        self._saved = (Z, arg)
+        self.Z = Z
+        return logits
+
+    def backward(self, dlogits, have_bias_grad=False):
+        """dW_c, db_c and every gradient of the stack from dlogits = dL/dlogits.  have_bias_grad: db_c was already written by the loss
+        kernel (softmax_ce(..., colsum_out=clf.db_c))."""
+        Z, arg = self._saved
+        if not have_bias_grad:
+            colsum(dlogits, out=self.db_c)
+        gemm(dlogits, Z, transA=True, out=self.dW_c)
+        dZ = gemm(dlogits, self.W_c, out=self._tmp("dZ", tuple(Z.shape)))
+        dH = segment_pool_bwd(self.batch.graph_ptr, dZ, self.pool, arg=arg, out=self.net.grad_buffer())
+        self.net.backward(dH, input_grad=False)
+
+    def step(self, lr, weight_decay=0.0):
+        self.net.step(lr, weight_decay)
+        sgd_step(self.W_c, self.dW_c, lr, weight_decay)
+        sgd_step(self.b_c, self.db_c, lr, weight_decay)
+
+    def train_step(self, X, target, lr, weight_decay=0.0):
+        """One SGD step on the batch: forward -> softmax_ce over the B graphs (db_c from the loss kernel) -> backward through the
+        readout and the stack, no input gradient -> step.  target: int32 [B].  Returns the loss tensor."""
+        logits = self.forward(X)
+        loss, d = softmax_ce(logits, target, colsum_out=self.db_c, grad_out=self._tmp("dlogits", tuple(logits.shape)))
+        self.backward(d, have_bias_grad=True)
+        self.step(lr, weight_decay)
+        return loss
+
+    def evaluate(self, X, target):
+        """(loss as a 1-element tensor, correctly classified graphs, B)."""
+        logits = self.forward(X)
+        return (softmax_ce(logits, target, want_grad=False)[0], *accuracy(logits, target))

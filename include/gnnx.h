@@ -819,6 +819,63 @@ int gnnx_spmm_csr_reduce_bwd_f32(int32_t n_rows_t, int32_t n_cols_t, int32_t n_f
                                  int64_t lda, const float *d_G, int64_t ldg, float beta, float *d_dX, int64_t ldx, void *d_workspace,
                                  size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ graph readout --------------- */
+/*
+ * One row of output per GRAPH of a batch: the SUM, MEAN or MAX of each segment of consecutive rows of X, and the backward that hands a
+ * segment's gradient back to its rows -- the readout of graph classification and regression.  The reference declares the batch
+ * (graph::DataBatch, reference graph.h:104-109) and leaves it without a body; the contract is this comment, restated in NumPy by
+ * tests/pool_ref.py.
+ *
+ * Segment b is the rows [segptr[b], segptr[b+1]) of X; segptr has n_seg + 1 entries and is TRUSTED to be non-decreasing with
+ * segptr[0] == 0 and segptr[n_seg] == n_rows.  X and dX: [n_rows, n_feat]; Y (float), arg (int32) and G (float): [n_seg, n_feat]; every
+ * matrix has its own leading dimension and columns beyond n_feat are never touched.  len = segptr[b+1] - segptr[b].
+ *
+ * Forward, gnnx_segment_pool_f32:
+ *   GNNX_POOL_SUM   With T = GNNX_POOL_CHUNK a segment is cut into chunks of T consecutive rows counted from the segment's OWN first
+ *                   row (the last chunk may be short).  A chunk is summed by ONE accumulator per feature that starts at +0 and walks the
+ *                   chunk's rows in ASCENDING order; the segment's sum is ((c_0 + c_1) + c_2) + ... in ascending chunk order.  A graph's
+ *                   readout is therefore a function of that graph's rows alone: the same bits whether the graph is pooled by itself or
+ *                   at any position of any batch, and however chunks are mapped to lanes, workgroups or XCDs.
+ *   GNNX_POOL_MEAN  Y = sum / (float)len with the sum above and ONE correctly rounded fp32 division (no reciprocal multiply).
+ *   GNNX_POOL_MAX   arg[b, f] = the SMALLEST row i of the segment such that no row q of it has X[q, f] > X[i, f]: an ABSOLUTE row index.
+ *                   Y[b, f] = X[arg, f] with that row's bits: between +0 and -0 the earlier row wins and keeps its sign.  A non-empty
+ *                   segment ALWAYS gets a valid row, also when every value is -inf.  With a NaN in the segment the value and the arg
+ *                   are unspecified; no access is ever out of range.
+ *   An empty segment writes Y = +0 for every op and arg = -1 for MAX.  d_arg may be NULL; SUM and MEAN never write it.
+ *
+ * Backward, gnnx_segment_pool_bwd_f32, for row i of segment b:
+ *   t = G[b, f] (SUM);  t = G[b, f] / (float)len (MEAN, the same single division);  t = G[b, f] if arg[b, f] == i and +0 otherwise (MAX);
+ *   dX[i, f] = t with beta == 0 -- dX is never read, a NaN already in it vanishes -- and dX[i, f] + t (one rounded add) with beta == 1.
+ *   Every row of dX is written.
+ *
+ * Both calls are asynchronous on `stream` (a chain of launches on that one stream); they allocate nothing, synchronise nothing and use
+ * no atomics on any value: the bits are the same on every run.  All element offsets are 64-bit.  GNNX_ERR_INVALID_ARG before any device
+ * call for: a negative size, a leading dimension < n_feat (lda only where the op is MAX), an op outside the enum, a beta other than 0 or 1, n_seg == 0 with
+ * n_rows != 0, and a null pointer (the forward's d_arg may be NULL, MAX backward requires it, SUM / MEAN backward ignore it; d_X / d_dX
+ * may be NULL with n_rows == 0).  n_feat == 0 or n_seg == 0 returns GNNX_OK and writes nothing; n_rows == 0 with n_seg > 0 still writes
+ * the per-segment outputs.  A workspace that is NULL or smaller than gnnx_segment_pool_workspace() bytes is GNNX_ERR_WORKSPACE with
+ * nothing written; it holds nothing between calls and may sit at any address.  Its size is a function of the sizes alone (n_seg does
+ * not enter):
+ *   tiles = n_rows / T + 1 (integer division);   bytes = 256 + round_up_256( 4 * tiles * (4 * n_feat + 1) )
+ * -- per tile of T rows two chunk partials, each a value and a position per feature, and the long segment that starts in the tile.
+ *
+ * Kernels (gnnx_pool.hip): the work unit is a (segment, chunk) pair.  The grid is dealt over global tiles of T rows; a lane group of
+ * 4 .. 64 lanes (one 16-byte piece of the feature row per lane, feature tiles in the grid's y) finds by binary search in segptr the
+ * chunks that START inside its tile -- any segment has at most one, and at most two of them belong to segments longer than T -- and
+ * reads their rows with no index array, the loads of sixteen rows issued ahead of the dependent chain.  A segment of at most T rows
+ * writes Y directly; a longer one writes chunk partials and a combine kernel finishes it in ascending chunk order (MAX: the better
+ * value wins and on equal values the smaller row).  n_feat % 4 != 0, or a pointer or leading dimension that is not 16-byte aligned,
+ * takes scalar lanes with the same bits.  The backward is one streaming pass over the rows of dX, each lane group finding its segment
+ * in segptr.
+ */
+enum { GNNX_POOL_SUM = 0, GNNX_POOL_MEAN = 1, GNNX_POOL_MAX = 2 };
+#define GNNX_POOL_CHUNK 256
+int gnnx_segment_pool_workspace(int32_t n_seg, int32_t n_rows, int32_t n_feat, size_t *bytes);
+int gnnx_segment_pool_f32(int op, int32_t n_seg, int32_t n_rows, int32_t n_feat, const int32_t *d_segptr, const float *d_X, int64_t ldx,
+                          float *d_Y, int64_t ldy, int32_t *d_arg, int64_t lda, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_segment_pool_bwd_f32(int op, int32_t n_seg, int32_t n_rows, int32_t n_feat, const int32_t *d_segptr, const int32_t *d_arg,
+                              int64_t lda, const float *d_G, int64_t ldg, float beta, float *d_dX, int64_t ldx, void *stream);
+
 /* ------------------------------------------------------------------ neighbour sampling ---------- */
 /*
  * A fixed fanout of k neighbours per vertex, drawn afresh from a seed: the other half of GraphSAGE (Hamilton et al. 2017).  The sample
