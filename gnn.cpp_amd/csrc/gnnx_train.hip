@@ -4,6 +4,13 @@
 //          loss = (sum_i l_i) / N.   No max-subtraction, like the reference (logits of a GCN layer are O(1..100)).
 //   dlogits (textbook; the reference has none that works):  (softmax(x_i) - onehot(t_i)) / N
 //   SGD    (textbook; the reference's step() reads an empty velocity vector, nn.cpp:414):  p -= lr * (g + wd * p)
+// Error bounds of the loss (include/gnnx.h; u = 2^-24, S = 4 ceil(C / 256) + 6 additions on the row sum of the vector form,
+// ceil(C / 64) + 6 on the generic walk): gradient (S + 8) u (p + onehot) / N, column sums (S + 8 + n) u sum (p + onehot) / N,
+// loss u [(S + 4) n + (ceil(n / 65536) + 266) sum |l_i|] / N.  Worst ratios error / (u * scale) that tests/test_gpu_loss.py has seen
+// on an MI355X:  vector form  gradient 5.3, column sums 5.4, loss 3.5 (of u sum |l_i| / N; 1.3 % of its bound)
+//                generic      gradient 5.4, column sums 4.4, loss 3.2
+//                BCE          gradient 3.4 (bound 6), loss 1.4 (bound 276)
+// On inputs where nothing rounds (logits 0 or dead, 1 / 2 / 4 / 8 live classes, N a power of two) every path is exact to the bit.
 #include "gnnx_common.h"
 
 #include <type_traits>

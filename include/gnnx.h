@@ -466,7 +466,23 @@ int gnnx_bn_relu_bwd_apply_f32(const float *d_X, int64_t ldx, const float *d_Y, 
  *   dlogits = (softmax(x_i) - onehot(t_i)) / N                             textbook (the reference's backward throws);
  *             may be NULL.  Synchronises `stream` (validates the targets: GNNX_ERR_INDEX_RANGE).
  *   One kernel set serves these calls and gnnx_softmax_ce_rows_f32 below (the loss over a row list); each *_workspace query is the
- *   layout its call then uses, and the workspace pointer may have any alignment.
+ *   layout its call then uses, and the workspace pointer may have any alignment -- for gnnx_softmax_ce_f32, _colsum_f32, _partial_f32
+ *   and gnnx_softmax_ce_rows_f32 (the query includes the room to round the pointer up; no byte outside the queried size is touched).
+ *   gnnx_bce_logits_f32 takes its workspace pointer as it is: 4-byte aligned.
+ *   Non-finite logits (there is no max-subtraction, so x >= 89 overflows expf like +inf): no error status.  The row's own
+ *   gradient row and the loss become non-finite (the column sums of the classes it poisons too); every other gradient row has the bits
+ *   it has without the poisoned row.  A -inf logit off the target is an ordinary dead class (probability 0, gradient +0).  A row whose
+ *   target's exp is 0 has an infinite row loss and the gradient p - onehot as usual; a FULLY dead row (every exp 0: the sum is 0, the
+ *   denominator 1e-20) gives exactly -onehot / n_total.
+ *   Error bounds against float64, u = 2^-24, p = softmax, d = onehot (tests/test_gpu_loss.py holds every form to them):
+ *     gradient     |dlogits - (p - d) / n_total| <= (S + 8) u (p + d) / n_total
+ *     column sums  |colsum - exact|              <= (S + 8 + n_listed) u sum_i (p + d) / n_total
+ *     loss         |loss - exact|                <= u [(S + 4) n_listed + (ceil(n_listed / 65536) + 266) sum_i |l_i|] / n_total
+ *   S = additions on the path of a row sum: 4 ceil(C / 256) + 6 on the vector form (C % 4 == 0, C <= 1024, ldx % 4 == 0, ldd % 4 == 0,
+ *   logits and dlogits 16-byte aligned), ceil(C / 64) + 6 otherwise.  Worst ratios error / (u * scale) observed on an MI355X: gradient
+ *   5.3 (vector) / 5.4 (generic) against S + 8 >= 15; column sums 5.4 / 4.4; loss 3.5 / 3.2 times u sum |l_i| / n_total, 1.3 % of its bound.
+ *   On inputs where nothing rounds (logits 0 or dead, 1 / 2 / 4 / 8 live classes a row, n_total a power of two) dlogits and the column
+ *   sums are exact on every path.
  *   sgd     : p -= lr * (g + weight_decay * p)                             textbook (nn.cpp:395-421 indexes an empty vector)
  */
 int gnnx_softmax_ce_workspace(int64_t n_rows, size_t *bytes);
@@ -493,7 +509,9 @@ int gnnx_sgd_step_f32(float *d_param, const float *d_grad, int64_t n, float lr, 
  * d_target is float: soft labels are allowed.  n_total >= n is the divisor (n on one GPU).  d_loss (one device float) and d_dscores
  * [n] may each be NULL.  The sum is two-stage on a fixed grid in a fixed order (as gnnx_colsum_f32): the same bits on every run.
  * Asynchronous.  n == 0 is GNNX_ERR_INVALID_ARG, never a NaN loss (as gnnx_softmax_ce_rows_f32).  Workspace:
- * gnnx_bce_logits_workspace() bytes. */
+ * gnnx_bce_logits_workspace() bytes, 4-byte aligned, needed only with d_loss; both outputs NULL: GNNX_OK, nothing is touched.
+ * Against float64 (tests/test_gpu_loss.py): |dscores - exact| <= 6 * 2^-24 (sigmoid + y) / n_total (observed 3.4) wherever sigmoid(x)
+ * is a normal f32 number; exact on scores of +-128 / +-256 with targets 0, 1, 0.25 and n_total a power of two, loss included. */
 int gnnx_bce_logits_workspace(int64_t n, size_t *bytes);
 int gnnx_bce_logits_f32(const float *d_scores, const float *d_target, int64_t n, int64_t n_total, float *d_loss, float *d_dscores,
                         void *d_workspace, size_t workspace_bytes, void *stream);

@@ -8,6 +8,7 @@ Bars (the project's own, tests/test_gpu_parity.py module docstring and its cross
   * pruning: BIT equality (torch.equal) between the step on the full CSR and the step on the restricted CSR -- a dropped term of a
     kept accumulator is norm * 0 -- and numeric == (tests.golden_util.same) against the oracle on the FULL CSR;
   * whole step against float64: the bounds of test_two_layer_training_step_vs_float64.
+These are the workload shapes; the tight bars are tests/test_gpu_loss.py (the loss) and tests/test_gpu_mask_calls.py (the index calls).
 """
 import importlib
 import os

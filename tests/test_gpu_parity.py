@@ -1273,7 +1273,8 @@ def test_softmax_cross_entropy_shapes_and_fused_bias_gradient(env, n, c):
     """Both kernels of gnnx_softmax_ce_colsum_f32 (the one-16-byte-load-per-lane form for class counts that are multiples of 4 up
     to 1024 -- the bench's 256 is one 1-KiB wave-instruction per row -- and the generic walk) against float64, an odd number of
     rows (the two-rows-in-flight tail), a padded row stride, and the column sums of dlogits written by the same kernel against a
-    float64 column sum and against gnnx_colsum_f32 over the stored gradient."""
+    float64 column sum and against gnnx_colsum_f32 over the stored gradient.
+    (Workload shapes; tests/test_gpu_loss.py holds every form to per-element bounds and to exact inputs.)"""
     ops, torch = env["ops"], env["torch"]
     X = synth.uniform_pm1(900 + c, (n, c)) * 3.0
     t = ((7 * np.arange(n) + 3) % c).astype(np.int32)
