@@ -52,6 +52,13 @@ def _workspace(nbytes, device, tag):
     return buf
 
 
+def _scratch(query_name, *sizes, device, tag):
+    """(scratch, nbytes): the library's own answer to `query_name(*sizes, &nbytes)` and the _workspace of `tag` grown to hold it."""
+    nbytes = C.c_size_t(0)
+    capi.call(query_name, *sizes, C.byref(nbytes))
+    return _workspace(nbytes.value, device, tag), nbytes.value
+
+
 class SpmmPlan:
     """gnnx_spmm_plan: hub rows (longer than `chunk`) to the sequential hub kernel, non-zero-balanced blocks for the rest; the
     planned aggregation has the same bits as the unplanned one."""
@@ -284,9 +291,7 @@ def rows_from_mask(mask):
     m = (m if m.dtype == torch.uint8 else m.to(torch.uint8)).contiguous()
     n = int(m.numel())
     rows = torch.empty(max(n, 1), dtype=torch.int32, device=m.device)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_mask_to_rows_workspace", n, C.byref(wsb))
-    ws = _workspace(wsb.value, m.device, "mask")
+    ws, _ = _scratch("gnnx_mask_to_rows_workspace", n, device=m.device, tag="mask")
     cnt = C.c_int32(0)
     capi.call("gnnx_mask_to_rows", _ptr(m), n, _ptr(rows), C.byref(cnt), _ptr(ws), ws.numel(), _stream())
     return rows[: cnt.value].clone()
@@ -308,9 +313,7 @@ def csr_restrict(rowptr, colidx, vals=None, row_keep=None, col_keep=None, n_cols
     rowptr_o = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
     colidx_o = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
     vals_o = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev) if vals is not None else None
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_csr_restrict_workspace", n_rows, nnz, C.byref(wsb))
-    ws = _workspace(wsb.value, dev, "mask")
+    ws, _ = _scratch("gnnx_csr_restrict_workspace", n_rows, nnz, device=dev, tag="mask")
     out_nnz = C.c_int64(0)
     capi.call("gnnx_csr_restrict", n_rows, int(n_cols), nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(vals), _ptr(rk), _ptr(ck),
               _ptr(rowptr_o), _ptr(colidx_o), _ptr(vals_o), C.byref(out_nnz), _ptr(ws), ws.numel(), _stream())
@@ -330,9 +333,7 @@ def _frontier(rowptr, colidx, rows, n_cols):
     rows = _row_list(rows)
     n_rows, k, dev = int(rowptr.numel() - 1), int(rows.numel()), rowptr.device
     mark = torch.zeros(max(int(n_cols), 1), dtype=torch.uint8, device=dev)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_frontier_mark_workspace", k, C.byref(wsb))
-    ws = _workspace(wsb.value, dev, "field")
+    ws, _ = _scratch("gnnx_frontier_mark_workspace", k, device=dev, tag="field")
     nnz = C.c_int64(0)
     capi.call("gnnx_frontier_mark", _ptr(rowptr), _ptr(colidx) if int(colidx.numel()) else None, n_rows, int(n_cols), _ptr(rows) if k else None, k,
               _ptr(mark), C.byref(nnz), _ptr(ws), ws.numel(), _stream())
@@ -372,9 +373,7 @@ def csr_extract_rows(rowptr, colidx, rows, vals=None, col_pos=None, n_cols=None,
     rowptr_o = torch.empty(k + 1, dtype=torch.int32, device=dev)
     colidx_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
     vals_o = torch.empty(max(cap, 1), dtype=torch.float32, device=dev) if vals is not None else None
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_csr_extract_rows_workspace", k, C.byref(wsb))
-    ws = _workspace(wsb.value, dev, "field")
+    ws, _ = _scratch("gnnx_csr_extract_rows_workspace", k, device=dev, tag="field")
     out_nnz = C.c_int64(0)
     capi.call("gnnx_csr_extract_rows", n_rows, int(n_cols), _ptr(rowptr), _ptr(colidx) if int(colidx.numel()) else None, _ptr(vals),
               _ptr(rows) if k else None, k, _ptr(col_pos), _ptr(rowptr_o), _ptr(colidx_o), _ptr(vals_o), cap, C.byref(out_nnz), _ptr(ws),
@@ -392,14 +391,12 @@ def sample_neighbors(rowptr, colidx, k, seed, want_pos=False, want_rowid=False):
     (seed, k) gives the same sample on every run; use one seed per epoch or layer."""
     n_rows, nnz, dev = int(rowptr.numel() - 1), int(colidx.numel()), rowptr.device
     k = int(k)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_csr_sample_workspace", n_rows, nnz, k, C.byref(wsb))     # refuses k < 1 and k > 64 before anything is sized
+    ws, _ = _scratch("gnnx_csr_sample_workspace", n_rows, nnz, k, device=dev, tag="sample")   # refuses k < 1 and k > 64 before anything is sized
     cap = int((rowptr[1:] - rowptr[:-1]).clamp(max=k).sum()) if n_rows else 0   # min(deg, k): the capacity is exact
     rowptr_o = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
     colidx_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
     pos_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_pos else None
     rowid_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_rowid else None
-    ws = _workspace(wsb.value, dev, "sample")
     out_nnz = C.c_int64(0)
     capi.call("gnnx_csr_sample_neighbors", n_rows, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, k, int(seed) & (2 ** 64 - 1), _ptr(rowptr_o),
               _ptr(colidx_o), _ptr(pos_o), _ptr(rowid_o), cap, C.byref(out_nnz), _ptr(ws), ws.numel(), _stream())
@@ -474,10 +471,8 @@ def linear_fwd_bf16(X, W, out=None):
           and out.data_ptr() % 16 == 0)
     if not ok:
         return to_bf16(gemm(X, W, transB=True), out=out)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_gemm_nt_bf16out_workspace", M, N, K, C.byref(wsb))
-    ws = _workspace(wsb.value, X.device, "gemm_bf16out")
-    capi.call("gnnx_gemm_nt_bf16out_f32", M, N, K, _ptr(X), _ld(X), _ptr(W), _ld(W), _ptr(out), _ld(out), _ptr(ws), wsb.value, _stream())
+    ws, wsb = _scratch("gnnx_gemm_nt_bf16out_workspace", M, N, K, device=X.device, tag="gemm_bf16out")
+    capi.call("gnnx_gemm_nt_bf16out_f32", M, N, K, _ptr(X), _ld(X), _ptr(W), _ld(W), _ptr(out), _ld(out), _ptr(ws), wsb, _stream())
     return out
 
 
@@ -581,11 +576,9 @@ def bce_logits(scores, target, want_grad=True, n_total=None, grad_out=None):
     loss = torch.empty(1, dtype=torch.float32, device=scores.device)
     d = (torch.empty_like(scores) if grad_out is None else grad_out) if want_grad else None
     assert d is None or (d.is_contiguous() and d.numel() == n)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_bce_logits_workspace", n, C.byref(wsb))
-    ws = _workspace(wsb.value, scores.device, "bce")
+    ws, wsb = _scratch("gnnx_bce_logits_workspace", n, device=scores.device, tag="bce")
     capi.call("gnnx_bce_logits_f32", _ptr(scores) if n else None, _ptr(target) if n else None, n, int(n if n_total is None else n_total),
-              _ptr(loss), _ptr(d), _ptr(ws), wsb.value, _stream())
+              _ptr(loss), _ptr(d), _ptr(ws), wsb, _stream())
     return loss, d
 
 
@@ -644,9 +637,7 @@ def _edge_softmax_args(rowptr, colidx, scores, rowterm, colterm):
     n_cols = int(colterm.numel()) if colterm is not None else n_rows
     rt, rs = _edge_term(rowterm, n_rows, "rowterm")
     ct, cs = _edge_term(colterm, n_cols, "colterm")
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_edge_softmax_workspace", n_rows, nnz, C.byref(wsb))
-    ws = _workspace(wsb.value, rowptr.device, "edge_softmax")
+    ws, _ = _scratch("gnnx_edge_softmax_workspace", n_rows, nnz, device=rowptr.device, tag="edge_softmax")
     return n_rows, n_cols, nnz, rt, rs, ct, cs, ws
 
 
@@ -762,9 +753,7 @@ def _edge_softmax_heads_args(rowptr, colidx, n_heads, scores, rowterm, colterm):
     n_cols = int(colterm.shape[0]) if colterm is not None else n_rows
     rt, rs = _edge_terms_heads(rowterm, n_rows, n_heads, "rowterm")
     ct, cs = _edge_terms_heads(colterm, n_cols, n_heads, "colterm")
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_edge_softmax_heads_workspace", n_rows, nnz, n_heads, C.byref(wsb))
-    ws = _workspace(wsb.value, rowptr.device, "edge_softmax")
+    ws, _ = _scratch("gnnx_edge_softmax_heads_workspace", n_rows, nnz, n_heads, device=rowptr.device, tag="edge_softmax")
     return n_rows, n_cols, nnz, lds, rt, rs, ct, cs, ws
 
 
@@ -808,12 +797,6 @@ def edge_softmax_heads_bwd(rowptr, colidx, n_heads, alpha, dalpha, scores=None, 
 REDUCE_OPS = {"max": 0, "min": 1}   # GNNX_REDUCE_MAX / GNNX_REDUCE_MIN
 
 
-def _reduce_workspace(n_rows, nnz, F, device):
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, F, C.byref(wsb))
-    return _workspace(wsb.value, device, "reduce")
-
-
 def spmm_reduce(rowptr, colidx, X, op="max", vals=None, out=None, arg_out=None, want_arg=True):
     """gnnx_spmm_csr_reduce_f32: (Y, arg) with Y[i, f] = max (op="min": min) over the stored entries p of row i of vals[p] * X[c_p, f]
     (X[c_p, f] itself without vals) and arg[i, f] = the first position p that attains it -- int32, absolute in colidx; an empty row
@@ -829,7 +812,7 @@ def spmm_reduce(rowptr, colidx, X, op="max", vals=None, out=None, arg_out=None, 
         out = torch.empty((n_rows, F), dtype=torch.float32, device=X.device)
     arg = (torch.empty((n_rows, F), dtype=torch.int32, device=X.device) if arg_out is None else arg_out) if want_arg else None
     assert tuple(out.shape) == (n_rows, F) and (arg is None or (tuple(arg.shape) == (n_rows, F) and arg.dtype == torch.int32))
-    ws = _reduce_workspace(n_rows, nnz, F, X.device)
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, F, device=X.device, tag="reduce")
     capi.call("gnnx_spmm_csr_reduce_f32", REDUCE_OPS[op], n_rows, n_cols, F, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None,
               _ptr(vals) if nnz else None, _ptr(X) if X.numel() else None, _ld(X), _ptr(out), _ld(out), _ptr(arg),
               _ld(arg) if arg is not None else 0, _ptr(ws), ws.numel(), _stream())
@@ -851,7 +834,7 @@ def spmm_reduce_bwd(rowptr_t, colidx_t, map_t, arg, G, vals=None, out=None, beta
             raise capi.GnnxError(-1, "spmm_reduce_bwd", "beta = 1 needs the matrix to add to (out)")
         out = torch.empty((n_rows_t, F), dtype=torch.float32, device=G.device)
     assert tuple(out.shape) == (n_rows_t, F)
-    ws = _reduce_workspace(n_rows_t, nnz, F, G.device)
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows_t, nnz, F, device=G.device, tag="reduce")
     capi.call("gnnx_spmm_csr_reduce_bwd_f32", n_rows_t, n_cols_t, F, nnz, _ptr(rowptr_t), _ptr(colidx_t) if nnz else None,
               _ptr(map_t) if nnz else None, _ptr(vals) if nnz else None, _ptr(arg) if arg.numel() else None, _ld(arg),
               _ptr(G) if G.numel() else None, _ld(G), float(beta), _ptr(out), _ld(out), _ptr(ws), ws.numel(), _stream())
@@ -891,11 +874,9 @@ def gemm_relu_colsum(A, B, Ymask, out=None, colsum_out=None):
     N = B.shape[1]
     out = torch.empty((M, N), dtype=torch.float32, device=A.device) if out is None else out
     colsum_out = torch.empty(N, dtype=torch.float32, device=A.device) if colsum_out is None else colsum_out
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_gemm_relu_colsum_workspace", M, N, K, C.byref(wsb))
-    ws = _workspace(wsb.value, A.device, "gemm_fuse")
+    ws, wsb = _scratch("gnnx_gemm_relu_colsum_workspace", M, N, K, device=A.device, tag="gemm_fuse")
     capi.call("gnnx_gemm_relu_colsum_f32", M, N, K, _ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(Ymask), _ld(Ymask), _ptr(out), _ld(out),
-              _ptr(colsum_out), _ptr(ws), wsb.value, _stream())
+              _ptr(colsum_out), _ptr(ws), wsb, _stream())
     return out, colsum_out
 
 
@@ -907,11 +888,9 @@ def linear_fwd_bn_stats(X, W, out=None):
     out = torch.empty((M, N), dtype=torch.float32, device=X.device) if out is None else out
     mean = torch.empty(N, dtype=torch.float32, device=X.device)
     var = torch.empty(N, dtype=torch.float32, device=X.device)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_gemm_bn_stats_workspace", M, N, K, C.byref(wsb))
-    ws = _workspace(wsb.value, X.device, "gemm_bn")
+    ws, wsb = _scratch("gnnx_gemm_bn_stats_workspace", M, N, K, device=X.device, tag="gemm_bn")
     capi.call("gnnx_gemm_bn_stats_f32", M, N, K, _ptr(X), _ld(X), _ptr(W), _ld(W), _ptr(out), _ld(out), _ptr(mean), _ptr(var), _ptr(ws),
-              wsb.value, _stream())
+              wsb, _stream())
     return out, mean, var
 
 
@@ -921,11 +900,9 @@ def gemm_split(A, B, transB=False, out=None):
     M, K = A.shape
     N = B.shape[0] if transB else B.shape[1]
     out = torch.empty((M, N), dtype=torch.float32, device=A.device) if out is None else out
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_gemm_split_workspace", M, N, K, C.byref(wsb))
-    ws = _workspace(wsb.value, A.device, "gemm_split")
+    ws, wsb = _scratch("gnnx_gemm_split_workspace", M, N, K, device=A.device, tag="gemm_split")
     capi.call("gnnx_gemm_split_bf16_f32", int(transB), M, N, K, _ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(out), _ld(out), _ptr(ws),
-              wsb.value, _stream())
+              wsb, _stream())
     return out
 
 
@@ -979,11 +956,9 @@ def linear_fwd_rows_to_slots(X, W, out, table, send):
     the pass that reads H back)."""
     M, K = X.shape
     N = W.shape[0]
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_gemm_nt_rows_to_slots_workspace", M, N, K, C.byref(wsb))
-    ws = _workspace(wsb.value, X.device, "gemm")
+    ws, wsb = _scratch("gnnx_gemm_nt_rows_to_slots_workspace", M, N, K, device=X.device, tag="gemm")
     capi.call("gnnx_gemm_nt_rows_to_slots_f32", M, N, K, _ptr(X), _ld(X), _ptr(W), _ld(W), _ptr(out), _ld(out), _ptr(table), _ptr(send), _ld(send),
-              _ptr(ws), wsb.value, _stream())
+              _ptr(ws), wsb, _stream())
     return out
 
 
@@ -1075,10 +1050,8 @@ def bn_stats(X):
     N, F = X.shape
     mean = torch.empty(F, dtype=torch.float32, device=X.device)
     var = torch.empty(F, dtype=torch.float32, device=X.device)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_bn_workspace", N, F, C.byref(wsb))
-    ws = _workspace(wsb.value, X.device, "bn")
-    capi.call("gnnx_bn_stats_f32", _ptr(X), _ld(X), N, F, _ptr(mean), _ptr(var), _ptr(ws), wsb.value, _stream())
+    ws, wsb = _scratch("gnnx_bn_workspace", N, F, device=X.device, tag="bn")
+    capi.call("gnnx_bn_stats_f32", _ptr(X), _ld(X), N, F, _ptr(mean), _ptr(var), _ptr(ws), wsb, _stream())
     return mean, var
 
 
@@ -1086,10 +1059,8 @@ def bn_partial(X, mean=None, scale=1.0):
     """scale * column sums of X (mean None) or of (X - mean)^2: the per-shard halves of the batch statistics (gnnx_bn_partial_f32)."""
     N, F = X.shape
     out = torch.empty(F, dtype=torch.float32, device=X.device)
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_bn_workspace", N, F, C.byref(wsb))
-    ws = _workspace(wsb.value, X.device, "bn")
-    capi.call("gnnx_bn_partial_f32", _ptr(X), _ld(X), N, F, _ptr(mean), float(scale), _ptr(out), _ptr(ws), wsb.value, _stream())
+    ws, wsb = _scratch("gnnx_bn_workspace", N, F, device=X.device, tag="bn")
+    capi.call("gnnx_bn_partial_f32", _ptr(X), _ld(X), N, F, _ptr(mean), float(scale), _ptr(out), _ptr(ws), wsb, _stream())
     return out
 
 
@@ -1107,20 +1078,12 @@ def bn_relu_bwd(X, Y, dY, mean=None, var=None, gamma=None, eps=1e-5, relu=True, 
     dX = torch.empty_like(X) if out is None else out
     dgamma = torch.empty(F, dtype=torch.float32, device=X.device) if mean is not None else None
     dbeta = torch.empty(F, dtype=torch.float32, device=X.device) if mean is not None else None
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_bn_workspace", N, F, C.byref(wsb))
-    ws = _workspace(wsb.value, X.device, "bn")
+    ws, wsb = _scratch("gnnx_bn_workspace", N, F, device=X.device, tag="bn")
     capi.call("gnnx_bn_relu_bwd_quirk_f32" if reference_quirk else "gnnx_bn_relu_bwd_f32", _ptr(X), _ld(X), _ptr(Y),
               _ld(Y) if Y is not None else 0, _ptr(dY), _ld(dY), N, F, _ptr(mean),
               _ptr(var), float(eps), _ptr(gamma), _ptr(beta), int(relu), _ptr(dX), _ld(dX), _ptr(dgamma), _ptr(dbeta), _ptr(ws),
-              wsb.value, _stream())
+              wsb, _stream())
     return dX, dgamma, dbeta
-
-
-def _bn_workspace(N, F, device):
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_bn_workspace", N, F, C.byref(wsb))
-    return _workspace(wsb.value, device, "bn"), wsb.value
 
 
 def bn_relu_bwd_sums(X, Y, dY, mean, var, gamma=None, eps=1e-5, relu=True, beta=None):
@@ -1129,7 +1092,7 @@ def bn_relu_bwd_sums(X, Y, dY, mean, var, gamma=None, eps=1e-5, relu=True, beta=
     N, F = X.shape
     dgamma = torch.empty(F, dtype=torch.float32, device=X.device)
     dbeta = torch.empty(F, dtype=torch.float32, device=X.device)
-    ws, wsb = _bn_workspace(N, F, X.device)
+    ws, wsb = _scratch("gnnx_bn_workspace", N, F, device=X.device, tag="bn")
     capi.call("gnnx_bn_relu_bwd_sums_f32", _ptr(X), _ld(X), _ptr(Y), _ld(Y) if Y is not None else 0, _ptr(dY), _ld(dY), N, F, _ptr(mean),
               _ptr(var), float(eps), _ptr(gamma), _ptr(beta), int(relu), _ptr(dgamma), _ptr(dbeta), _ptr(ws), wsb, _stream())
     return dgamma, dbeta
@@ -1140,7 +1103,7 @@ def bn_relu_bwd_apply(X, Y, dY, mean=None, var=None, gamma=None, dgamma=None, db
     """gnnx_bn_relu_bwd_apply_f32: dX of this call's rows from the (global) sums and the (global) row count n_total."""
     N, F = X.shape
     dX = torch.empty((N, F), dtype=torch.float32, device=X.device) if out is None else out
-    ws, wsb = _bn_workspace(N, F, X.device)
+    ws, wsb = _scratch("gnnx_bn_workspace", N, F, device=X.device, tag="bn")
     capi.call("gnnx_bn_relu_bwd_apply_f32", _ptr(X), _ld(X), _ptr(Y), _ld(Y) if Y is not None else 0, _ptr(dY), _ld(dY), N, F, _ptr(mean),
               _ptr(var), float(eps), _ptr(gamma), _ptr(beta), int(relu), _ptr(dgamma), _ptr(dbeta), int(N if n_total is None else n_total),
               _ptr(dX), _ld(dX), _ptr(ws), wsb, _stream())
@@ -1212,12 +1175,10 @@ def aggregate_bwd_bn_sums(g, G, H, mean, var, gamma=None, beta=None, eps=1e-5, r
     dbeta = torch.empty(F, dtype=torch.float32, device=G.device)
     plan = g.plan_t if use_plan else None
     ph = plan.h if plan is not None else None
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_spmm_csr_bn_sums_workspace", n, F, ph, C.byref(wsb))
-    ws = _workspace(wsb.value, G.device, "bn_sums")
+    ws, wsb = _scratch("gnnx_spmm_csr_bn_sums_workspace", n, F, ph, device=G.device, tag="bn_sums")
     capi.call("gnnx_spmm_csr_bn_sums_f32", n, n, F, _ptr(g.rowptr_t), _ptr(g.colidx_t), _ptr(g.norm_per_nz_t), _ptr(G), _ld(G), _ptr(out),
               _ld(out), _ptr(H), _ld(H), _ptr(mean), _ptr(var), float(eps), _ptr(gamma), _ptr(beta), int(relu), _ptr(dgamma), _ptr(dbeta),
-              _ptr(ws), wsb.value, ph, _stream())
+              _ptr(ws), wsb, ph, _stream())
     return out, dgamma, dbeta
 
 
@@ -1267,14 +1228,13 @@ def _softmax_ce(logits, target, rows, d, colsum_out, n_total):
     n = N if rows is None else int(rows.numel())
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     assert colsum_out is None or (d is not None and colsum_out.numel() == Cn and colsum_out.is_contiguous())
-    wsb = C.c_size_t(0)
     if rows is not None:
-        capi.call("gnnx_softmax_ce_rows_workspace", n, Cn, C.byref(wsb))
+        query = ("gnnx_softmax_ce_rows_workspace", n, Cn)
     elif colsum_out is not None:
-        capi.call("gnnx_softmax_ce_colsum_workspace", n, Cn, C.byref(wsb))
+        query = ("gnnx_softmax_ce_colsum_workspace", n, Cn)
     else:
-        capi.call("gnnx_softmax_ce_workspace", n, C.byref(wsb))
-    ws = _workspace(wsb.value, logits.device, "ce")
+        query = ("gnnx_softmax_ce_workspace", n)
+    ws, _ = _scratch(*query, device=logits.device, tag="ce")
     tail = (int(n if n_total is None else n_total), _ptr(loss), _ptr(d), 0 if d is None else _ld(d), _ptr(colsum_out), _ptr(ws), ws.numel(),
             _stream())
     if rows is None:
@@ -1322,18 +1282,6 @@ def accuracy(logits, target, rows=None):
     return correct.value, nl
 
 
-def _zeroed_grad_buffer(net, key_obj):
-    """net.grad_buffer() zero everywhere outside the rows softmax_ce_rows writes for key_obj (a labelled set, a row list): zeroed when
-    first used and whenever a different object arrives (the rows the previous one wrote must become zero again)."""
-    G = net.grad_buffer()
-    key = (id(key_obj), G.data_ptr())
-    if getattr(net, "_grad_zeroed_for", None) != key:
-        G.zero_()
-        net._grad_zeroed_for = key
-        net._grad_set = key_obj   # keeps the object alive: id() stays unique
-    return G
-
-
 def _loss_and_accuracy(logits, target, rows):
     """(loss over `rows` as a 1-element tensor, correct predictions among them, len(rows)) of a forward's logits."""
     return (softmax_ce_rows(logits, target, rows, want_grad=False)[0], *accuracy(logits, target, rows))
@@ -1344,9 +1292,103 @@ def sgd_step(param, grad, lr, weight_decay=0.0):
     return param
 
 
-class GcnStack:
+class _Model:
+    """What the trainable models share: the table `_buf` of persistent scratch buffers, one SGD step over the parallel lists params() /
+    grads() (a subclass defines both: every parameter tensor, and its gradient at the same position), and _view, the one way to make a
+    second model on the same parameters.  A subclass creates `_buf = {}` and `_saved = None` in its __init__."""
+
+    gather_pitch = False   # only GcnStack asks its graph (GcnStack._bind)
+
+    def _tmp(self, key, shape, dtype=torch.float32, zero=False, gathered=False):
+        """The persistent buffer `key`: the cached tensor while the shape matches, a new one otherwise (zero-filled with `zero`), on the
+        parameters' device.  gathered: an [n, F] float32 matrix whose rows an aggregation gathers -- on the gather pitch
+        (empty_gathered) when the model's graph wants it."""
+        t = self._buf.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            dev = self.params()[0].device
+            if gathered and self.gather_pitch:
+                t = empty_gathered(*shape, device=dev)
+            else:
+                t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=dev)
+            self._buf[key] = t
+        return t
+
+    def step(self, lr, weight_decay=0.0):
+        for p, gr in zip(self.params(), self.grads()):
+            sgd_step(p, gr, lr, weight_decay)
+
+    def _view(self, share_buf=False, **rebound):
+        """A second model of this class on the SAME parameter and gradient tensors (a step through either is a step of both), with no
+        saved activations, the attributes of `rebound` replaced, and either this model's buffer table itself (share_buf: the shapes
+        stay) or an empty one."""
+        view = object.__new__(type(self))
+        view.__dict__.update(self.__dict__)   # the parameter lists themselves, not copies
+        view.__dict__.update(rebound, _saved=None, _buf=self._buf if share_buf else {})
+        return view
+
+
+class _Stack(_Model):
+    """What the three graph stacks share.  A subclass has forward(X) / backward(dOut, input_grad, have_last_bias_grad), the bias
+    gradients `db`, and _bind(g): the ONE method that derives everything the class takes from its graph (g itself included) and returns
+    self -- __init__ and every rebinding to another graph call it (SageStack.on_graph, GraphClassifier).
+
+    The top gradient's buffer carries a mark in `_buf`, next to it: the selection object (a row list, a LabelledSet) outside whose rows
+    the buffer is known to be zero, which is what softmax_ce_rows needs of it.  masked_grad_buffer zeroes the buffer only when the mark
+    names another object; the mark is dropped when the buffer is reallocated and whenever grad_buffer() hands the buffer to a caller,
+    who may write every row (softmax_ce, GraphClassifier.backward, GcnStack.link_grad).  Models that share `_buf` share the mark."""
+
+    _ZERO_OUTSIDE = "zero outside"   # the mark's key in _buf; the entry keeps the selection alive, so `is` cannot match a recycled id
+
+    def _grad(self, n=None):
+        """The top gradient's buffer, [n (default g.n), dims[-1]], with the mark as it stands unless the buffer had to be reallocated."""
+        key = ("G", len(self.dims) - 1)
+        old = self._buf.get(key)
+        G = self._tmp(key, (self.g.n if n is None else n, self.dims[-1]), gathered=True)   # gathered by the last backward aggregation
+        if G is not old:
+            self._buf.pop(self._ZERO_OUTSIDE, None)
+        return G
+
+    def grad_buffer(self):
+        """Where the loss should write dlogits ([n, dims[-1]]): softmax_ce(..., grad_out=net.grad_buffer())."""
+        self._buf.pop(self._ZERO_OUTSIDE, None)
+        return self._grad()
+
+    def masked_grad_buffer(self, selection):
+        """The gradient buffer, zero everywhere outside the rows softmax_ce_rows writes for `selection`: zeroed when the object is first
+        used and whenever the mark names another one (the rows that one wrote must become zero again)."""
+        G = self._grad()
+        if self._buf.get(self._ZERO_OUTSIDE) is not selection:
+            G.zero_()
+            self._buf[self._ZERO_OUTSIDE] = selection
+        return G
+
+    def _selected(self, selection):
+        """(rows of the selection, what forward and backward are told about it)"""
+        return selection, {}
+
+    def train_step(self, X, target, rows, lr, weight_decay=0.0):
+        """One SGD step on the selected rows: forward -> softmax_ce_rows over them (db[-1] from the loss kernel) -> backward without an
+        input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)) -- for GcnStack a LabelledSet (CsrGraph.labelled(mask)),
+        which also prunes the last layer's two aggregations to its rows; no other layer of any stack is pruned.  X and target in the
+        graph's ROW order (g.to_new_order of vertex-order data); target is read at selected rows only.  Returns the loss tensor."""
+        selection, (rows, pruned) = rows, self._selected(rows)
+        logits = self.forward(X, **pruned)
+        loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=self.masked_grad_buffer(selection))
+        self.backward(G, input_grad=False, have_last_bias_grad=True, **pruned)
+        self.step(lr, weight_decay)
+        return loss
+
+    def evaluate(self, X, target, rows):
+        """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows)).  rows: ascending
+        int32 rows of the graph (g.rows_of(mask) for a vertex-order validation / test mask)."""
+        return _loss_and_accuracy(self.forward(X), target, rows)
+
+
+class GcnStack(_Stack):
     """L GCN layers on one graph: h_{l+1} = act( norm (.) (A . (h_l W_l^T)) + b_l ), ReLU between layers, none after the
-    last.  forward / backward / SGD step, every op a C-ABI call; activations are kept for backward.
+    last.  forward / backward / SGD step, every op a C-ABI call; activations are kept for backward.  train_step / evaluate /
+    grad_buffer / masked_grad_buffer are _Stack's; the selection of train_step and masked_grad_buffer is a LabelledSet
+    (CsrGraph.labelled(mask)), which forward and backward also take to prune the last layer (_selected).
 
     Layout for widths off the 128 grid (pad_streamed; automatic for widths >= 64 on graphs of >= 100 000 nodes: the
     products-shaped F = 100): matrices whose rows are only STREAMED by the dense products -- layer inputs / outputs Y_l, dH_l,
@@ -1357,7 +1399,7 @@ class GcnStack:
     every fmaf chain: the logical columns have the same bits in both layouts (dW: up to how split-K cuts the rows)."""
 
     def __init__(self, g, dims, seed=0, device="cuda", pad_streamed=None):
-        self.g = g
+        self._bind(g)
         self.dims = list(dims)
         L = len(dims) - 1
         if pad_streamed is None:
@@ -1374,30 +1416,32 @@ class GcnStack:
         self.db = [torch.zeros_like(b) for b in self.b]
         self._saved = None
         self._buf = {}
-        # The matrices the aggregations GATHER rows from -- H_l = h_l W_l^T forward, the gradients G_l backward -- sit on the padded
-        # row pitch (gnnx_gather_row_stride) when the graph's hub ids call for it (a synthetic power-law graph in its as-generated
-        # vertex order: gnnx_spmm_plan_hub_ids_structured).  Every one of them is written by a kernel of this stack (the products,
-        # the loss: softmax_ce(grad_out=net.grad_buffer())), so the pitch costs nothing per step; same bits.
-        self.gather_pitch = bool(g.plan is not None and g.plan_t is not None and (g.plan.hub_ids_structured() or g.plan_t.hub_ids_structured()))
 
-    def _gathered(self, key, n, F, device):
-        """persistent [n, F] buffer for a gathered matrix: on the gather pitch when the graph wants it"""
-        t = self._buf.get(key)
-        if t is None or tuple(t.shape) != (n, F):
-            t = self._buf[key] = empty_gathered(n, F, device=device) if self.gather_pitch else torch.empty((n, F), dtype=torch.float32, device=device)
-        return t
+    def _bind(self, g):
+        """The matrices the aggregations GATHER rows from -- H_l = h_l W_l^T forward, the gradients G_l backward -- sit on the padded
+        row pitch (gnnx_gather_row_stride) when the graph's hub ids call for it (a synthetic power-law graph in its as-generated
+        vertex order: gnnx_spmm_plan_hub_ids_structured).  Every one of them is written by a kernel of this stack (the products,
+        the loss: softmax_ce(grad_out=net.grad_buffer())), so the pitch costs nothing per step; same bits.  A caller's wide input
+        that forward checked once is checked again on a new graph."""
+        self.g = g
+        self.gather_pitch = bool(g.plan is not None and g.plan_t is not None and (g.plan.hub_ids_structured() or g.plan_t.hub_ids_structured()))
+        self._checked_input = None
+        return self
+
+    def params(self):
+        return self.Wp + self.b   # padded storage: pads are 0 - lr * (0 + wd * 0) = 0
+
+    def grads(self):
+        return self.dWp + self.db
 
     def grad_buffer(self, n=None):
-        """Where the loss should write dlogits (softmax_ce(..., grad_out=net.grad_buffer())): the top gradient is gathered by the last
-        layer's backward aggregation."""
-        return self._gathered(("G", len(self.W)), self.g.n if n is None else n, self.dims[-1], self.Wp[0].device)
+        """_Stack.grad_buffer for n rows (default: the graph's), on the gather pitch when the graph wants it: the top gradient is
+        gathered by the last layer's backward aggregation."""
+        self._buf.pop(self._ZERO_OUTSIDE, None)
+        return self._grad(n)
 
-    def _zeros(self, key, shape, device):
-        """persistent zero-initialised buffer (padded layout: pad columns are written once, here)"""
-        t = self._buf.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[key] = torch.zeros(shape, dtype=torch.float32, device=device)
-        return t
+    def _selected(self, labelled):
+        return labelled.rows, {"labelled": labelled}
 
     def pad_input(self, X):
         """[n, P0] zero-padded copy of the layer-0 input (call once for static features; forward() accepts its [:, :d0] view)."""
@@ -1414,7 +1458,7 @@ class GcnStack:
         if not self.padded:
             saved, h = [], X
             for l in range(L):
-                H = linear_fwd(h, self.W[l], out=self._gathered(("H", l), X.shape[0], self.dims[l + 1], X.device))
+                H = linear_fwd(h, self.W[l], out=self._tmp(("H", l), (X.shape[0], self.dims[l + 1]), gathered=True))
                 # the ReLU between layers rides in the aggregation's epilogue: only relu(Z) is stored (its sign is the mask)
                 Y = aggregate_fwd(self.g, H, self.b[l], relu_out=l + 1 < L, labelled=labelled if l + 1 == L else None)
                 saved.append((h, Y))
@@ -1435,7 +1479,7 @@ class GcnStack:
         saved = []
         for l in range(L):
             H = linear_fwd(hp, self.Wp[l][:d[l + 1]])                 # K = P[l] (zero pads), N = d[l+1]: gathered, own width
-            Yp = self._zeros(("Y", l), (n, P[l + 1]), X.device)
+            Yp = self._tmp(("Y", l), (n, P[l + 1]), zero=True)   # (pad columns are written once, here)
             aggregate_fwd(self.g, H, self.b[l], out=Yp[:, :d[l + 1]], relu_out=l + 1 < L, labelled=labelled if l + 1 == L else None)
             saved.append((hp, Yp))
             hp = Yp
@@ -1461,7 +1505,7 @@ class GcnStack:
                 # streamed: padded width.  One buffer per (padded, logical) width pair: the aggregation writes columns [:d] only, so two
                 # layers whose widths differ but round to the same 128-float bucket must not share pad columns (a narrower layer
                 # would inherit the wider one's values there, and dW / W pads would stop being zero)
-                dH = self._zeros(("dH", P[l + 1], d[l + 1]), (G.shape[0], P[l + 1]), G.device)
+                dH = self._tmp(("dH", P[l + 1], d[l + 1]), (G.shape[0], P[l + 1]), zero=True)
                 aggregate_bwd(self.g, G, out=dH[:, :d[l + 1]], labelled=labelled if l + 1 == L else None)
                 Wl, hl = self.Wp[l][:, :d[l]], h[:, :d[l]]            # [P_out, d_in] (ld P_in); the layer input, logical width
                 gemm(dH, h, transA=True, out=self.dWp[l])             # dW_l = dH^T . h on the padded widths
@@ -1473,30 +1517,12 @@ class GcnStack:
                 G = gemm(dH, Wl) if input_grad else None             # dX of the first layer: no ReLU below it
             elif fused:
                 # h = Y_{l-1} = relu output of the layer below; G_{l-1} is gathered by that layer's backward aggregation
-                G, _ = gemm_relu_colsum(dH, Wl, hl, out=self._gathered(("G", l), dH.shape[0], Wl.shape[1], dH.device), colsum_out=self.db[l - 1])
+                G, _ = gemm_relu_colsum(dH, Wl, hl, out=self._tmp(("G", l), (dH.shape[0], Wl.shape[1]), gathered=True), colsum_out=self.db[l - 1])
             else:
                 G = gemm(dH, Wl)
                 G, _, _ = bn_relu_bwd(hl, hl, G, relu=True)
                 colsum(G, out=self.db[l - 1])
         return G
-
-    def step(self, lr, weight_decay=0.0):
-        for p, gr in zip(self.Wp + self.b, self.dWp + self.db):   # padded storage: pads are 0 - lr * (0 + wd * 0) = 0
-            sgd_step(p, gr, lr, weight_decay)
-
-    def masked_grad_buffer(self, labelled):
-        """grad_buffer() zero everywhere outside the rows softmax_ce_rows writes for this labelled set."""
-        return _zeroed_grad_buffer(self, labelled)
-
-    def train_step(self, X, target, labelled, lr, weight_decay=0.0):
-        """One semi-supervised SGD step: forward with the pruned last layer -> softmax_ce_rows over labelled.rows (db[-1] from the loss
-        kernel) -> backward with the pruned last aggregation, no input gradient -> step.  X and target in the graph's ROW order
-        (g.to_new_order of vertex-order data); target is read at labelled rows only.  Returns the loss tensor."""
-        logits = self.forward(X, labelled=labelled)
-        loss, G = softmax_ce_rows(logits, target, labelled.rows, colsum_out=self.db[-1], grad_out=self.masked_grad_buffer(labelled))
-        self.backward(G, input_grad=False, have_last_bias_grad=True, labelled=labelled)
-        self.step(lr, weight_decay)
-        return loss
 
     def link_scores(self, X, edges):
         """Inner-product decoder on the stack's embeddings Z = forward(X): the logit <Z[i], Z[c]> of every pair (i, c) of the EdgeSet, in
@@ -1524,11 +1550,6 @@ class GcnStack:
         self.backward(dZ, input_grad=False)
         self.step(lr, weight_decay)
         return loss
-
-    def evaluate(self, X, target, rows):
-        """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows)).  rows: ascending
-        int32 rows of the graph (g.rows_of(mask) for a vertex-order validation / test mask)."""
-        return _loss_and_accuracy(self.forward(X), target, rows)
 
     def _field_logits(self, X, field):
         """[len(field.rows[L]), C] logits of the field's unique query rows (compact row k = graph row field.rows[L][k]), each layer a
@@ -1582,7 +1603,7 @@ class GcnStack:
         return _loss_and_accuracy(logits, t, field.compact_rows)
 
 
-class GatStack:
+class GatStack(_Stack):
     """L graph-attention layers (GAT, Velickovic et al. 2018) on one graph, the surface of GcnStack.  Layer l has heads[l] heads of width
     D = dims[l+1] / heads[l]; per head
         H = h W^T;   el = H a_l,  er = H a_r;   alpha_ic = softmax over the stored entries c of row i of leaky_relu(el_i + er_c);
@@ -1610,10 +1631,9 @@ class GatStack:
     A vertex without entries (only possible without the diagonal) has an empty softmax: its row is the bias alone."""
 
     def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda", heads=None):
-        self.g = g
+        self._bind(g)
         self.dims = list(dims)
         self.negative_slope = float(negative_slope)
-        self.map_t = g.attention_map()
         L = len(dims) - 1
         heads = [1] * L if heads is None else list(heads)
         if len(heads) != L or any(int(k) != k or k < 1 for k in heads):
@@ -1638,15 +1658,16 @@ class GatStack:
         self._saved = None
         self._buf = {}
 
-    def _tmp(self, key, shape, device, zero=False):
-        t = self._buf.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[key] = (torch.zeros if zero else torch.empty)(shape, dtype=torch.float32, device=device)
-        return t
+    def _bind(self, g):
+        self.g = g
+        self.map_t = g.attention_map()
+        return self
 
-    def grad_buffer(self):
-        """Where the loss should write dlogits ([n, dims[-1]])."""
-        return self._tmp("G", (self.g.n, self.dims[-1]), self.W[0].device)
+    def params(self):
+        return self.W + self.A + self.b
+
+    def grads(self):
+        return self.dW + self.dA + self.db
 
     def attention(self, H, l):
         """(ER, alpha) of layer l from H = h W_l^T: ER = H A^T as [n, 2 Hh] (el of head h in column h, er in column Hh + h), alpha entry-major
@@ -1694,12 +1715,12 @@ class GatStack:
             colsum(G, out=self.db[L - 1])
         for l in reversed(range(L)):
             h, H, ER, alpha, _ = self._saved[l]
-            Hh, dev = self.heads[l], G.device
+            Hh = self.heads[l]
             dalpha = self._vals_grad(l, G, H)
-            dER = self._tmp(("dER", Hh), (n, 2 * Hh), dev)                                # left half: del, right half: der
+            dER = self._tmp(("dER", Hh), (n, 2 * Hh))                                     # left half: del, right half: der
             dt, _ = edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, rowterm=ER[:, :Hh], colterm=ER[:, Hh:],
                                            negative_slope=self.negative_slope, drowterm_out=dER[:, :Hh])
-            vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh), dev)
+            vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh))
             self._to_transposed(dt, vals_t)
             csr_rowsum_heads(g.rowptr_t, vals_t, out=dER[:, Hh:])                         # der: what flows back to a column's vertex
             self._to_transposed(alpha, vals_t)
@@ -1720,38 +1741,18 @@ class GatStack:
             gather_rows(vals.reshape(int(vals.shape[0]), -1), self.map_t, out=out.reshape(int(out.shape[0]), -1))
         return out
 
-    def step(self, lr, weight_decay=0.0):
-        for p, gr in zip(self.W + self.A + self.b, self.dW + self.dA + self.db):
-            sgd_step(p, gr, lr, weight_decay)
-
-    def train_step(self, X, target, rows, lr, weight_decay=0.0):
-        """One SGD step on the listed rows: forward -> softmax_ce_rows over `rows` (db[-1] from the loss kernel) -> backward without an
-        input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)); target is read at listed rows only.  No layer is
-        pruned to the listed rows.  Returns the loss tensor."""
-        logits = self.forward(X)
-        loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=_zeroed_grad_buffer(self, rows))
-        self.backward(G, input_grad=False, have_last_bias_grad=True)
-        self.step(lr, weight_decay)
-        return loss
-
-    def evaluate(self, X, target, rows):
-        """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows))."""
-        return _loss_and_accuracy(self.forward(X), target, rows)
-
 
 def relu_mask(Y, dY, out=None):
     """out = dY where Y > 0, else 0 -- ReLU's backward from its stored output (gnnx_bn_relu_bwd_f32 without statistics)."""
     N, F = Y.shape
     out = torch.empty_like(dY) if out is None else out
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_bn_workspace", N, F, C.byref(wsb))
-    ws = _workspace(wsb.value, Y.device, "bn")
+    ws, wsb = _scratch("gnnx_bn_workspace", N, F, device=Y.device, tag="bn")
     capi.call("gnnx_bn_relu_bwd_f32", _ptr(Y), _ld(Y), _ptr(Y), _ld(Y), _ptr(dY), _ld(dY), N, F, None, None, 0.0, None, None, 1, _ptr(out), _ld(out),
-              None, None, _ptr(ws), wsb.value, _stream())
+              None, None, _ptr(ws), wsb, _stream())
     return out
 
 
-class SageStack:
+class SageStack(_Stack):
     """L GraphSAGE layers (Hamilton et al. 2017) on one graph, the surface of GatStack: the vertex keeps a weight of its own,
         M = agg_j h_j over the STORED columns j of row i;   h' = act( h W_s^T + M W_n^T + b ),  ReLU between layers, none after the last.
     aggr="mean": M = inv_deg (.) (A . h) with inv_deg[i] = 1 / deg_i (one correctly rounded division; 0 for an empty row) -- the planned
@@ -1785,43 +1786,31 @@ class SageStack:
         else:
             deg = (g.rowptr[1:] - g.rowptr[:-1]).cpu().to(torch.float32)      # the division on the host: IEEE, rounded once
             self.inv_deg = torch.where(deg > 0, 1.0 / deg, torch.zeros_like(deg)).to(g.rowptr.device)
+        return self
+
+    def params(self):
+        return self.W_s + self.W_n + self.b
+
+    def grads(self):
+        return self.dW_s + self.dW_n + self.db
 
     def on_graph(self, g):
         """This stack on another graph over the same vertices -- a sample of its neighbourhoods: a SageStack that SHARES this one's
-        parameters, gradients and scratch buffers (the same tensors: a step through either is a step of both) and has its own
-        inv_deg / map_t.  The training surface of neighbour sampling:
+        parameters, gradients and scratch buffers (the same tensors and the same table, the gradient buffer's zeroed-rows mark
+        included: a step through either is a step of both) and has its own inv_deg / map_t.  The training surface of neighbour sampling:
             net.on_graph(g.sample_neighbors(k, seed=epoch)).train_step(X, target, rows, lr)
         while net.evaluate(...) keeps running on the full graph."""
         if g.n != self.g.n:
             raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
-        view = object.__new__(SageStack)
-        view.__dict__.update(self.__dict__)   # the parameter lists and the buffer table themselves, not copies
-        view._saved = None
-        view._bind(g)
-        return view
-
-    def _tmp(self, key, shape, device, dtype=torch.float32):
-        t = self._buf.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[key] = torch.empty(shape, dtype=dtype, device=device)
-        return t
-
-    # for which row list the gradient buffer is zero outside the rows the loss writes (_zeroed_grad_buffer): kept WITH the buffer, so
-    # that this stack and its on_graph views, which share the buffer, share that knowledge too
-    _grad_zeroed_for = property(lambda self: self._buf.get("zeroed_for"), lambda self, v: self._buf.__setitem__("zeroed_for", v))
-    _grad_set = property(lambda self: self._buf.get("zeroed_set"), lambda self, v: self._buf.__setitem__("zeroed_set", v))
-
-    def grad_buffer(self):
-        """Where the loss should write dlogits ([n, dims[-1]])."""
-        return self._tmp("G", (self.g.n, self.dims[-1]), self.W_s[0].device)
+        return self._view(share_buf=True)._bind(g)
 
     def _aggregate(self, l, h):
         """(M, arg) of layer l: the neighbourhood's mean (arg None) or its maximum with the winning entries."""
         g = self.g
-        M = self._tmp(("M", l), (g.n, self.dims[l]), h.device)
+        M = self._tmp(("M", l), (g.n, self.dims[l]))
         if self.aggr == "mean":
             return spmm(g.rowptr, g.colidx, h, out=M, rowscale=self.inv_deg, plan=g.plan), None
-        return spmm_reduce(g.rowptr, g.colidx, h, op="max", out=M, arg_out=self._tmp(("arg", l), (g.n, self.dims[l]), h.device, torch.int32))
+        return spmm_reduce(g.rowptr, g.colidx, h, op="max", out=M, arg_out=self._tmp(("arg", l), (g.n, self.dims[l]), torch.int32))
 
     def _aggregate_bwd(self, l, dM, arg, out):
         """out += the aggregation's gradient with respect to h."""
@@ -1837,9 +1826,9 @@ class SageStack:
         saved, h = [], X
         for l in range(L):
             M, arg = self._aggregate(l, h)
-            Z = gemm(h, self.W_s[l], transB=True, out=self._tmp(("Z", l), (n, self.dims[l + 1]), X.device))
+            Z = gemm(h, self.W_s[l], transB=True, out=self._tmp(("Z", l), (n, self.dims[l + 1])))
             gemm(M, self.W_n[l], transB=True, out=Z, beta=1.0)
-            Y = self._tmp(("Y", l), (n, self.dims[l + 1]), X.device)
+            Y = self._tmp(("Y", l), (n, self.dims[l + 1]))
             bias_add(Z, self.b[l], out=Y)
             if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
                 bn_relu_fwd(Y, relu=True, out=Y)
@@ -1861,32 +1850,14 @@ class SageStack:
             gemm(G, M, transA=True, out=self.dW_n[l])
             if l == 0 and not input_grad:
                 return None
-            dM = gemm(G, self.W_n[l], out=self._tmp(("dM", l), (n, self.dims[l]), G.device))
-            dh = gemm(G, self.W_s[l], out=self._tmp(("dh", l), (n, self.dims[l]), G.device))     # through the vertex itself
-            self._aggregate_bwd(l, dM, arg, dh)                                                  # + through its neighbourhood
+            dM = gemm(G, self.W_n[l], out=self._tmp(("dM", l), (n, self.dims[l])))
+            dh = gemm(G, self.W_s[l], out=self._tmp(("dh", l), (n, self.dims[l])))     # through the vertex itself
+            self._aggregate_bwd(l, dM, arg, dh)                                        # + through its neighbourhood
             if l == 0:
                 return dh
-            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l]), G.device))           # h = relu output of the layer below
+            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l])))           # h = relu output of the layer below
             colsum(G, out=self.db[l - 1])
         return G
-
-    def step(self, lr, weight_decay=0.0):
-        for p, gr in zip(self.W_s + self.W_n + self.b, self.dW_s + self.dW_n + self.db):
-            sgd_step(p, gr, lr, weight_decay)
-
-    def train_step(self, X, target, rows, lr, weight_decay=0.0):
-        """One SGD step on the listed rows: forward -> softmax_ce_rows over `rows` (db[-1] from the loss kernel) -> backward without an
-        input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)); target is read at listed rows only.  Returns the
-        loss tensor."""
-        logits = self.forward(X)
-        loss, G = softmax_ce_rows(logits, target, rows, colsum_out=self.db[-1], grad_out=_zeroed_grad_buffer(self, rows))
-        self.backward(G, input_grad=False, have_last_bias_grad=True)
-        self.step(lr, weight_decay)
-        return loss
-
-    def evaluate(self, X, target, rows):
-        """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows))."""
-        return _loss_and_accuracy(self.forward(X), target, rows)
 
 
 # ---- graph readout: segment pooling, graph batches, a classifier head (include/gnnx.h "graph readout") ----------------------------------
@@ -1926,11 +1897,9 @@ def segment_pool(segptr, X, op="sum", out=None, arg_out=None, want_arg=True):
         arg = torch.empty((n_seg, F), dtype=torch.int32, device=X.device) if arg_out is None else arg_out
         _pool_matrix(arg, (n_seg, F), torch.int32, "arg_out", "segment_pool")
     _pool_matrix(out, (n_seg, F), torch.float32, "out", "segment_pool")
-    wsb = C.c_size_t(0)
-    capi.call("gnnx_segment_pool_workspace", n_seg, n_rows, F, C.byref(wsb))
-    ws = _workspace(wsb.value, X.device, "pool")
+    ws, wsb = _scratch("gnnx_segment_pool_workspace", n_seg, n_rows, F, device=X.device, tag="pool")
     capi.call("gnnx_segment_pool_f32", POOL_OPS[op], n_seg, n_rows, F, _ptr(segptr), _ptr(X) if X.numel() else None, _ld(X), _ptr(out), _ld(out),
-              _ptr(arg), _ld(arg) if arg is not None else 0, _ptr(ws), wsb.value, _stream())
+              _ptr(arg), _ld(arg) if arg is not None else 0, _ptr(ws), wsb, _stream())
     return out, arg
 
 
@@ -2032,43 +2001,25 @@ class GraphBatch(CsrGraph):
         return self._batch
 
 
-def _stack_on_graph(net, g):
-    """`net` (GcnStack, GatStack or SageStack) on ANOTHER graph, of any vertex count: a stack of the same class that SHARES the
-    parameter and gradient tensors (a step through either is a step of both) and derives from g what the class's __init__ / _bind
-    derives from its graph -- g itself, SageStack's inv_deg / map_t, GatStack's map_t, GcnStack's gather_pitch -- with no saved
-    activations, no checked input and scratch buffers of its own (they are shaped by the vertex count)."""
-    view = object.__new__(type(net))
-    view.__dict__.update(net.__dict__)
-    view._saved = None
-    view._buf = {}
-    if isinstance(net, SageStack):
-        view._bind(g)
-    elif isinstance(net, GatStack):
-        view.g = g
-        view.map_t = g.attention_map()
-    elif isinstance(net, GcnStack):
-        view.g = g
-        view.gather_pitch = bool(g.plan is not None and g.plan_t is not None and (g.plan.hub_ids_structured() or g.plan_t.hub_ids_structured()))
-        view._checked_input = None
-        view._grad_zeroed_for = view._grad_set = None
-    else:
-        raise TypeError(f"GcnStack, GatStack or SageStack expected, got {type(net).__name__}")
-    return view
-
-
-class GraphClassifier:
+class GraphClassifier(_Model):
     """One answer per GRAPH of a GraphBatch: a readout and a linear head over any of the three stacks,
         Z = segment_pool(net.forward(X), pool) [B, dims[-1]];   logits = Z W_c^T + b_c   [B, n_classes],
-    trained through the readout.  The surface of the stacks: forward / backward / step / train_step / evaluate, and on_batch for an epoch
-    over mini-batches of any size.  Every operation is a C-ABI call: the stack's own, segment_pool, gemm, bias_add, softmax_ce (db_c from
-    the loss kernel), segment_pool_bwd into net.grad_buffer(), sgd_step.  No atomics on any value; the same bits every run."""
+    trained through the readout.  forward / backward / step / train_step / evaluate (no row selection: every graph of the batch counts),
+    and on_batch for an epoch over mini-batches of any size.  Every operation is a C-ABI call: the stack's own, segment_pool, gemm,
+    bias_add, softmax_ce (db_c from the loss kernel), segment_pool_bwd into net.grad_buffer(), sgd_step.  No atomics on any value; the
+    same bits every run.
+
+    The stack is bound to the batch with net._view()._bind(batch), for any vertex count: a stack of the same class on the same parameter
+    and gradient tensors, with what its _bind derives from the batch and scratch buffers of its own (they are shaped by the vertex count)."""
 
     def __init__(self, net, batch, n_classes, pool="mean", seed=0):
         if pool not in POOL_OPS:
             raise ValueError(f"pool must be 'sum', 'mean' or 'max', got {pool!r}")
         if not isinstance(batch, GraphBatch):
             raise TypeError("batch must be a GraphBatch")
-        self.net = net if net.g is batch else _stack_on_graph(net, batch)
+        if not isinstance(net, _Stack):
+            raise TypeError(f"GcnStack, GatStack or SageStack expected, got {type(net).__name__}")
+        self.net = net if net.g is batch else net._view()._bind(batch)
         self.batch, self.pool, self.n_classes = batch, pool, int(n_classes)
         d = self.net.dims[-1]
         dev = batch.graph_ptr.device
@@ -2085,19 +2036,13 @@ class GraphClassifier:
             for b in batches: clf.on_batch(b).train_step(X_b, target_b, lr)"""
         if not isinstance(batch, GraphBatch):
             raise TypeError("batch must be a GraphBatch")
-        view = object.__new__(GraphClassifier)
-        view.__dict__.update(self.__dict__)
-        view.net = _stack_on_graph(self.net, batch)
-        view.batch = batch
-        view._saved = None
-        view._buf = {}
-        return view
+        return self._view(net=self.net._view()._bind(batch), batch=batch)
 
-    def _tmp(self, key, shape, dtype=torch.float32):
-        t = self._buf.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[key] = torch.empty(shape, dtype=dtype, device=self.W_c.device)
-        return t
+    def params(self):
+        return self.net.params() + [self.W_c, self.b_c]
+
+    def grads(self):
+        return self.net.grads() + [self.dW_c, self.db_c]
 
     def forward(self, X):
         """logits [B, n_classes]; the pooled Z [B, dims[-1]] is kept (self.Z) with the readout's arg for backward."""
@@ -2120,11 +2065,6 @@ class GraphClassifier:
         dZ = gemm(dlogits, self.W_c, out=self._tmp("dZ", tuple(Z.shape)))
         dH = segment_pool_bwd(self.batch.graph_ptr, dZ, self.pool, arg=arg, out=self.net.grad_buffer())
         self.net.backward(dH, input_grad=False)
-
-    def step(self, lr, weight_decay=0.0):
-        self.net.step(lr, weight_decay)
-        sgd_step(self.W_c, self.dW_c, lr, weight_decay)
-        sgd_step(self.b_c, self.db_c, lr, weight_decay)
 
     def train_step(self, X, target, lr, weight_decay=0.0):
         """One SGD step on the batch: forward -> softmax_ce over the B graphs (db_c from the loss kernel) -> backward through the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Measurement (GPU box): the semi-supervised training step of ops.GcnStack with the last layer pruned to the labelled rows
-(train_step(labelled=...)) against the same masked step on the full CSR, in ONE process with the variants alternated:
+(train_step with a LabelledSet) against the same masked step on the full CSR, in ONE process with the variants alternated:
 
     unpruned (A) | pruned | unpruned (B) | unmasked, each a block of --steps steps between two device events, --rounds times
 
@@ -107,8 +107,8 @@ def main():
 
         def unmasked():
             logits = net.forward(X)
+            # (grad_buffer() drops the stack's zeroed-rows mark: the buffer now holds every row)
             _, dlog = ops.softmax_ce(logits, target_all, colsum_out=net.db[-1], grad_out=net.grad_buffer())
-            net._grad_zeroed_for = None                                     # the buffer now holds every row
             net.backward(dlog, input_grad=False, have_last_bias_grad=True)
             net.step(lr)
 
