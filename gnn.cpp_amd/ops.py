@@ -234,6 +234,20 @@ class CsrGraph:
             g.make_plans(*self._plan_args)
         return g
 
+    def sample_negatives(self, m, seed, positives=None, exclude_self=True):
+        """(neg int32 [nnz_pos, m], n_unfilled): m non-neighbours per positive, drawn from the columns its row does not hold in this
+        graph's forward CSR (sample_negatives; the row itself excluded too).  positives: an EdgeSet or a (rowptr, colidx) pair on this
+        graph's rows -- a training split, held-out edges --, default the graph itself.  GnnxError on a relabelled graph, with
+        attention_map's reasoning: its rows are not ascending, and the selection searches them."""
+        if self.nid is not None:
+            raise capi.GnnxError(-7, "sample_negatives", "a relabelled graph keeps each row in original-id order, not ascending: the "
+                                 "selection cannot search it (build the graph without relabel)")
+        rowptr, colidx = (self.rowptr, self.colidx) if positives is None else _pattern_of(positives, "sample_negatives")
+        if int(rowptr.numel()) != self.n + 1:
+            raise capi.GnnxError(-2, "sample_negatives", f"the positives have {int(rowptr.numel()) - 1} rows, the graph {self.n}")
+        return sample_negatives(rowptr, m, seed, excluded=(self.rowptr, self.colidx), n_cols=self.n, exclude_self=exclude_self,
+                                nnz=None if colidx is None else int(colidx.numel()))
+
     def mask_in_row_order(self, mask):
         """A vertex-order mask ([n] bool / uint8, vertex v at position v) as uint8 in this graph's row order (vertex v at nid[v])."""
         if int(mask.numel()) != self.n:
@@ -404,6 +418,100 @@ def sample_neighbors(rowptr, colidx, k, seed, want_pos=False, want_rowid=False):
     # (an empty result stays a view of its 1-element buffer, as csr_restrict's: the aggregation wants a device pointer)
     shrink = lambda t: None if t is None else (t[:m] if m else t[:0])  # noqa: E731
     return rowptr_o, shrink(colidx_o), shrink(pos_o), shrink(rowid_o)
+
+
+NEG_EXCLUDE_SELF = 1
+
+
+def _pattern_of(positives, where):
+    """(rowptr, colidx or None) of a positives argument: an EdgeSet / CsrGraph (its forward pattern) or a (rowptr, colidx) pair."""
+    if hasattr(positives, "rowptr") and hasattr(positives, "colidx"):
+        return positives.rowptr, positives.colidx
+    if isinstance(positives, (tuple, list)) and len(positives) == 2:
+        return positives[0], positives[1]
+    raise capi.GnnxError(-1, where, "positives: an EdgeSet, a CsrGraph or a (rowptr, colidx) pair expected")
+
+
+def sample_negatives(rowptr, m, seed, excluded=None, n_cols=None, exclude_self=True, nnz=None):
+    """gnnx_csr_sample_negatives: for every entry of the positives pattern `rowptr` (int32 [n_rows + 1]; only the row structure is read;
+    nnz = rowptr[-1], read from the device when not given) m columns drawn uniformly from the columns that the entry's row does NOT hold
+    in `excluded` = (rowptr_ex, colidx_ex) -- same rows, n_cols columns (default: n_rows), rows strictly ascending; None: nothing is
+    excluded -- nor, with exclude_self, the row's own id.  -> (neg int32 [nnz, m], entry-major; n_unfilled): a row that holds every
+    column has nothing to draw, its draws are -1 and counted in n_unfilled.  Exact, without a rejection loop; the m draws of a positive
+    are independent and may repeat.  The same (seed, m) gives the same draws on every run; use one seed per epoch."""
+    n_rows, dev = int(rowptr.numel() - 1), rowptr.device
+    n_cols = n_rows if n_cols is None else int(n_cols)
+    m = int(m)
+    nnz = (int(rowptr[-1]) if n_rows >= 0 and rowptr.numel() else 0) if nnz is None else int(nnz)
+    if excluded is None:
+        rowptr_ex, colidx_ex = torch.zeros(n_rows + 1, dtype=torch.int32, device=dev), None
+    else:
+        rowptr_ex, colidx_ex = excluded
+        if int(rowptr_ex.numel()) != n_rows + 1:
+            raise capi.GnnxError(-2, "sample_negatives", f"the excluded pattern has {int(rowptr_ex.numel()) - 1} rows, the positives {n_rows}")
+    nnz_ex = 0 if colidx_ex is None else int(colidx_ex.numel())
+    neg = torch.empty((nnz, max(m, 0)), dtype=torch.int32, device=dev)
+    ws = _workspace(256, dev, "negatives")
+    unfilled = C.c_int64(0)
+    capi.call("gnnx_csr_sample_negatives", n_rows, n_cols, nnz, _ptr(rowptr), nnz_ex, _ptr(rowptr_ex), _ptr(colidx_ex) if nnz_ex else None, m,
+              int(seed) & (2 ** 64 - 1), NEG_EXCLUDE_SELF if exclude_self else 0, _ptr(neg) if neg.numel() else None, C.byref(unfilled), _ptr(ws),
+              ws.numel(), _stream())
+    return neg, unfilled.value
+
+
+def rank_counts(pos_scores, neg_scores, neg=None):
+    """gnnx_rank_counts_f32: (greater, equal, valid) int32 [P] for positive scores [P] and negative scores [P, m] (or [P * m],
+    entry-major): the number of a positive's negatives that score higher, the same, and that were compared at all.  Draws with
+    neg[p, t] < 0 (unfilled, sample_negatives) are skipped; IEEE comparisons: -0 == +0, a NaN on either side counts in none of the
+    three, so valid - greater - equal is the number that score lower."""
+    P = int(pos_scores.numel())
+    if P == 0 or int(neg_scores.numel()) % P:
+        if P or int(neg_scores.numel()):
+            raise capi.GnnxError(-2, "rank_counts", f"{int(neg_scores.numel())} negative scores for {P} positives")
+        m = 1
+    else:
+        m = int(neg_scores.numel()) // P
+    assert pos_scores.is_contiguous() and neg_scores.is_contiguous() and pos_scores.dtype == neg_scores.dtype == torch.float32
+    if neg is not None:
+        assert neg.is_contiguous() and neg.dtype == torch.int32 and neg.numel() == neg_scores.numel()
+    out = torch.empty((3, max(P, 1)), dtype=torch.int32, device=pos_scores.device)
+    capi.call("gnnx_rank_counts_f32", P, m, _ptr(pos_scores) if P else None, _ptr(neg_scores) if P else None,
+              _ptr(neg) if (neg is not None and P) else None, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream())
+    return out[0, :P], out[1, :P], out[2, :P]
+
+
+def link_metrics(pos_scores, neg_scores, neg=None, ks=(10, 50, 100)):
+    """Ranking metrics of a link model from rank_counts -- integers, so every figure is exact in any summation order.  -> dict:
+      mrr           mean of 1 / (1 + greater + equal): the PESSIMISTIC rank (ties rank the positive last), in float64
+      hits@K        share of positives with greater + equal < K, for every K of ks
+      auc_grouped   (sum(valid - greater - equal) + sum(equal) / 2) / sum(valid): each positive against its own negatives
+      auc           the global AUC of all positive scores against all valid negative scores, ties count 1/2 (formed in int64 by a
+                    sort and two searches -- plumbing)
+      auc_fraction, auc_grouped_fraction   (numerator, denominator) of the two as Python ints, over twice the number of pairs
+      n_pos, n_valid   positives, and compared (positive, own negative) pairs
+    NaN rule: a NaN score counts as neither above nor below anything.  rank_counts leaves such a comparison out of greater, equal AND
+    valid; the global AUC leaves NaN positives and NaN negatives out of numerator and denominator.  A positive without a compared
+    negative (a NaN score, a complete row) has rank 1.  A metric whose denominator is 0 is NaN."""
+    P = int(pos_scores.numel())
+    greater, equal, valid = (t.long() for t in rank_counts(pos_scores, neg_scores, neg))
+    ge = greater + equal
+    nan = float("nan")
+    out = {"n_pos": P, "n_valid": int(valid.sum())}
+    out["mrr"] = float((1.0 / (1 + ge).double()).mean()) if P else nan
+    for k in ks:
+        out[f"hits@{int(k)}"] = int((ge < int(k)).sum()) / P if P else nan
+    num, den = int(2 * (valid - ge).sum() + equal.sum()), 2 * out["n_valid"]
+    out["auc_grouped_fraction"], out["auc_grouped"] = (num, den), num / den if den else nan
+    q = neg_scores.reshape(-1)
+    keep = ~q.isnan() if neg is None else (~q.isnan()) & (neg.reshape(-1) >= 0)
+    qs, _ = torch.sort(q[keep] + 0.0)          # (+ 0.0: one zero, whatever the sort makes of -0 against +0)
+    s = pos_scores.reshape(-1)
+    s = s[~s.isnan()] + 0.0
+    below = torch.searchsorted(qs, s, right=False)
+    upto = torch.searchsorted(qs, s, right=True)
+    num, den = int((below + upto).sum()), 2 * int(s.numel()) * int(qs.numel())
+    out["auc_fraction"], out["auc"] = (num, den), num / den if den else nan
+    return out
 
 
 class ReceptiveField:
@@ -599,12 +707,33 @@ class EdgeSet:
         (1 = an edge, 0 = a non-edge; soft labels allowed); n: the number of vertices.  The pattern is built with
         csr_from_coo_weighted(src, dst, label, DIAG_KEEP): of duplicate pairs the LAST one in the list wins, and explicit 0 labels stay
         as entries.  So negatives concatenated BEFORE the positives lose a collision with a positive: a sampled "non-edge" that is in
-        fact an edge is scored as the edge it is.  Uniform negatives: rmat_edges(seed, n, k, a=.25, b=.25, c=.25)."""
+        fact an edge is scored as the edge it is.  Uniform negatives: rmat_edges(seed, n, k, a=.25, b=.25, c=.25); negatives drawn from
+        the non-edges of a graph: from_graph."""
         src, dst = src.to(torch.int32).contiguous(), dst.to(torch.int32).contiguous()
         label = label.to(torch.float32).contiguous()
         rowptr, colidx, target = csr_from_coo_weighted(src, dst, label, n, DIAG_KEEP)
         rowptr_t, colidx_t, _ = csr_from_coo_weighted(dst, src, label, n, DIAG_KEEP)
         return cls(n, rowptr, colidx, target, rowptr_t, colidx_t, csr_transpose_map(rowptr, colidx, rowptr_t, colidx_t))
+
+    @classmethod
+    def from_graph(cls, g, m, seed, positives=None):
+        """The positives (an EdgeSet or a (rowptr, colidx) pair on g's rows; default: every stored entry of g) with target 1 and m
+        negatives per positive with target 0, drawn by g.sample_negatives(m, seed, positives): the destination of each positive
+        replaced by a column its row does not hold in g, never the row itself.  Built through from_pairs with the negatives listed
+        BEFORE the positives, as its docstring prescribes; a negative is never an edge of g, so it can only collide with another
+        negative: repeated draws of one row collapse into one entry there, and unfilled draws (rows that hold every column) are
+        dropped -- the pattern holds at most nnz_pos * (1 + m) entries.  link_train_step(X, EdgeSet.from_graph(g, 1, seed=epoch), lr)
+        is an epoch with fresh negatives."""
+        rowptr, colidx = (g.rowptr, g.colidx) if positives is None else _pattern_of(positives, "from_graph")
+        neg, _ = g.sample_negatives(m, seed, (rowptr, colidx))
+        deg = (rowptr[1:] - rowptr[:-1]).long()
+        rows = torch.repeat_interleave(torch.arange(g.n, dtype=torch.int32, device=rowptr.device), deg)
+        nsrc, ndst = torch.repeat_interleave(rows, int(m)), neg.reshape(-1)
+        keep = ndst >= 0
+        nsrc, ndst = nsrc[keep], ndst[keep]
+        label = torch.cat([torch.zeros(nsrc.numel(), dtype=torch.float32, device=rows.device),
+                           torch.ones(rows.numel(), dtype=torch.float32, device=rows.device)])
+        return cls.from_pairs(torch.cat([nsrc, rows]), torch.cat([ndst, colidx.to(torch.int32)]), label, g.n)
 
     def to_transposed(self, vals, out=None):
         """Per-entry values of the pattern in the transposed pattern's order: out[q] = vals[map_t[q]]."""
@@ -1550,6 +1679,18 @@ class GcnStack(_Stack):
         self.backward(dZ, input_grad=False)
         self.step(lr, weight_decay)
         return loss
+
+    def link_evaluate(self, X, g, positives, m, seed, ks=(10, 50, 100)):
+        """link_metrics of held-out edges: every positive (an EdgeSet or a (rowptr, colidx) pair on g's rows) against m negatives drawn
+        by g.sample_negatives(m, seed, positives).  Z = forward(X); the positive scores are sddmm on the positives' pattern, the
+        negative scores sddmm on (rowptr * m, neg): the entry-major layout makes a row's draws one contiguous row of that pattern, so
+        the scores carry sddmm's bit contract.  An unfilled draw (-1) is scored at column 0 and skipped by the rank counts."""
+        rowptr, colidx = _pattern_of(positives, "link_evaluate")
+        neg, _ = g.sample_negatives(m, seed, (rowptr, colidx))
+        Z = self.forward(X)
+        pos_scores = sddmm(rowptr, colidx, Z, Z)
+        neg_scores = sddmm(rowptr * int(m), neg.reshape(-1).clamp(min=0), Z, Z)
+        return link_metrics(pos_scores, neg_scores.reshape(-1, int(m)), neg, ks)
 
     def _field_logits(self, X, field):
         """[len(field.rows[L]), C] logits of the field's unique query rows (compact row k = graph row field.rows[L][k]), each layer a

@@ -952,6 +952,67 @@ int gnnx_csr_sample_neighbors(int32_t n_rows, int64_t nnz, const int32_t *d_rowp
                               int32_t *d_rowptr_out, int32_t *d_colidx_out, int32_t *d_pos_out, int32_t *d_rowid_out,
                               int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ negative sampling, ranking --- */
+/*
+ * The negative half of link prediction: for every stored entry of a POSITIVES pattern, m columns drawn uniformly from the columns its
+ * row does NOT hold in an EXCLUDED pattern (normally the whole graph), and the per-positive counts that MRR, Hits@K and AUC are made
+ * of.  The contract is this comment, restated with Python sets and integers by tests/negative_ref.py.
+ *
+ * gnnx_csr_sample_negatives.  The positives pattern is (d_rowptr_pos, nnz_pos) on n_rows rows: only its row structure is read.  The
+ * excluded pattern (d_rowptr_ex, d_colidx_ex) has the same n_rows rows, n_cols columns, and STRICTLY ASCENDING rows (what every
+ * gnnx_csr_from_coo build gives).  Take entry j (offset within its row) of row i of the positives -- entry p = rowptr_pos[i] + j --
+ * and a draw t < m:
+ *   S_i   = row i of the excluded pattern, d = |S_i|;   E = S_i, plus {i} when flags has GNNX_NEG_EXCLUDE_SELF and i < n_cols
+ *   count = n_cols - |E|
+ *   s     = splitmix64(seed ^ 0x6E65676174697665)                 a domain constant: independent of the neighbour sampler's draw
+ *                                                                 under the same seed
+ *   h     = splitmix64( splitmix64( s ^ (((uint64)i << 32 | (uint64)j) * 0x9E3779B97F4A7C15) ) ^ ((uint64)t * 0x9E3779B97F4A7C15) )
+ *                                                                 the finaliser of the neighbour sampler; products wrap in 64 bits
+ *   r     = floor(h * count / 2^64)                               the high 64 bits of the 128-bit product: bias <= count / 2^64
+ *   d_neg[p * m + t] = the r-th smallest element (from 0) of [0, n_cols) \ E
+ * Exact and bounded: there is no rejection loop and no spin.  count == 0 (a complete row): d_neg[p * m + t] = -1 for every t, and the
+ * positive adds m to the unfilled counter -- a counter atomic on an integer, the only atomic: the same bits on every run.  The m draws
+ * of one positive are independent and may repeat.  The result is a function of (seed, i, j, t, S_i, n_cols, flags) alone, however
+ * positives and draws are mapped to lanes.  A different seed gives an independent draw; a caller uses one seed per epoch.
+ *
+ * The selection needs no list of non-members.  For the ascending c_0 < .. < c_{d-1} of S_i, g(x) = c_x - x is non-decreasing, and
+ * with J(r) = #{x : g(x) <= r} (one upper-bound search) the r-th non-member of S_i is r + J(r).  With the self flag set, i < n_cols
+ * and i not in S_i (one lower-bound search): if r + J(r) >= i the answer is (r + 1) + J(r + 1), otherwise r + J(r).  O(log d)
+ * dependent loads per negative.
+ *
+ * Outputs: d_neg [nnz_pos, m] int32, entry-major like the per-head arrays; *n_unfilled_out (HOST) = the number of -1 entries, valid
+ * on return: the call synchronises `stream`, as gnnx_csr_sample_neighbors does.
+ *
+ * Statuses.  GNNX_ERR_INVALID_ARG before any device call: negative sizes, m < 1, nnz_pos * m >= 2^31, nnz_ex >= 2^31, a null
+ * rowptr_pos / rowptr_ex / n_unfilled_out, a null d_neg with nnz_pos > 0, a null colidx_ex with nnz_ex > 0.  GNNX_ERR_WORKSPACE with
+ * nothing written: a workspace that is NULL or smaller than GNNX_NEG_WORKSPACE_BYTES (it holds the counter, keeps nothing between
+ * calls and may sit at any address).  n_rows == 0 or nnz_pos == 0 is a valid empty result (*n_unfilled_out = 0, no device call).
+ * Both patterns, nnz_pos (= rowptr_pos[n_rows]) and nnz_ex are TRUSTED, as everywhere else: with an excluded column outside
+ * [0, n_cols) or a row that is not strictly ascending the values of that row's draws are unspecified; no access is ever out of range.
+ *
+ * Kernel (gnnx_negative.hip): work is dealt in the entry domain, as in gnnx_sddmm_csr_f32: a wavefront owns GNNX_NEG_RUN consecutive
+ * positives and finds the rows of its first and last one in rowptr_pos, so a hub row spreads over the device without a plan; the
+ * (positive, draw) items of the run go to the lanes draw-fastest, so the m draws of a positive sit on adjacent lanes, search the same
+ * row and share the loads of the search's top levels.  Offsets are 64-bit.
+ *
+ * gnnx_rank_counts_f32.  For positive scores s[n_pos] and negative scores q[n_pos, m] (entry-major), with an optional d_neg[n_pos, m]
+ * whose entries < 0 mark draws to SKIP (NULL: none is skipped):
+ *   greater[p] = #{t : q[p,t] >  s[p]}     equal[p] = #{t : q[p,t] == s[p]}     valid[p] = #{t : q[p,t] <, == or > s[p]}
+ * over the draws that are not skipped.  Comparisons are IEEE: -0 == +0, and a NaN on either side is counted in none of the three --
+ * valid[p] - greater[p] - equal[p] is exactly #{t : q[p,t] < s[p]}.  One streaming pass of m loads per positive (a lane group of
+ * 1 .. 64 lanes by m), integer sums, no atomics; asynchronous on `stream`.  Every metric is a function of these integers, so it is exact in any
+ * summation order.  GNNX_ERR_INVALID_ARG: negative n_pos, n_pos >= 2^31, m < 1, a null pointer among s, q, greater, equal, valid
+ * with n_pos > 0.
+ */
+#define GNNX_NEG_EXCLUDE_SELF 1u
+#define GNNX_NEG_RUN 64
+#define GNNX_NEG_WORKSPACE_BYTES 256
+int gnnx_csr_sample_negatives(int32_t n_rows, int32_t n_cols, int64_t nnz_pos, const int32_t *d_rowptr_pos, int64_t nnz_ex,
+                              const int32_t *d_rowptr_ex, const int32_t *d_colidx_ex, int32_t m, uint64_t seed, uint32_t flags,
+                              int32_t *d_neg, int64_t *n_unfilled_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_rank_counts_f32(int64_t n_pos, int32_t m, const float *d_pos_scores, const float *d_neg_scores, const int32_t *d_neg,
+                         int32_t *d_greater, int32_t *d_equal, int32_t *d_valid, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */
