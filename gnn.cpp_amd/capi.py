@@ -138,6 +138,13 @@ _SIGS = {
     "gnnx_softmax_ce_colsum_f32": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_softmax_ce_partial_f32": [_vp, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_sgd_step_f32": [_vp, _vp, _i64, _f32, _f32, _vp],
+    "gnnx_optim_table_bytes": [_i32, C.POINTER(_sz)],
+    "gnnx_optim_table_build": [_i32, _vp, _vp, _vp, _vp, _sz, C.POINTER(_i64), C.POINTER(_i64), _vp],
+    "gnnx_adam_bias_corrections": [_f32, _f32, _i64, C.POINTER(_f32), C.POINTER(_f32)],
+    "gnnx_adam_step_f32": [_vp, _i32, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, C.c_int, _vp, _vp],
+    "gnnx_momentum_step_f32": [_vp, _i32, _i64, _vp, _f32, _f32, _f32, C.c_int, C.c_int, _f32, _vp, _vp],
+    "gnnx_grad_sqnorm_workspace": [C.POINTER(_sz)],
+    "gnnx_grad_sqnorm_f32": [_vp, _i32, _f32, _vp, _vp, _vp, _sz, _vp],
     "gnnx_bce_logits_workspace": [_i64, C.POINTER(_sz)],
     "gnnx_bce_logits_f32": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp],
     "gnnx_sddmm_csr_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],

@@ -122,11 +122,19 @@ float accuracy(const cyg::tptr<float> logits, const cyg::tptr<int> target, cyg::
 // Optimisers over device-resident parameters (reference nn.h:156-191).  SGD is the textbook update
 // p -= lr * (g + weight_decay * p) (+ momentum buffers); the reference's step() reads an empty velocity vector
 // (nn.cpp:414) and cannot run, so there is nothing to be bit-compatible with.
+// With momentum (and for Adam) a step is ONE launch over all parameters: gnnx_momentum_step_f32 / gnnx_adam_step_f32 on a parameter
+// table (include/gnnx.h, "optimisers"), whose arithmetic -- one float32 rounding per operation -- is the contract; momentum == 0
+// stays the per-tensor gnnx_sgd_step_f32.  Parameters without a device gradient are skipped; which ones those are must not change
+// between the steps of one optimiser (the state is laid out over the ones that take part).
+struct OptimTable;   // the device table, its state arenas and the step count (host.cpp)
 class Optimizer {
 public:
     explicit Optimizer(std::vector<cyg::tptr<float>> parameters) : _parameters(std::move(parameters)) {}
     void zero_grad();
     std::vector<cyg::tptr<float>> _parameters;
+
+protected:
+    std::shared_ptr<OptimTable> _table;
 };
 
 class SGD : public Optimizer {
@@ -140,6 +148,20 @@ public:
     void step();
     float _lr, _dampening, _momentum, _weight_decay;
     bool _nestorov;
+};
+
+// Adam (reference nn.h:180-190, the constructor's order).  The reference's default `eps = 10 - 8` is 2, and its step() multiplies
+// sqrt(v) by `_eps` where the update adds eps, sets the parameter to `g - ...` (the gradient, not the parameter, minus the update) and
+// corrects with pow(b, i + 1) over the PARAMETER index i (nn.cpp:428-441): it cannot run meaningfully, so there is nothing to be bit-compatible with.  The update is the
+// textbook one (Kingma & Ba 2015) with bias corrections 1 - b^t over the STEP count t, eps = 1e-8 by default, no weight decay.
+class Adam : public Optimizer {
+public:
+    Adam(std::vector<cyg::tptr<float>> parameters, float lr, float b1, float b2, float eps = 1e-8f)
+        : Optimizer(std::move(parameters)), _lr(lr), _b1(b1), _b2(b2), _eps(eps)
+    {
+    }
+    void step();
+    float _lr, _b1, _b2, _eps;
 };
 
 }  // namespace nn

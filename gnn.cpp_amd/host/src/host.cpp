@@ -751,14 +751,88 @@ void Optimizer::zero_grad()
     for (auto &p : _parameters) p->zero_grad();
 }
 
+// The parameter table of gnnx_optim_table_build over the parameters that have a device gradient, the zeroed state arenas and the
+// step count.  A tensor's device buffers may move between steps (zero_grad() starts a new gradient store): the table is rebuilt
+// whenever an address differs from the one it holds.  The state's layout depends on the sizes alone, so it survives a rebuild; a
+// step over other sizes (another set of parameters with a gradient) is refused.
+struct OptimTable {
+    std::vector<float *> params;
+    std::vector<const float *> grads;
+    std::vector<int64_t> sizes;
+    void *table = nullptr, *arena[2] = {nullptr, nullptr};
+    size_t table_bytes = 0, arena_bytes = 0;
+    int64_t n_chunks = 0, t = 0;
+
+    ~OptimTable()
+    {
+        if (table) cyg::detail::dev_free(table, table_bytes);
+        for (void *a : arena)
+            if (a) cyg::detail::dev_free(a, arena_bytes);
+    }
+
+    // bring the table up to date with the parameters' current addresses; n_state arenas (zeroed when first made)
+    void bind(std::vector<cyg::tptr<float>> &parameters, int n_state, const char *who)
+    {
+        std::vector<float *> p;
+        std::vector<const float *> g;
+        std::vector<int64_t> s;
+        for (auto &q : parameters) {
+            const float *gq = q->device_grad();
+            if (!gq) continue;
+            p.push_back(q->device_inplace());
+            g.push_back(gq);
+            s.push_back((int64_t)q->numel());
+        }
+        if (table && s != sizes) throw std::runtime_error(ERROR_BACKEND_UNSUPPORTED);   // the state is laid out over the first step's sizes
+        if (table && p == params && g == grads) return;
+        void *st = cyg::detail::current_stream();
+        if (!table) {
+            cyg::detail::gx(gnnx_optim_table_bytes((int32_t)s.size(), &table_bytes), who);
+            table = cyg::detail::dev_alloc(table_bytes);
+        }
+        int64_t elems = 0;
+        cyg::detail::gx(gnnx_optim_table_build((int32_t)s.size(), p.data(), g.data(), s.data(), table, table_bytes, &n_chunks, &elems, st), who);
+        if (!arena[0] && elems > 0) {
+            arena_bytes = sizeof(float) * (size_t)elems;
+            for (int k = 0; k < n_state; k++) {
+                arena[k] = cyg::detail::dev_alloc(arena_bytes);
+                cyg::detail::gx(gnnx_memset(arena[k], 0, arena_bytes, st), who);
+            }
+        }
+        params = std::move(p);
+        grads = std::move(g);
+        sizes = std::move(s);
+    }
+};
+
 void SGD::step()
 {
-    if (_momentum != 0) throw std::runtime_error(ERROR_BACKEND_UNSUPPORTED);  // plain SGD only (momentum: next)
-    for (auto &p : _parameters) {
-        float *g = p->device_grad();
-        if (!g) continue;
-        detail::gx(gnnx_sgd_step_f32(p->device_inplace(), g, (int64_t)p->numel(), _lr, _weight_decay, detail::current_stream()), "SGD");
+    if (_momentum == 0) {   // plain SGD: a launch per tensor, as ever
+        for (auto &p : _parameters) {
+            float *g = p->device_grad();
+            if (!g) continue;
+            detail::gx(gnnx_sgd_step_f32(p->device_inplace(), g, (int64_t)p->numel(), _lr, _weight_decay, detail::current_stream()), "SGD");
+        }
+        return;
     }
+    if (!_table) _table = std::make_shared<OptimTable>();
+    OptimTable &tb = *_table;
+    tb.bind(_parameters, 1, "SGD");
+    detail::gx(gnnx_momentum_step_f32(tb.table, (int32_t)tb.sizes.size(), tb.n_chunks, static_cast<float *>(tb.arena[0]), _lr, _momentum, _dampening,
+                                      _nestorov ? 1 : 0, tb.t == 0 ? 1 : 0, _weight_decay, nullptr, detail::current_stream()), "SGD");
+    tb.t++;
+}
+
+void Adam::step()
+{
+    if (!_table) _table = std::make_shared<OptimTable>();
+    OptimTable &tb = *_table;
+    tb.bind(_parameters, 2, "Adam");
+    float c1 = 0, c2 = 0;
+    detail::gx(gnnx_adam_bias_corrections(_b1, _b2, tb.t + 1, &c1, &c2), "Adam");
+    detail::gx(gnnx_adam_step_f32(tb.table, (int32_t)tb.sizes.size(), tb.n_chunks, static_cast<float *>(tb.arena[0]), static_cast<float *>(tb.arena[1]),
+                                  _lr, _b1, _b2, _eps, c1, c2, 0.0f, 0, nullptr, detail::current_stream()), "Adam");
+    tb.t++;
 }
 
 }  // namespace nn

@@ -1421,10 +1421,119 @@ def sgd_step(param, grad, lr, weight_decay=0.0):
     return param
 
 
+class _TableOptimizer:
+    """What Adam and Momentum share: the parameter table of gnnx_optim_table_build over a model's params() / grads(), built at the
+    first step together with zeroed state arenas (`n_state` of them), the step count `t`, and gradient clipping by the global norm
+    (max_grad_norm: gnnx_grad_sqnorm_f32 writes the scale on the device; the update reads it there).  A step is one launch -- two with
+    clipping -- however many tensors the model has.  The table holds addresses: a step on parameter or gradient tensors other than
+    the bound ones raises; it never rebuilds (the state would silently start over)."""
+
+    n_state = 1
+
+    def __init__(self, max_grad_norm=None):
+        if max_grad_norm is not None and not max_grad_norm >= 0:
+            raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm!r}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.t = 0
+        self._bound = None
+
+    def _bind(self, params, grads):
+        n = len(params)
+        for p, g in zip(params, grads):
+            if p.dtype != torch.float32 or g.dtype != torch.float32 or not (p.is_contiguous() and g.is_contiguous()) or p.numel() != g.numel():
+                raise ValueError("the optimiser needs contiguous float32 parameters with gradients of the same size")
+        dev = params[0].device
+        self._sizes = [p.numel() for p in params]
+        self._bound = [p.data_ptr() for p in params] + [g.data_ptr() for g in grads]
+        nbytes, chunks, elems = C.c_size_t(0), C.c_int64(0), C.c_int64(0)
+        capi.call("gnnx_optim_table_bytes", n, C.byref(nbytes))
+        self._table = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        capi.call("gnnx_optim_table_build", n, (C.c_void_p * n)(*self._bound[:n]), (C.c_void_p * n)(*self._bound[n:]),
+                  (C.c_int64 * n)(*self._sizes), _ptr(self._table), nbytes.value, C.byref(chunks), C.byref(elems), _stream())
+        self._n, self._chunks = n, chunks.value
+        self._arenas = [torch.zeros(max(elems.value, 1), dtype=torch.float32, device=dev) for _ in range(self.n_state)]
+        self._offsets = [sum((s + 3) // 4 * 4 for s in self._sizes[:k]) for k in range(n)]
+        ws = C.c_size_t(0)
+        capi.call("gnnx_grad_sqnorm_workspace", C.byref(ws))
+        self._norm_ws = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        self.sqnorm = torch.zeros(1, dtype=torch.float32, device=dev)    # of the last clipped step's gradients
+        self.gscale = torch.ones(1, dtype=torch.float32, device=dev)     # and the factor they were multiplied with
+
+    def step(self, params, grads, lr, weight_decay=0.0):
+        """One update of `params` from `grads` (the model's lists; _Model.step calls this)."""
+        if self._bound is None:
+            self._bind(params, grads)
+        now = [p.data_ptr() for p in params] + [g.data_ptr() for g in grads]
+        if now != self._bound:
+            k = next((i for i, (a, b) in enumerate(zip(now, self._bound)) if a != b), min(len(now), len(self._bound)))
+            raise RuntimeError(f"the optimiser is bound to {self._n} tensors at fixed addresses; "
+                               + (f"this step has {len(params)} tensors" if len(now) != len(self._bound) else
+                                  f"{'parameter' if k < self._n else 'gradient'} {k % self._n} has moved from {self._bound[k]:#x} to {now[k]:#x}")
+                               + " (one optimiser per model; its state is not rebuilt)")
+        scale = None
+        if self.max_grad_norm is not None:
+            capi.call("gnnx_grad_sqnorm_f32", _ptr(self._table), self._n, self.max_grad_norm, _ptr(self.sqnorm), _ptr(self.gscale),
+                      _ptr(self._norm_ws), self._norm_ws.numel(), _stream())
+            scale = self.gscale
+        self._update(float(lr), float(weight_decay), _ptr(scale))
+        self.t += 1
+
+    def _views(self, arena):
+        return [arena[o:o + s] for o, s in zip(self._offsets, self._sizes)]
+
+
+class Adam(_TableOptimizer):
+    """Adam (Kingma & Ba 2015); decoupled=True: AdamW (Loshchilov & Hutter 2019).  The arithmetic is include/gnnx.h's, one float32
+    rounding per operation; the betas are rounded to float32 once, here; the bias corrections 1 - beta^t come from
+    gnnx_adam_bias_corrections.  net.set_optimizer(ops.Adam()) -- lr and weight_decay stay arguments of step / train_step."""
+
+    n_state = 2
+
+    def __init__(self, betas=(0.9, 0.999), eps=1e-8, decoupled=False, max_grad_norm=None):
+        super().__init__(max_grad_norm)
+        self.b1, self.b2 = (C.c_float(b).value for b in betas)
+        if not (0.0 <= self.b1 < 1.0 and 0.0 <= self.b2 < 1.0):
+            raise ValueError(f"betas must be in [0, 1), got {betas!r}")
+        if not eps > 0:
+            raise ValueError(f"eps must be > 0, got {eps!r}")
+        self.eps, self.decoupled = float(eps), bool(decoupled)
+
+    def _update(self, lr, wd, scale):
+        c1, c2 = C.c_float(0), C.c_float(0)
+        capi.call("gnnx_adam_bias_corrections", self.b1, self.b2, self.t + 1, C.byref(c1), C.byref(c2))
+        capi.call("gnnx_adam_step_f32", _ptr(self._table), self._n, self._chunks, _ptr(self._arenas[0]), _ptr(self._arenas[1]), lr, self.b1,
+                  self.b2, self.eps, c1.value, c2.value, wd, int(self.decoupled), scale, _stream())
+
+    def state(self):
+        """dict(m=[...], v=[...], t=t): per-tensor views of the two moment arenas, in params() order (empty before the first step)."""
+        if self._bound is None:
+            return dict(m=[], v=[], t=self.t)
+        return dict(m=self._views(self._arenas[0]), v=self._views(self._arenas[1]), t=self.t)
+
+
+class Momentum(_TableOptimizer):
+    """SGD with momentum, dampening and Nesterov's form (torch.optim.SGD's update, include/gnnx.h): the buffer of the first step is the
+    gradient itself."""
+
+    def __init__(self, momentum=0.9, dampening=0.0, nesterov=False, max_grad_norm=None):
+        super().__init__(max_grad_norm)
+        self.momentum, self.dampening, self.nesterov = float(momentum), float(dampening), bool(nesterov)
+
+    def _update(self, lr, wd, scale):
+        capi.call("gnnx_momentum_step_f32", _ptr(self._table), self._n, self._chunks, _ptr(self._arenas[0]), lr, self.momentum, self.dampening,
+                  int(self.nesterov), int(self.t == 0), wd, scale, _stream())
+
+    def state(self):
+        """dict(buf=[...], t=t): per-tensor views of the momentum arena, in params() order (empty before the first step)."""
+        return dict(buf=[] if self._bound is None else self._views(self._arenas[0]), t=self.t)
+
+
 class _Model:
-    """What the trainable models share: the table `_buf` of persistent scratch buffers, one SGD step over the parallel lists params() /
-    grads() (a subclass defines both: every parameter tensor, and its gradient at the same position), and _view, the one way to make a
-    second model on the same parameters.  A subclass creates `_buf = {}` and `_saved = None` in its __init__."""
+    """What the trainable models share: the table `_buf` of persistent scratch buffers, one step of the model's optimiser over the
+    parallel lists params() / grads() (a subclass defines both: every parameter tensor, and its gradient at the same position), and
+    _view, the one way to make a second model on the same parameters.  A subclass creates `_buf = {}`, `_saved = None` and the
+    optimiser's slot `_opt = [None]` in its __init__: _view hands the slot itself on, so the optimiser set on a model is the
+    optimiser of every view of it, made before or after set_optimizer."""
 
     gather_pitch = False   # only GcnStack asks its graph (GcnStack._bind)
 
@@ -1442,7 +1551,27 @@ class _Model:
             self._buf[key] = t
         return t
 
+    def set_optimizer(self, opt):
+        """Every later step of this model and of every view of it (SageStack.on_graph, GraphClassifier.on_batch) is a step of `opt`
+        (ops.Adam, ops.Momentum), with ONE state and one step count; None: back to plain SGD.  The optimiser binds to params() /
+        grads() at its first step.  Returns the model.  A GraphClassifier owns the optimiser of net.params() + [W_c, b_c]; one set on
+        the stack it was built from drives that stack's own steps only."""
+        if opt is not None and not isinstance(opt, _TableOptimizer):
+            raise TypeError(f"ops.Adam or ops.Momentum expected, got {type(opt).__name__}")
+        self._opt[0] = opt
+        return self
+
+    @property
+    def optimizer(self):
+        return self._opt[0]
+
     def step(self, lr, weight_decay=0.0):
+        """One step of the model's optimiser: plain SGD, a launch per tensor, unless set_optimizer chose another (one launch for all
+        tensors, two with gradient clipping)."""
+        opt = self._opt[0]
+        if opt is not None:
+            opt.step(self.params(), self.grads(), lr, weight_decay)
+            return
         for p, gr in zip(self.params(), self.grads()):
             sgd_step(p, gr, lr, weight_decay)
 
@@ -1496,9 +1625,9 @@ class _Stack(_Model):
         return selection, {}
 
     def train_step(self, X, target, rows, lr, weight_decay=0.0):
-        """One SGD step on the selected rows: forward -> softmax_ce_rows over them (db[-1] from the loss kernel) -> backward without an
-        input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)) -- for GcnStack a LabelledSet (CsrGraph.labelled(mask)),
-        which also prunes the last layer's two aggregations to its rows; no other layer of any stack is pruned.  X and target in the
+        """One step of the model's optimiser (plain SGD by default) on the selected rows: forward -> softmax_ce_rows over them (db[-1]
+        from the loss kernel) -> backward without an input gradient -> step.  rows: ascending int32 rows (CsrGraph.rows_of(mask)) --
+        for GcnStack a LabelledSet (CsrGraph.labelled(mask)), which also prunes the last layer's two aggregations to its rows; no other layer of any stack is pruned.  X and target in the
         graph's ROW order (g.to_new_order of vertex-order data); target is read at selected rows only.  Returns the loss tensor."""
         selection, (rows, pruned) = rows, self._selected(rows)
         logits = self.forward(X, **pruned)
@@ -1545,6 +1674,7 @@ class GcnStack(_Stack):
         self.db = [torch.zeros_like(b) for b in self.b]
         self._saved = None
         self._buf = {}
+        self._opt = [None]
 
     def _bind(self, g):
         """The matrices the aggregations GATHER rows from -- H_l = h_l W_l^T forward, the gradients G_l backward -- sit on the padded
@@ -1670,8 +1800,9 @@ class GcnStack(_Stack):
         return out
 
     def link_train_step(self, X, edges, lr, weight_decay=0.0):
-        """One link-prediction SGD step: forward -> pair scores (sddmm) -> bce_logits against edges.target -> dZ (link_grad, into
-        grad_buffer()) -> backward without an input gradient -> step.  X in the graph's ROW order.  Returns the loss tensor."""
+        """One link-prediction step of the model's optimiser (plain SGD by default): forward -> pair scores (sddmm) -> bce_logits
+        against edges.target -> dZ (link_grad, into grad_buffer()) -> backward without an input gradient -> step.  X in the graph's
+        ROW order.  Returns the loss tensor."""
         Z = self.forward(X)
         scores = sddmm(edges.rowptr, edges.colidx, Z, Z)
         loss, ds = bce_logits(scores, edges.target)
@@ -1798,6 +1929,7 @@ class GatStack(_Stack):
         self.db = [torch.zeros_like(b) for b in self.b]
         self._saved = None
         self._buf = {}
+        self._opt = [None]
 
     def _bind(self, g):
         self.g = g
@@ -1918,6 +2050,7 @@ class SageStack(_Stack):
         self.db = [torch.zeros_like(b) for b in self.b]
         self._saved = None
         self._buf = {}
+        self._opt = [None]
 
     def _bind(self, g):
         """What the stack holds of the graph itself: the transpose map (max) or 1 / deg (mean)."""
@@ -2170,6 +2303,7 @@ class GraphClassifier(_Model):
         self.db_c = torch.zeros_like(self.b_c)
         self._saved = None
         self._buf = {}
+        self._opt = [None]
 
     def on_batch(self, batch):
         """This classifier on another GraphBatch, of ANY vertex and graph count: it shares W_c, b_c, their gradients and the stack's
@@ -2208,8 +2342,9 @@ class GraphClassifier(_Model):
         self.net.backward(dH, input_grad=False)
 
     def train_step(self, X, target, lr, weight_decay=0.0):
-        """One SGD step on the batch: forward -> softmax_ce over the B graphs (db_c from the loss kernel) -> backward through the
-        readout and the stack, no input gradient -> step.  target: int32 [B].  Returns the loss tensor."""
+        """One step of the model's optimiser (plain SGD by default) on the batch: forward -> softmax_ce over the B graphs (db_c from the
+        loss kernel) -> backward through the readout and the stack, no input gradient -> step.  target: int32 [B].  Returns the
+        loss tensor."""
         logits = self.forward(X)
         loss, d = softmax_ce(logits, target, colsum_out=self.db_c, grad_out=self._tmp("dlogits", tuple(logits.shape)))
         self.backward(d, have_bias_grad=True)

@@ -516,6 +516,73 @@ int gnnx_bce_logits_workspace(int64_t n, size_t *bytes);
 int gnnx_bce_logits_f32(const float *d_scores, const float *d_target, int64_t n, int64_t n_total, float *d_loss, float *d_dscores,
                         void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ optimisers over a parameter table ---- */
+/*
+ * Adam / AdamW, SGD with momentum and the global gradient norm (clipping) for ALL parameter tensors of a model in one launch.  A
+ * model's parameters are many small tensors; a launch per tensor is what a step costs, so the tensors are listed once in a TABLE
+ * in device memory and a step is one workgroup of 256 threads per chunk of 1024 elements, whatever the number of tensors.
+ *
+ *   gnnx_optim_table_bytes   size of the table for n_tensors tensors.
+ *   gnnx_optim_table_build   fills d_table (8-byte aligned, >= the queried size: GNNX_ERR_WORKSPACE) from HOST arrays of n_tensors
+ *                       device pointers (parameter, gradient; 4-byte aligned) and element counts; copies it to the device and
+ *                       synchronises `stream` (a build call).  Per tensor the table holds the two pointers, the count and the offset
+ *                       of the tensor's state in ONE flat state arena of *state_elems_out floats that the caller owns (zeroed before
+ *                       the first step; Adam has two such arenas, m and v); offsets are rounded up to 4 elements, so on a 16-byte
+ *                       aligned arena every tensor's state is 16-byte aligned.  Behind the entries: int32 first[n_tensors + 1], the
+ *                       running chunk count (a workgroup finds its tensor by binary search).  A tensor of size 0 is legal and has no
+ *                       chunk (its pointers may be NULL).  *n_chunks_out = the total chunk count = the grid of a step; 2^31 chunks or
+ *                       more: GNNX_ERR_UNSUPPORTED.  Every check precedes the first HIP call.  The table stays valid while the
+ *                       tensors stay where they are.
+ *   gnnx_adam_step_f32 / gnnx_momentum_step_f32   one launch, n_chunks workgroups (n_chunks: what the build returned; workgroups
+ *                       past the table's own count return at once, a smaller count leaves the last chunks alone).  A chunk runs on
+ *                       16-byte lanes where its parameter, gradient and state addresses are all 16-byte aligned and on scalar lanes
+ *                       otherwise, its tail on scalar lanes either way.  No host synchronisation, no copy, no atomics: capturable.
+ *                       d_gscale (may be NULL): one device float every gradient is multiplied with -- gnnx_grad_sqnorm_f32's.
+ *   gnnx_grad_sqnorm_f32     *d_sqnorm = sum of g^2 over every gradient of the table: a fixed grid of 256 workgroups strides the
+ *                       chunks, thread i adds elements i, i + 256, i + 512, i + 768 of each of its chunks in that order (scalar loads
+ *                       whatever the alignment), a fixed tree folds the workgroup, a second stage adds the 256 partials in order: the
+ *                       same bits on every run.  The second stage also writes *d_gscale = min(1, max_norm / (sqrtf(sq) + 1e-6f))
+ *                       (torch's clip_grad_norm_): clipping never visits the host.  Either output may be NULL.  Workspace:
+ *                       gnnx_grad_sqnorm_workspace() bytes, 4-byte aligned.
+ *   gnnx_adam_bias_corrections   HOST only, no device: *c = (float)(1.0 - pow((double)b, (double)t)) for both betas, t >= 1 the number
+ *                       of the step about to be taken.  Every caller gets its two floats here; the step is a pure function of its
+ *                       arguments.
+ *
+ * The arithmetic is the contract: every line is ONE float32 operation with one rounding (nothing is contracted to an fma), division
+ * and sqrtf correctly rounded, float32 denormals kept.
+ *     g1 = g * s                       only with d_gscale (s = *d_gscale)
+ *     g2 = g1 + wd * p                 only when wd != 0 and the decay is coupled (product rounded, then the sum; as gnnx_sgd_step_f32)
+ *   Adam:      m' = b1 * m + (1.0f - b1) * g2
+ *              v' = b2 * v + ((1.0f - b2) * g2) * g2
+ *              u  = (m' / c1) / (sqrtf(v' / c2) + eps)
+ *              p1 = p - (lr * wd) * p          only when decoupled and wd != 0 (AdamW)
+ *              p' = p1 - lr * u
+ *   momentum:  buf' = g2 if first else momentum * buf + (1.0f - dampening) * g2
+ *              d    = g2 + momentum * buf' if nesterov else buf'
+ *              p'   = p - lr * d
+ * With momentum == 0, dampening == 0 and no scale the momentum call gives the bits of gnnx_sgd_step_f32 (g = -0, an infinite p and
+ * wd == 0, where the decay term is skipped, included) -- with `first` for every input; without it on a +0 buffer for every input but
+ * p = -0 with g2 = -0 (0 * buf + g2 is +0 there: p' = -0 where gnnx_sgd_step_f32 gives +0).  Subnormal intermediates are outside the
+ * contract.  A zero gradient on zero state leaves p as it is and m, v at +0 (zero pad columns stay zero without weight decay, and
+ * with it: wd * 0 = 0).
+ * Non-finite gradients: no error status.  Without a scale a NaN or Inf gradient element changes its own element of p, m and v (or
+ * buf) and no other bit.  With clipping it poisons the norm: a NaN makes the scale NaN and with it every element; an Inf makes the
+ * scale 0, so every finite gradient counts as 0 and the infinite one as NaN.
+ * GNNX_ERR_INVALID_ARG before any HIP call: a null table / arena / output, a negative count, b1 or b2 outside [0, 1), eps <= 0,
+ * c1 or c2 <= 0, t < 1, a negative max_norm.
+ */
+int gnnx_optim_table_bytes(int32_t n_tensors, size_t *bytes);
+int gnnx_optim_table_build(int32_t n_tensors, float *const *h_params, const float *const *h_grads, const int64_t *h_sizes, void *d_table,
+                           size_t table_bytes, int64_t *n_chunks_out, int64_t *state_elems_out, void *stream);
+int gnnx_adam_bias_corrections(float b1, float b2, int64_t t, float *c1, float *c2);
+int gnnx_adam_step_f32(const void *d_table, int32_t n_tensors, int64_t n_chunks, float *d_m, float *d_v, float lr, float b1, float b2,
+                       float eps, float c1, float c2, float weight_decay, int decoupled, const float *d_gscale, void *stream);
+int gnnx_momentum_step_f32(const void *d_table, int32_t n_tensors, int64_t n_chunks, float *d_buf, float lr, float momentum, float dampening,
+                           int nesterov, int first, float weight_decay, const float *d_gscale, void *stream);
+int gnnx_grad_sqnorm_workspace(size_t *bytes);
+int gnnx_grad_sqnorm_f32(const void *d_table, int32_t n_tensors, float max_norm, float *d_sqnorm, float *d_gscale, void *d_workspace,
+                         size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ semi-supervised training: masks ---- */
 /*
  * Node classification with a label mask (reference include/graph.h:86-94 / src/graph.cpp:130-151: Data::set_mask with a train, a
