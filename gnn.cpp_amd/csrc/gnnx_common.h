@@ -115,4 +115,24 @@ inline int lds_opt_in(K kernel, size_t lds, std::atomic<uint64_t> &done, const c
     }
     return GNNX_OK;
 }
+
+// The one carver of a caller's workspace: a cursor over `base` -- the caller's pointer as it is where the unit's contract or its
+// 4-byte words allow that, aligned_base() of it otherwise (the query then adds 256 bytes of room) -- or over null.  Null is the sizing
+// mode of a *_workspace query: every take() returns null and only the cursor moves, so a query and its entry point agree because
+// they run the same takes.  take<T>(count, align) starts the array at the next offset that is a multiple of `align` bytes (a power
+// of two): 4 packs arrays of words, 256 gives each array lines of its own.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    explicit Carver(void *b) : base(static_cast<char *>(b)) {}
+    template <class T>
+    T *take(size_t count, size_t align)
+    {
+        off = (off + align - 1) & ~(align - 1);
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+    size_t bytes() const { return align256(off); }   // what the arrays taken so far occupy, rounded up to 256
+};
 }  // namespace gnnx

@@ -11,14 +11,14 @@
 //   * long rows, kShortW < d <= S: a wavefront per listed row; up to 64 entries stay in registers, a longer row walks its entries
 //     in three passes and parks e_p, then x_p, in d_out between them (each lane re-reads only what it stored itself): the column
 //     term is gathered once;
-//   * hub rows, d > S: a fixed grid strides over the (hub, segment) pairs listed in the workspace; the maximum, the sum and the
+//   * hub rows, d > S: a fixed grid strides over the segment slots of the hub list (gnnx_worklist.h); the maximum, the sum and the
 //     division are separate launches because each needs the previous one complete for the whole row.  The segments' partial results
 //     sit in the workspace and are combined in the fixed order by one lane per hub.
 // Every launch is on the caller's stream and every ordering is a stream ordering; nothing is allocated or synchronised.  The
 // order in which rows land in the lists varies from call to call, the values do not: a row's result never depends on its slot.
 // Several heads (include/gnnx.h "multi-head attention"): every kernel takes the head from blockIdx.y and reads column h of the entry-major
 // per-entry arrays; the lists are the pattern's and are written by head 0 only.  The single-head entry points launch one head.
-#include "gnnx_common.h"
+#include "gnnx_worklist.h"
 
 #pragma clang fp contract(off)
 
@@ -26,13 +26,12 @@ using namespace gnnx;
 
 namespace {
 
-constexpr int kSeg = 4096;          // S: the contract's segment length
 constexpr int kShortW = 16;         // lanes per row of the short-row kernel
 constexpr int kShortR = 8;          // rows per lane group of the short-row kernel
 constexpr int kShortRowsPerBlock = (256 / kShortW) * kShortR;
 constexpr int kLongWaves = 8192;    // wavefronts of the long-row kernel (grid stride over the list)
 constexpr int kHubWaves = 4096;     // wavefronts of the hub kernels (stride over (hub, segment) pairs)
-constexpr int kCounters = 16;       // int32 words in front of the workspace: [0] long rows, [1] hubs, [2] segments
+constexpr int kCounters = 16;       // int32 words in front of the workspace: [0], [1] the hub list's, [2] long rows
 
 // the three operands of the pre-activation (each may be null, not all three) and the slope
 struct Pre {
@@ -46,37 +45,28 @@ struct Pre {
 // the caller's workspace, carved
 struct Lists {
     int32_t *counters;      // kCounters words, zeroed by a memset on the stream in front of the first kernel
-    int32_t *long_rows;     // [cap_long]
-    int32_t *hub_rows;      // [cap_hub]; -1: a hub whose segments did not fit (only a broken CSR can do that)
-    int32_t *hub_seg0;      // [cap_hub] first slot of the hub's segments in `part`
+    int32_t *long_rows;     // [cap_long] rows of more than kShortW and at most S entries
+    HubList hubs;
     float *hub_val;         // [H, cap_hub] the row's maximum, later its sum (forward); dot_i (backward)
-    float *part;            // [H, cap_seg] one value per segment
-    int32_t *seg_hub;       // [cap_seg] the hub (its slot in hub_rows) that a segment slot belongs to; -1: none
-    int64_t cap_long, cap_hub, cap_seg;
+    float *part;            // [H, cap_seg] one value per segment slot
+    int64_t cap_long;
 };
 
+// the caller's pointer is taken as it is: the arrays are 4-byte words
 size_t carve(int32_t n_rows, int64_t nnz, int32_t H, void *base, Lists *out)
 {
     Lists w{};
-    w.cap_long = nnz / (kShortW + 1) < n_rows ? nnz / (kShortW + 1) : n_rows;   // rows of more than kShortW entries
-    w.cap_hub = nnz / (kSeg + 1) < n_rows ? nnz / (kSeg + 1) : n_rows;          // rows of more than S entries
-    w.cap_seg = nnz / kSeg + w.cap_hub;                                         // sum of ceil(d / S) <= nnz / S + hubs
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t words) {
-        char *q = p ? p + off : nullptr;
-        off += 4 * words;
-        return q;
-    };
-    w.counters = reinterpret_cast<int32_t *>(take(kCounters));
-    w.long_rows = reinterpret_cast<int32_t *>(take((size_t)w.cap_long));
-    w.hub_rows = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
-    w.hub_seg0 = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
-    w.hub_val = reinterpret_cast<float *>(take((size_t)w.cap_hub * H));   // head h: hub_val + h cap_hub
-    w.part = reinterpret_cast<float *>(take((size_t)w.cap_seg * H));      //         part + h cap_seg
-    w.seg_hub = reinterpret_cast<int32_t *>(take((size_t)w.cap_seg));
+    w.cap_long = cap_rows_longer(n_rows, nnz, kShortW);
+    w.hubs.size(n_rows, nnz);
+    Carver c(base);
+    w.counters = c.take<int32_t>(kCounters, 4);
+    w.long_rows = c.take<int32_t>((size_t)w.cap_long, 4);
+    w.hubs.take_hubs(c, w.counters);
+    w.hub_val = c.take<float>((size_t)w.hubs.cap_hub * H, 4);   // head h: hub_val + h cap_hub
+    w.part = c.take<float>((size_t)w.hubs.cap_seg * H, 4);      //         part + h cap_seg
+    w.hubs.take_slots(c);
     if (out) *out = w;
-    return (off + 255) & ~(size_t)255;
+    return c.bytes();
 }
 
 // t_p = (scores[p] + rowterm[i]) + colterm[c_p], a null operand skipped; rt = rowterm[i * rs], loaded once per row
@@ -107,8 +97,8 @@ __device__ __forceinline__ int head(Pre &a, Lists &w)
     if (a.scores) a.scores += h;
     if (a.rowterm) a.rowterm += h;
     if (a.colterm) a.colterm += h;
-    w.hub_val += (int64_t)h * w.cap_hub;
-    w.part += (int64_t)h * w.cap_seg;
+    w.hub_val += (int64_t)h * w.hubs.cap_hub;
+    w.part += (int64_t)h * w.hubs.cap_seg;
     return h;
 }
 
@@ -187,7 +177,7 @@ __device__ __forceinline__ ShortRows load_short_rows(const int32_t *__restrict__
 
 // Every row of the workgroup with more than kShortW entries goes to the lists.  Long rows: the workgroup counts them in LDS and
 // reserves its run of slots with ONE global atomic (one per row, or per wavefront, serialises on the counter's address: a tenth of a
-// power-law graph's rows are long).  Hubs are rare: an atomic each, which also reserves the hub's run of segment slots.
+// power-law graph's rows are long).  Hubs are rare: each is appended to the hub list by its leader lane.
 __device__ __forceinline__ void classify(const Lists &w, const ShortRows &r)
 {
     __shared__ int32_t s_count, s_base;
@@ -203,18 +193,10 @@ __device__ __forceinline__ void classify(const Lists &w, const ShortRows &r)
             slot[j] = atomicAdd(&s_count, 1);
             continue;
         }
-        const int32_t nseg = (r.d[j] + kSeg - 1) / kSeg;
-        const int32_t h = atomicAdd(&w.counters[1], 1);
-        const int32_t s0 = atomicAdd(&w.counters[2], nseg);
-        const bool fits = h < w.cap_hub && (int64_t)s0 + nseg <= w.cap_seg;   // holds on a valid CSR
-        if (h < w.cap_hub) {
-            w.hub_rows[h] = fits ? r.row[j] : -1;
-            w.hub_seg0[h] = fits ? s0 : 0;
-        }
-        for (int64_t s = s0; s < (int64_t)s0 + nseg && s < w.cap_seg; s++) w.seg_hub[s] = fits ? h : -1;
+        append(w.hubs, r.row[j], r.d[j]);
     }
     __syncthreads();
-    if (threadIdx.x == 0 && s_count > 0) s_base = atomicAdd(&w.counters[0], s_count);
+    if (threadIdx.x == 0 && s_count > 0) s_base = atomicAdd(&w.counters[2], s_count);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < kShortR; j++) {
@@ -222,12 +204,6 @@ __device__ __forceinline__ void classify(const Lists &w, const ShortRows &r)
         const int64_t at = (int64_t)s_base + slot[j];
         if (at < w.cap_long) w.long_rows[at] = r.row[j];   // the bound holds on a valid CSR
     }
-}
-
-__device__ __forceinline__ int64_t listed(const int32_t *counter, int64_t cap)
-{
-    const int64_t n = *counter;
-    return n < cap ? n : cap;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
@@ -279,7 +255,7 @@ __global__ __launch_bounds__(256) void fwd_long_kernel(const int32_t *__restrict
     out += hd;
     const int l = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
-    const int64_t n_long = listed(&w.counters[0], w.cap_long);
+    const int64_t n_long = listed(&w.counters[2], w.cap_long);
     for (int64_t i = wave; i < n_long; i += n_waves) {
         const int32_t row = w.long_rows[i];
         const int64_t b = rowptr[row], d = (int64_t)rowptr[row + 1] - b;
@@ -322,31 +298,23 @@ __global__ __launch_bounds__(256) void fwd_long_kernel(const int32_t *__restrict
     }
 }
 
-// Hub passes: the wavefronts stride over the segment slots the short-row kernel handed out; a slot names its hub, the hub its row
-// and its first slot.  b, n: the segment's first entry and length; part[s]: its slot.
-#define GNNX_FOR_HUB_SEGMENTS(BODY)                                                                                \
-    const int l = threadIdx.x & 63;                                                                                \
-    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;        \
-    const int64_t n_slots = listed(&w.counters[2], w.cap_seg);                                                     \
-    for (int64_t slot = wave; slot < n_slots; slot += n_waves) {                                                   \
-        const int32_t h = w.seg_hub[slot];                                                                         \
-        if (h < 0) continue;                                                                                       \
-        const int32_t row = w.hub_rows[h];                                                                         \
-        const int64_t s = slot - w.hub_seg0[h];                                                                    \
-        const int64_t rb = rowptr[row], d = (int64_t)rowptr[row + 1] - rb;                                         \
-        const int64_t b = rb + s * kSeg;                                                                           \
-        const int64_t n = d - s * kSeg < kSeg ? d - s * kSeg : kSeg;                                               \
-        float *part = w.part + w.hub_seg0[h];                                                                      \
-        (void)part;                                                                                                \
-        BODY                                                                                                       \
-    }
+// Hub passes: the wavefronts stride over the hub list's segment slots.  body(row, h, b, n, slot, l): the segment's first entry and
+// length, its slot (of the head's `part`, too) and the lane.
+template <class Body>
+__device__ __forceinline__ void for_wave_segments(const int32_t *__restrict__ rowptr, const Lists &w, Body body)
+{
+    const int l = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
+    for_hub_segments(w.hubs, rowptr, wave, n_waves,
+                     [&](int32_t row, int32_t h, int64_t, int64_t b, int64_t n, int64_t slot) { body(row, h, b, n, slot, l); });
+}
 
 // e_p -> out, the segment's maximum -> part
 __global__ __launch_bounds__(256) void fwd_hub_max_kernel(const int32_t *__restrict__ rowptr, Pre a, float *__restrict__ out, int64_t ldo,
                                                           Lists w)
 {
     out += head(a, w);
-    GNNX_FOR_HUB_SEGMENTS({
+    for_wave_segments(rowptr, w, [&](int32_t row, int32_t, int64_t b, int64_t n, int64_t slot, int l) {
         const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
         float m = -INFINITY;
         for_lane_entries(a, b, n, rt, l, [&](int64_t k, float t) {
@@ -355,8 +323,8 @@ __global__ __launch_bounds__(256) void fwd_hub_max_kernel(const int32_t *__restr
             m = fmaxf(m, e);
         });
         m = max_lanes<64>(m);
-        if (l == 0) part[s] = m;
-    })
+        if (l == 0) w.part[slot] = m;
+    });
 }
 
 // a wavefront per hub: the maximum of its segments' maxima -> hub_val (and rowmax)
@@ -366,12 +334,12 @@ __global__ __launch_bounds__(256) void hub_combine_max_kernel(const int32_t *__r
     const int hd = head(none, w), H = gridDim.y;
     const int l = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
-    const int64_t n_hub = listed(&w.counters[1], w.cap_hub);
+    const int64_t n_hub = listed_hubs(w.hubs);
     for (int64_t h = wave; h < n_hub; h += n_waves) {
-        const int32_t row = w.hub_rows[h];
+        const int32_t row = w.hubs.hub_rows[h];
         if (row < 0) continue;
         const int64_t nseg = ((int64_t)rowptr[row + 1] - rowptr[row] + kSeg - 1) / kSeg;
-        const float *part = w.part + w.hub_seg0[h];
+        const float *part = w.part + w.hubs.hub_seg0[h];
         float m = -INFINITY;
         for (int64_t s = l; s < nseg; s += 64) m = fmaxf(m, part[s]);
         m = max_lanes<64>(m);
@@ -387,7 +355,7 @@ __global__ __launch_bounds__(256) void fwd_hub_exp_kernel(const int32_t *__restr
 {
     Pre none{};
     out += head(none, w);
-    GNNX_FOR_HUB_SEGMENTS({
+    for_wave_segments(rowptr, w, [&](int32_t, int32_t h, int64_t b, int64_t n, int64_t slot, int l) {
         const float m = w.hub_val[h];
         float acc = 0.f;
         for (int64_t k = l; k < n; k += 64) {
@@ -396,8 +364,8 @@ __global__ __launch_bounds__(256) void fwd_hub_exp_kernel(const int32_t *__restr
             acc = acc + x;
         }
         acc = add_lanes<64>(acc, 64);
-        if (l == 0) part[s] = acc;
-    })
+        if (l == 0) w.part[slot] = acc;
+    });
 }
 
 // one lane per hub: ((seg_0 + seg_1) + seg_2) + ... -> hub_val and, when given, rows[row]
@@ -406,12 +374,12 @@ __global__ __launch_bounds__(256) void hub_combine_sum_kernel(const int32_t *__r
 {
     Pre none{};
     const int hd = head(none, w);
-    const int64_t n_hub = listed(&w.counters[1], w.cap_hub);
+    const int64_t n_hub = listed_hubs(w.hubs);
     for (int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x; h < n_hub; h += (int64_t)gridDim.x * 256) {
-        const int32_t row = w.hub_rows[h];
+        const int32_t row = w.hubs.hub_rows[h];
         if (row < 0) continue;
         const int64_t nseg = ((int64_t)rowptr[row + 1] - rowptr[row] + kSeg - 1) / kSeg;
-        const float *part = w.part + w.hub_seg0[h];
+        const float *part = w.part + w.hubs.hub_seg0[h];
         float z = part[0];
         for (int64_t s = 1; s < nseg; s++) z = z + part[s];
         w.hub_val[h] = z;
@@ -424,10 +392,10 @@ __global__ __launch_bounds__(256) void fwd_hub_div_kernel(const int32_t *__restr
 {
     Pre none{};
     out += head(none, w);
-    GNNX_FOR_HUB_SEGMENTS({
+    for_wave_segments(rowptr, w, [&](int32_t, int32_t h, int64_t b, int64_t n, int64_t, int l) {
         const float z = w.hub_val[h];
         for (int64_t k = l; k < n; k += 64) out[(b + k) * ldo] = __fdiv_rn(out[(b + k) * ldo], z);
-    })
+    });
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------
@@ -502,7 +470,7 @@ __global__ __launch_bounds__(256) void bwd_long_kernel(const int32_t *__restrict
     head(g, head(a, w));
     const int l = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (int64_t)gridDim.x * 4;
-    const int64_t n_long = listed(&w.counters[0], w.cap_long);
+    const int64_t n_long = listed(&w.counters[2], w.cap_long);
     for (int64_t i = wave; i < n_long; i += n_waves) {
         const int32_t row = w.long_rows[i];
         const int64_t b = rowptr[row], d = (int64_t)rowptr[row + 1] - b;
@@ -546,19 +514,19 @@ __global__ __launch_bounds__(256) void bwd_hub_dot_kernel(const int32_t *__restr
 {
     Pre none{};
     head(g, head(none, w));
-    GNNX_FOR_HUB_SEGMENTS({
+    for_wave_segments(rowptr, w, [&](int32_t, int32_t, int64_t b, int64_t n, int64_t slot, int l) {
         float acc = 0.f;
         for (int64_t k = l; k < n; k += 64) acc = acc + (g.alpha[(b + k) * g.lda] * g.dalpha[(b + k) * g.ldd]);
         acc = add_lanes<64>(acc, 64);
-        if (l == 0) part[s] = acc;
-    })
+        if (l == 0) w.part[slot] = acc;
+    });
 }
 
 // dt_p -> dt, the segment's sum of dt_p -> part
 __global__ __launch_bounds__(256) void bwd_hub_dt_kernel(const int32_t *__restrict__ rowptr, Pre a, Bwd g, Lists w)
 {
     head(g, head(a, w));
-    GNNX_FOR_HUB_SEGMENTS({
+    for_wave_segments(rowptr, w, [&](int32_t row, int32_t h, int64_t b, int64_t n, int64_t slot, int l) {
         const float rt = a.rowterm ? a.rowterm[(int64_t)row * a.rs] : 0.f;
         const float dot = w.hub_val[h];
         float acc = 0.f;
@@ -568,11 +536,9 @@ __global__ __launch_bounds__(256) void bwd_hub_dt_kernel(const int32_t *__restri
             acc = acc + v;
         });
         acc = add_lanes<64>(acc, 64);
-        if (l == 0) part[s] = acc;
-    })
+        if (l == 0) w.part[slot] = acc;
+    });
 }
-
-#undef GNNX_FOR_HUB_SEGMENTS
 
 inline uint32_t blocks_for_waves(int64_t waves, int64_t cap) { return (uint32_t)ceil_div(waves < cap ? waves : cap, 4); }
 
@@ -620,15 +586,15 @@ int forward(int32_t n_rows, int32_t n_cols, int64_t nnz, int32_t H, const int32_
                            d_rowmax, d_rowsum, w);
         GNNX_LAUNCH_CHECK();
     }
-    if (w.cap_hub > 0) {
-        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves), Hy), hub_grid(blocks_for_waves(w.cap_hub, 1024), Hy);
+    if (w.hubs.cap_hub > 0) {
+        const dim3 seg_grid(blocks_for_waves(w.hubs.cap_seg, kHubWaves), Hy), hub_grid(blocks_for_waves(w.hubs.cap_hub, 1024), Hy);
         hipLaunchKernelGGL(fwd_hub_max_kernel, seg_grid, dim3(256), 0, st, d_rowptr, a, d_out, ldo, w);
         GNNX_LAUNCH_CHECK();
         hipLaunchKernelGGL(hub_combine_max_kernel, hub_grid, dim3(256), 0, st, d_rowptr, d_rowmax, w);
         GNNX_LAUNCH_CHECK();
         hipLaunchKernelGGL(fwd_hub_exp_kernel, seg_grid, dim3(256), 0, st, d_rowptr, d_out, ldo, w);
         GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hub_combine_sum_kernel, dim3((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256), Hy), dim3(256), 0, st,
+        hipLaunchKernelGGL(hub_combine_sum_kernel, dim3((uint32_t)ceil_div(w.hubs.cap_hub < 65536 ? w.hubs.cap_hub : 65536, 256), Hy), dim3(256), 0, st,
                            d_rowptr, d_rowsum, (int64_t)H, w);
         GNNX_LAUNCH_CHECK();
         if (!unnorm) {
@@ -662,9 +628,9 @@ int backward(int32_t n_rows, int32_t n_cols, int64_t nnz, int32_t H, const int32
         hipLaunchKernelGGL(bwd_long_kernel, dim3(blocks_for_waves(w.cap_long, kLongWaves), Hy), dim3(256), 0, st, d_rowptr, a, g, w);
         GNNX_LAUNCH_CHECK();
     }
-    if (w.cap_hub > 0) {
-        const dim3 seg_grid(blocks_for_waves(w.cap_seg, kHubWaves), Hy);
-        const dim3 lane_grid((uint32_t)ceil_div(w.cap_hub < 65536 ? w.cap_hub : 65536, 256), Hy);
+    if (w.hubs.cap_hub > 0) {
+        const dim3 seg_grid(blocks_for_waves(w.hubs.cap_seg, kHubWaves), Hy);
+        const dim3 lane_grid((uint32_t)ceil_div(w.hubs.cap_hub < 65536 ? w.hubs.cap_hub : 65536, 256), Hy);
         hipLaunchKernelGGL(bwd_hub_dot_kernel, seg_grid, dim3(256), 0, st, d_rowptr, g, w);
         GNNX_LAUNCH_CHECK();
         hipLaunchKernelGGL(hub_combine_sum_kernel, lane_grid, dim3(256), 0, st, d_rowptr, (float *)nullptr, (int64_t)0, w);   // dot_i -> hub_val

@@ -231,8 +231,6 @@ int libm_pow_m05_table(size_t need_len, const float **d_table_out, size_t *len_o
 }  // namespace gnnx
 
 namespace {
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct CsrWorkspace {
     uint64_t *keys_in, *keys_out;
     int32_t *flag, *pos, *bad;
@@ -257,16 +255,15 @@ hipError_t plan_workspace(int64_t n_edges, int32_t n_nodes, char *base, CsrWorks
     e = rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, n, rocprim::plus<int32_t>());
     if (e != hipSuccess) return e;
     (void)n_nodes;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return base + o; };
-    w.keys_in = (uint64_t *)take(n * 8);
-    w.keys_out = (uint64_t *)take(n * 8);
-    w.flag = (int32_t *)take(n * 4);
-    w.pos = (int32_t *)take(n * 4);
-    w.bad = (int32_t *)take(256);
+    Carver c(base);
+    w.keys_in = c.take<uint64_t>(n, 256);
+    w.keys_out = c.take<uint64_t>(n, 256);
+    w.flag = c.take<int32_t>(n, 256);
+    w.pos = c.take<int32_t>(n, 256);
+    w.bad = c.take<int32_t>(64, 256);
     w.prim_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    w.prim = take(w.prim_bytes);
-    w.total = off;
+    w.prim = c.take<char>(w.prim_bytes, 256);
+    w.total = c.bytes();
     return hipSuccess;
 }
 
@@ -349,18 +346,17 @@ hipError_t plan_workspace_weighted(int64_t n_keys, char *base, CsrWorkspaceW &w)
     if (e != hipSuccess) return e;
     e = rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, n, rocprim::plus<int32_t>());
     if (e != hipSuccess) return e;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return base + o; };
-    w.keys_in = (uint64_t *)take(n * 8);
-    w.keys_out = (uint64_t *)take(n * 8);
-    w.idx_in = (int32_t *)take(n * 4);
-    w.idx_out = (int32_t *)take(n * 4);
-    w.flag = (int32_t *)take(n * 4);
-    w.pos = (int32_t *)take(n * 4);
-    w.bad = (int32_t *)take(256);
+    Carver c(base);
+    w.keys_in = c.take<uint64_t>(n, 256);
+    w.keys_out = c.take<uint64_t>(n, 256);
+    w.idx_in = c.take<int32_t>(n, 256);
+    w.idx_out = c.take<int32_t>(n, 256);
+    w.flag = c.take<int32_t>(n, 256);
+    w.pos = c.take<int32_t>(n, 256);
+    w.bad = c.take<int32_t>(64, 256);
     w.prim_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    w.prim = take(w.prim_bytes);
-    w.total = off;
+    w.prim = c.take<char>(w.prim_bytes, 256);
+    w.total = c.bytes();
     return hipSuccess;
 }
 

@@ -12,6 +12,7 @@
 //   scores: work is dealt in the non-zero domain as in gnnx_sddmm.hip; GE lanes per entry hold HP = GE / G heads of G lanes each, a
 //     pattern with more heads than that takes several passes over the same entry.
 #include "gnnx_edge_dot.h"
+#include "gnnx_lanes.h"
 
 #pragma clang fp contract(off)
 
@@ -32,28 +33,20 @@ struct AggArgs {
     int64_t ldy;
 };
 
-template <int VEC> struct Piece;
-template <> struct Piece<1> { using type = float; };
-template <> struct Piece<4> { using type = float4; };
-
 __device__ __forceinline__ float mul_add(float acc, float x, float v) { return acc + (x * v); }   // the product rounded, then the sum
 __device__ __forceinline__ float4 mul_add(float4 acc, float4 x, float v)
 {
     return make_float4(acc.x + (x.x * v), acc.y + (x.y * v), acc.z + (x.z * v), acc.w + (x.w * v));
 }
-__device__ __forceinline__ float add(float a, float b) { return a + b; }
-__device__ __forceinline__ float4 add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float relu(float a) { return a > 0.f ? a : 0.f; }
 __device__ __forceinline__ float4 relu(float4 a) { return make_float4(relu(a.x), relu(a.y), relu(a.z), relu(a.w)); }
-__device__ __forceinline__ void clear(float &a) { a = 0.f; }
-__device__ __forceinline__ void clear(float4 &a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
 
 // B neighbours k .. k + B - 1 from the top of the group's current window (entries top - k, top - k - 1, ...): all loads, then the adds
 template <int G, int VEC, int B>
-__device__ __forceinline__ void agg_batch(typename Piece<VEC>::type &acc, int k, int32_t top, int32_t myc, int gbase, const float *xf,
+__device__ __forceinline__ void agg_batch(typename Piece<VEC>::F &acc, int k, int32_t top, int32_t myc, int gbase, const float *xf,
                                           const float *vf, const AggArgs &a)
 {
-    using V = typename Piece<VEC>::type;
+    using V = typename Piece<VEC>::F;
     int32_t c[B];
     V x[B];
     float v[B];
@@ -72,7 +65,7 @@ __device__ __forceinline__ void agg_batch(typename Piece<VEC>::type &acc, int k,
 template <int G, int VEC>
 __global__ __launch_bounds__(256) void agg_heads_kernel(AggArgs a)
 {
-    using V = typename Piece<VEC>::type;
+    using V = typename Piece<VEC>::F;
     constexpr int GROUPS = 256 / G;
     const int li = threadIdx.x % G;
     const int gbase = (threadIdx.x & 63) - li;

@@ -140,19 +140,14 @@ hipError_t restrict_ws(int64_t n_chunks, char *base, RestrictWs &w)
     hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)n_chunks + 1,
                                            rocprim::plus<int32_t>());
     if (e != hipSuccess) return e;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    w.cnt = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * ((size_t)n_chunks + 1)));
-    w.pos = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * ((size_t)n_chunks + 1)));
-    w.bits = reinterpret_cast<uint64_t *>(take(sizeof(uint64_t) * ((size_t)n_chunks + 1)));
-    w.bad = reinterpret_cast<int32_t *>(take(256));
-    w.prim = take(scan_bytes);
+    Carver c(base);
+    w.cnt = c.take<int32_t>((size_t)n_chunks + 1, 256);
+    w.pos = c.take<int32_t>((size_t)n_chunks + 1, 256);
+    w.bits = c.take<uint64_t>((size_t)n_chunks + 1, 256);
+    w.bad = c.take<int32_t>(64, 256);
+    w.prim = c.take<char>(scan_bytes, 256);
     w.prim_bytes = scan_bytes;
-    w.total = off + 256;   // room to align the caller's pointer
+    w.total = c.bytes() + 256;   // room to align the caller's pointer
     return hipSuccess;
 }
 

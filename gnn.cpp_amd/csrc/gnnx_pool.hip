@@ -14,7 +14,7 @@
 // allocated or synchronised, and no atomic exists in this file.
 #include <type_traits>
 
-#include "gnnx_common.h"
+#include "gnnx_lanes.h"
 
 #pragma clang fp contract(off)
 
@@ -41,42 +41,18 @@ size_t carve(int32_t n_rows, int32_t F, void *ws, Parts *out)
 {
     Parts w{};
     w.tiles = (int64_t)n_rows / kT + 1;
-    char *p = ws ? aligned_base(ws) : nullptr;
-    const size_t slab = (size_t)4 * 2 * (size_t)w.tiles * (size_t)F;   // a multiple of 16 bytes whenever F % 4 == 0
-    w.val = reinterpret_cast<float *>(p);
-    w.pos = reinterpret_cast<int32_t *>(p ? p + slab : nullptr);
-    w.long_seg = reinterpret_cast<int32_t *>(p ? p + 2 * slab : nullptr);
+    Carver c(ws ? aligned_base(ws) : nullptr);
+    const size_t slab = 2 * (size_t)w.tiles * (size_t)F;   // words: a multiple of 16 bytes whenever F % 4 == 0
+    w.val = c.take<float>(slab, 4);
+    w.pos = c.take<int32_t>(slab, 4);
+    w.long_seg = c.take<int32_t>((size_t)w.tiles, 4);
     if (out) *out = w;
-    return align256(2 * slab + (size_t)4 * (size_t)w.tiles);
+    return c.bytes();
 }
 
-template <int VEC> struct Piece;
-template <> struct Piece<1> { using F = float; using I = int32_t; };
-template <> struct Piece<4> { using F = float4; using I = int4; };
-
-__device__ __forceinline__ void clear(float &a) { a = 0.f; }
-__device__ __forceinline__ void clear(float4 &a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void none(int32_t &p) { p = -1; }
-__device__ __forceinline__ void none(int4 &p) { p = make_int4(-1, -1, -1, -1); }
-__device__ __forceinline__ float add(float a, float b) { return a + b; }
-__device__ __forceinline__ float4 add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float div(float a, float d) { return __fdiv_rn(a, d); }
 __device__ __forceinline__ float4 div(float4 a, float d) { return make_float4(__fdiv_rn(a.x, d), __fdiv_rn(a.y, d), __fdiv_rn(a.z, d), __fdiv_rn(a.w, d)); }
 
-// row p meets the running (value, row): the first row is taken as it is, a later one only when it is strictly better
-__device__ __forceinline__ void meet(float &val, int32_t &pos, float t, int32_t p)
-{
-    const bool take = pos < 0 || t > val;
-    val = take ? t : val;
-    pos = take ? p : pos;
-}
-__device__ __forceinline__ void meet(float4 &val, int4 &pos, float4 t, int32_t p)
-{
-    meet(val.x, pos.x, t.x, p);
-    meet(val.y, pos.y, t.y, p);
-    meet(val.z, pos.z, t.z, p);
-    meet(val.w, pos.w, t.w, p);
-}
 // what MAX stores: +0 where the segment has no row
 __device__ __forceinline__ float stored(float val, int32_t pos) { return pos < 0 ? 0.f : val; }
 __device__ __forceinline__ float4 stored(float4 v, int4 p) { return make_float4(stored(v.x, p.x), stored(v.y, p.y), stored(v.z, p.z), stored(v.w, p.w)); }

@@ -8,15 +8,14 @@
 //   * rows of d <= S entries: the lane-group shape of gnnx_heads.hip's aggregation -- G = 4 .. 64 lanes per row, lane l owns features
 //     f0 .. f0 + VEC - 1 of tile blockIdx.y, the group fetches G entries of the pattern with one coalesced load and hands them out by
 //     shuffle, four gathered rows are requested before the first is compared (added).  A lane carries (value, position) per feature;
-//   * hub rows, d > S: the row kernel appends them to a list in the caller's workspace (a counter atomic reserves the hub's slot and
-//     its run of segment slots: never an atomic on a value), a fixed grid of lane groups strides over the segment slots and writes
-//     each segment's (value, position) or sum to the workspace, and a thread per (hub, feature) finishes the row: the better value
-//     wins and on equal values the smaller position (forward), ascending segment order (backward).
+//   * hub rows, d > S: the row kernel appends them to the hub list (gnnx_worklist.h), a fixed grid of lane groups strides over the
+//     segment slots and writes each segment's (value, position) or sum to the workspace, and a thread per (hub, feature) finishes the
+//     row: the better value wins and on equal values the smaller position (forward), ascending segment order (backward).
 // MIN is MAX on the sign-flipped values: flipping the sign bit is exact both ways, keeps every tie a tie and the first of them first.
 // The running value starts from the FIRST entry (position -1 means "none yet"), never from a sentinel: a row of -inf gets its first
-// entry.  Every launch is on the caller's stream and every ordering is a stream ordering; nothing is allocated or synchronised.  The
-// order in which hubs land in the list varies from call to call, the values do not: a row's result never depends on its slot.
-#include "gnnx_common.h"
+// entry.  Every launch is on the caller's stream and every ordering is a stream ordering; nothing is allocated or synchronised.
+#include "gnnx_lanes.h"
+#include "gnnx_worklist.h"
 
 #pragma clang fp contract(off)
 
@@ -24,8 +23,7 @@ using namespace gnnx;
 
 namespace {
 
-constexpr int kSeg = 4096;        // S: the contract's segment length
-constexpr int kCounters = 16;     // int32 words in front of the workspace: [0] hubs, [1] segment slots
+constexpr int kCounters = 16;     // int32 words in front of the workspace: [0], [1] the hub list's
 constexpr int kSegGroups = 8192;  // lane groups of the segment kernels (stride over the slots)
 
 // the caller's workspace, carved
@@ -33,67 +31,26 @@ struct Lists {
     int32_t *counters;    // kCounters words, zeroed by a memset on the stream in front of the first kernel
     float *part_val;      // [cap_seg, F] a segment's value (forward, in the flipped domain) or sum (backward)
     int32_t *part_pos;    // [cap_seg, F] a segment's position (forward)
-    int32_t *hub_rows;    // [cap_hub]; -1: a hub whose segments did not fit (only a broken CSR can do that)
-    int32_t *hub_seg0;    // [cap_hub] first slot of the hub's segments
-    int32_t *seg_hub;     // [cap_seg] the hub (its slot in hub_rows) that a segment slot belongs to; -1: none
-    int64_t cap_hub, cap_seg;
+    HubList hubs;
 };
 
 // bytes the carving takes from the first 256-byte boundary on; the query adds 256 for a workspace at any address
 size_t carve(int32_t n_rows, int64_t nnz, int32_t F, void *ws, Lists *out)
 {
     Lists w{};
-    w.cap_hub = nnz / (kSeg + 1) < n_rows ? nnz / (kSeg + 1) : n_rows;   // rows of more than S entries
-    w.cap_seg = nnz / kSeg + w.cap_hub;                                  // sum of ceil(d / S) <= nnz / S + hubs
-    char *p = ws ? aligned_base(ws) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t words) {
-        char *q = p ? p + off : nullptr;
-        off += 4 * words;
-        return q;
-    };
-    w.counters = reinterpret_cast<int32_t *>(take(kCounters));            // 64 bytes: the partials stay 16-byte aligned (F % 4 == 0)
-    w.part_val = reinterpret_cast<float *>(take((size_t)w.cap_seg * F));
-    w.part_pos = reinterpret_cast<int32_t *>(take((size_t)w.cap_seg * F));
-    w.hub_rows = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
-    w.hub_seg0 = reinterpret_cast<int32_t *>(take((size_t)w.cap_hub));
-    w.seg_hub = reinterpret_cast<int32_t *>(take((size_t)w.cap_seg));
+    w.hubs.size(n_rows, nnz);
+    Carver c(ws ? aligned_base(ws) : nullptr);
+    w.counters = c.take<int32_t>(kCounters, 4);   // 64 bytes: the partials stay 16-byte aligned (F % 4 == 0)
+    w.part_val = c.take<float>((size_t)w.hubs.cap_seg * F, 4);
+    w.part_pos = c.take<int32_t>((size_t)w.hubs.cap_seg * F, 4);
+    w.hubs.take_hubs(c, w.counters);
+    w.hubs.take_slots(c);
     if (out) *out = w;
-    return align256(off);
+    return c.bytes();
 }
-
-__device__ __forceinline__ int64_t listed(const int32_t *counter, int64_t cap)
-{
-    const int64_t n = *counter;
-    return n < cap ? n : cap;
-}
-
-// one lane per hub row: its slot in the list and its run of segment slots
-__device__ __forceinline__ void list_hub(const Lists &w, int32_t row, int64_t d)
-{
-    const int32_t nseg = (int32_t)((d + kSeg - 1) / kSeg);
-    const int32_t h = atomicAdd(&w.counters[0], 1);
-    const int32_t s0 = atomicAdd(&w.counters[1], nseg);
-    const bool fits = h < w.cap_hub && (int64_t)s0 + nseg <= w.cap_seg;   // holds on a valid CSR
-    if (h < w.cap_hub) {
-        w.hub_rows[h] = fits ? row : -1;
-        w.hub_seg0[h] = fits ? s0 : 0;
-    }
-    for (int64_t s = s0; s < (int64_t)s0 + nseg && s < w.cap_seg; s++) w.seg_hub[s] = fits ? h : -1;
-}
-
-template <int VEC> struct Piece;
-template <> struct Piece<1> { using F = float; using I = int32_t; };
-template <> struct Piece<4> { using F = float4; using I = int4; };
 
 __device__ __forceinline__ float flip(float t, uint32_t sign) { return __uint_as_float(__float_as_uint(t) ^ sign); }
 __device__ __forceinline__ float4 flip(float4 t, uint32_t s) { return make_float4(flip(t.x, s), flip(t.y, s), flip(t.z, s), flip(t.w, s)); }
-__device__ __forceinline__ float4 mul(float4 x, float v) { return make_float4(x.x * v, x.y * v, x.z * v, x.w * v); }
-__device__ __forceinline__ float mul(float x, float v) { return x * v; }
-__device__ __forceinline__ void clear(float &a) { a = 0.f; }
-__device__ __forceinline__ void clear(float4 &a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void none(int32_t &p) { p = -1; }
-__device__ __forceinline__ void none(int4 &p) { p = make_int4(-1, -1, -1, -1); }
 
 // ---- forward -------------------------------------------------------------------------------------------------------------------
 struct FwdArgs {
@@ -108,20 +65,6 @@ struct FwdArgs {
     int64_t lda;
 };
 
-// the entry at position p meets the running (value, position): the first entry is taken as it is, a later one only when it is better
-__device__ __forceinline__ void meet(float &val, int32_t &pos, float t, int32_t p)
-{
-    const bool take = pos < 0 || t > val;
-    val = take ? t : val;
-    pos = take ? p : pos;
-}
-__device__ __forceinline__ void meet(float4 &val, int4 &pos, float4 t, int32_t p)
-{
-    meet(val.x, pos.x, t.x, p);
-    meet(val.y, pos.y, t.y, p);
-    meet(val.z, pos.z, t.z, p);
-    meet(val.w, pos.w, t.w, p);
-}
 // what is stored for a lane's features: the value with its own sign again, +0 where the row has no entry
 __device__ __forceinline__ float stored(float val, int32_t pos, uint32_t sign) { return pos < 0 ? 0.f : flip(val, sign); }
 __device__ __forceinline__ float4 stored(float4 v, int4 p, uint32_t s)
@@ -181,7 +124,7 @@ __global__ __launch_bounds__(256) void fwd_rows_kernel(FwdArgs a, Lists w)
     if (row >= a.n_rows) return;                // uniform in the lane group; shuffles only ever meet lanes of the own group
     const int64_t b = a.rowptr[row], e = a.rowptr[row + 1];
     if (e - b > kSeg) {
-        if (li == 0 && blockIdx.y == 0) list_hub(w, (int32_t)row, e - b);
+        if (li == 0 && blockIdx.y == 0) append(w.hubs, (int32_t)row, e - b);
         return;
     }
     V val;
@@ -194,10 +137,10 @@ __global__ __launch_bounds__(256) void fwd_rows_kernel(FwdArgs a, Lists w)
     if (a.arg) *reinterpret_cast<P *>(a.arg + row * a.lda + f0) = pos;
 }
 
-// The lane groups of the segment kernels stride over the slots the row kernel handed out; a slot names its hub, the hub its row and
-// its first slot.  body(b, e, at, ...): the segment's entries b .. e - 1 and the slot's place in the partials.
+// The lane groups of the segment kernels stride over the hub list's slots.  body(b, e, at, ...): the segment's entries b .. e - 1 and
+// the slot's place in the partials.
 template <int G, int VEC, class Body>
-__device__ __forceinline__ void for_hub_segments(const int32_t *__restrict__ rowptr, int32_t F, const Lists &w, Body body)
+__device__ __forceinline__ void for_group_segments(const int32_t *__restrict__ rowptr, int32_t F, const Lists &w, Body body)
 {
     constexpr int GROUPS = 256 / G;
     const int li = threadIdx.x % G;
@@ -205,17 +148,8 @@ __device__ __forceinline__ void for_hub_segments(const int32_t *__restrict__ row
     const int64_t f0 = ((int64_t)blockIdx.y * G + li) * VEC;
     const bool active = f0 < F;
     const int64_t fa = active ? f0 : 0;
-    const int64_t n_slots = listed(&w.counters[1], w.cap_seg);
-    for (int64_t slot = (int64_t)blockIdx.x * GROUPS + threadIdx.x / G; slot < n_slots; slot += (int64_t)gridDim.x * GROUPS) {
-        const int32_t h = w.seg_hub[slot];
-        if (h < 0) continue;
-        const int32_t row = w.hub_rows[h];
-        const int64_t s = slot - w.hub_seg0[h];
-        const int64_t re = rowptr[row + 1];
-        const int64_t b = (int64_t)rowptr[row] + s * kSeg;
-        const int64_t e = b + kSeg < re ? b + kSeg : re;
-        body(b, e, slot * F + f0, li, gbase, fa, active);
-    }
+    for_hub_segments(w.hubs, rowptr, (int64_t)blockIdx.x * GROUPS + threadIdx.x / G, (int64_t)gridDim.x * GROUPS,
+                     [&](int32_t, int32_t, int64_t, int64_t b, int64_t n, int64_t slot) { body(b, b + n, slot * F + f0, li, gbase, fa, active); });
 }
 
 template <int G, int VEC>
@@ -223,7 +157,7 @@ __global__ __launch_bounds__(256) void fwd_seg_kernel(FwdArgs a, Lists w)
 {
     using V = typename Piece<VEC>::F;
     using P = typename Piece<VEC>::I;
-    for_hub_segments<G, VEC>(a.rowptr, a.F, w, [&](int64_t b, int64_t e, int64_t at, int li, int gbase, int64_t fa, bool active) {
+    for_group_segments<G, VEC>(a.rowptr, a.F, w, [&](int64_t b, int64_t e, int64_t at, int li, int gbase, int64_t fa, bool active) {
         V val;
         P pos;
         clear(val);
@@ -239,13 +173,13 @@ __global__ __launch_bounds__(256) void fwd_seg_kernel(FwdArgs a, Lists w)
 // a thread per (hub, feature): the segments meet in ascending order, so of equal values the smaller position stays
 __global__ __launch_bounds__(256) void fwd_combine_kernel(FwdArgs a, Lists w)
 {
-    const int64_t total = listed(&w.counters[0], w.cap_hub) * a.F;
+    const int64_t total = listed_hubs(w.hubs) * a.F;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         const int64_t h = idx / a.F, f = idx - h * a.F;
-        const int32_t row = w.hub_rows[h];
+        const int32_t row = w.hubs.hub_rows[h];
         if (row < 0) continue;
         const int64_t nseg = ((int64_t)a.rowptr[row + 1] - a.rowptr[row] + kSeg - 1) / kSeg;
-        const int64_t at = (int64_t)w.hub_seg0[h] * a.F + f;
+        const int64_t at = (int64_t)w.hubs.hub_seg0[h] * a.F + f;
         float val = 0.f;
         int32_t pos = -1;
         for (int64_t s = 0; s < nseg; s++) meet(val, pos, w.part_val[at + s * a.F], w.part_pos[at + s * a.F]);
@@ -274,8 +208,6 @@ __device__ __forceinline__ float4 route(float4 acc, float4 t, int4 won, int32_t 
 {
     return make_float4(route(acc.x, t.x, won.x, p), route(acc.y, t.y, won.y, p), route(acc.z, t.z, won.z, p), route(acc.w, t.w, won.w, p));
 }
-__device__ __forceinline__ float add(float a, float b) { return a + b; }
-__device__ __forceinline__ float4 add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // B entries k .. k + B - 1 from the top of the group's current window (entries top - k, top - k - 1, ...): all loads, then the adds
 template <int G, int VEC, int B>
@@ -331,7 +263,7 @@ __global__ __launch_bounds__(256) void bwd_rows_kernel(BwdArgs a, Lists w)
     if (row >= a.n_rows) return;
     const int64_t b = a.rowptr[row], e = a.rowptr[row + 1];
     if (e - b > kSeg) {
-        if (li == 0 && blockIdx.y == 0) list_hub(w, (int32_t)row, e - b);
+        if (li == 0 && blockIdx.y == 0) append(w.hubs, (int32_t)row, e - b);
         return;
     }
     V acc;
@@ -346,7 +278,7 @@ template <int G, int VEC>
 __global__ __launch_bounds__(256) void bwd_seg_kernel(BwdArgs a, Lists w)
 {
     using V = typename Piece<VEC>::F;
-    for_hub_segments<G, VEC>(a.rowptr, a.F, w, [&](int64_t b, int64_t e, int64_t at, int li, int gbase, int64_t fa, bool active) {
+    for_group_segments<G, VEC>(a.rowptr, a.F, w, [&](int64_t b, int64_t e, int64_t at, int li, int gbase, int64_t fa, bool active) {
         V acc;
         clear(acc);
         bwd_span<G, VEC>(acc, b, e, li, gbase, fa, a);
@@ -357,13 +289,13 @@ __global__ __launch_bounds__(256) void bwd_seg_kernel(BwdArgs a, Lists w)
 // a thread per (hub, feature): ((seg_0 + seg_1) + seg_2) + ...
 __global__ __launch_bounds__(256) void bwd_combine_kernel(BwdArgs a, Lists w)
 {
-    const int64_t total = listed(&w.counters[0], w.cap_hub) * a.F;
+    const int64_t total = listed_hubs(w.hubs) * a.F;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         const int64_t h = idx / a.F, f = idx - h * a.F;
-        const int32_t row = w.hub_rows[h];
+        const int32_t row = w.hubs.hub_rows[h];
         if (row < 0) continue;
         const int64_t nseg = ((int64_t)a.rowptr[row + 1] - a.rowptr[row] + kSeg - 1) / kSeg;
-        const int64_t at = (int64_t)w.hub_seg0[h] * a.F + f;
+        const int64_t at = (int64_t)w.hubs.hub_seg0[h] * a.F + f;
         float z = w.part_val[at];
         for (int64_t s = 1; s < nseg; s++) z = z + w.part_val[at + s * a.F];
         float *dst = a.dX + (int64_t)row * a.ldx + f;
@@ -385,18 +317,18 @@ inline Shape shape_of(int32_t F, bool vec)
     return Shape{vec, G, (uint32_t)ceil_div(lanes, G)};
 }
 
-inline uint32_t seg_blocks(const Lists &w, int G) { return (uint32_t)ceil_div(w.cap_seg < kSegGroups ? w.cap_seg : kSegGroups, 256 / G); }
-inline uint32_t combine_blocks(const Lists &w, int32_t F) { return (uint32_t)ceil_div(w.cap_hub * F < (1 << 19) ? w.cap_hub * F : (1 << 19), 256); }
+inline uint32_t seg_blocks(const HubList &w, int G) { return (uint32_t)ceil_div(w.cap_seg < kSegGroups ? w.cap_seg : kSegGroups, 256 / G); }
+inline uint32_t combine_blocks(const HubList &w, int32_t F) { return (uint32_t)ceil_div(w.cap_hub * F < (1 << 19) ? w.cap_hub * F : (1 << 19), 256); }
 
 template <int G, int VEC>
 int launch_fwd(const FwdArgs &a, const Lists &w, uint32_t tiles, hipStream_t st)
 {
     hipLaunchKernelGGL((fwd_rows_kernel<G, VEC>), dim3((uint32_t)ceil_div(a.n_rows, 256 / G), tiles), dim3(256), 0, st, a, w);
     GNNX_LAUNCH_CHECK();
-    if (w.cap_hub > 0) {
-        hipLaunchKernelGGL((fwd_seg_kernel<G, VEC>), dim3(seg_blocks(w, G), tiles), dim3(256), 0, st, a, w);
+    if (w.hubs.cap_hub > 0) {
+        hipLaunchKernelGGL((fwd_seg_kernel<G, VEC>), dim3(seg_blocks(w.hubs, G), tiles), dim3(256), 0, st, a, w);
         GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(fwd_combine_kernel, dim3(combine_blocks(w, a.F)), dim3(256), 0, st, a, w);
+        hipLaunchKernelGGL(fwd_combine_kernel, dim3(combine_blocks(w.hubs, a.F)), dim3(256), 0, st, a, w);
         GNNX_LAUNCH_CHECK();
     }
     return GNNX_OK;
@@ -407,10 +339,10 @@ int launch_bwd(const BwdArgs &a, const Lists &w, uint32_t tiles, hipStream_t st)
 {
     hipLaunchKernelGGL((bwd_rows_kernel<G, VEC>), dim3((uint32_t)ceil_div(a.n_rows, 256 / G), tiles), dim3(256), 0, st, a, w);
     GNNX_LAUNCH_CHECK();
-    if (w.cap_hub > 0) {
-        hipLaunchKernelGGL((bwd_seg_kernel<G, VEC>), dim3(seg_blocks(w, G), tiles), dim3(256), 0, st, a, w);
+    if (w.hubs.cap_hub > 0) {
+        hipLaunchKernelGGL((bwd_seg_kernel<G, VEC>), dim3(seg_blocks(w.hubs, G), tiles), dim3(256), 0, st, a, w);
         GNNX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(bwd_combine_kernel, dim3(combine_blocks(w, a.F)), dim3(256), 0, st, a, w);
+        hipLaunchKernelGGL(bwd_combine_kernel, dim3(combine_blocks(w.hubs, a.F)), dim3(256), 0, st, a, w);
         GNNX_LAUNCH_CHECK();
     }
     return GNNX_OK;

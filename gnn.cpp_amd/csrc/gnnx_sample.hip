@@ -16,22 +16,21 @@
 //   * long rows, L < d <= S = 4096: the row kernel appends them to a second list and a fixed grid gives each a wavefront of its own.
 //     On a power-law graph they are few, sit next to each other (low ids) and cost hundreds of passes over a narrow lane group:
 //     left in the row kernel they were 1.9 of the 2.0 ms of a call on the R-MAT graph of 10^6 vertices.
-//   * hub rows, d > S: the row kernel appends them to a list in the workspace (a counter atomic reserves the hub's slot and its run
-//     of segment slots, as in gnnx_reduce.hip: never an atomic on a value); a fixed grid of wavefronts strides over the segments of S
-//     consecutive entries and writes the offsets j of each segment's min(k, len) smallest keys, ascending, to the segment's slot; one
-//     wavefront per hub then selects the k smallest of the hub's candidates (every segment but the last gives exactly k, so they
-//     are one contiguous ascending run) and writes the row.  The k smallest of a row are among the k smallest of their segments.
+//   * hub rows, d > S: the row kernel appends them to the hub list (gnnx_worklist.h); a fixed grid of wavefronts strides over the
+//     segments of S consecutive entries and writes the offsets j of each segment's min(k, len) smallest keys, ascending, to the
+//     segment's slot; one wavefront per hub then selects the k smallest of the hub's candidates (every segment but the last gives
+//     exactly k, so they are one contiguous ascending run) and writes the row.  The k smallest of a row are among the k smallest of
+//     their segments.
 // Integer work only.  Every loop is bounded by a row, segment or candidate length or by the 64 key bits; there is no spin wait.
-#include "gnnx_common.h"
+#include "gnnx_worklist.h"
 
 using namespace gnnx;
 
 namespace {
 
-constexpr int kSeg = 4096;         // S: rows longer than this are selected by segments
 constexpr int kLong = 256;         // L: rows longer than this (and not longer than S) get a wavefront of their own
 constexpr int kMaxFanout = 64;     // one wavefront holds a segment's candidates
-constexpr int kCounters = 16;      // int32 words in front of the workspace: [0] hubs, [1] segment slots, [2] kept entries in all, [3] long rows
+constexpr int kCounters = 16;      // int32 words in front of the workspace: [0], [1] the hub list's, [2] kept entries in all, [3] long rows
 constexpr int kSegWaves = 8192;    // wavefronts of the long-row, segment and combine kernels (stride over their lists)
 constexpr int kScanTile = 1024;    // rows per block of the scan kernels: 4 per thread
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
@@ -55,38 +54,28 @@ __device__ __forceinline__ uint64_t key_of(uint64_t s, uint32_t row, uint32_t j)
 struct Lists {
     int32_t *counters;    // kCounters words, zeroed by a memset on the stream in front of the first kernel
     int32_t *tile_sum;    // [n_tiles] kept entries of a tile of kScanTile rows, then their exclusive scan
-    int32_t *hub_rows;    // [cap_hub]; -1: a hub whose segments did not fit (only a broken CSR can do that)
-    int32_t *hub_seg0;    // [cap_hub] first slot of the hub's segments
-    int32_t *seg_hub;     // [cap_seg] the hub (its slot in hub_rows) that a segment slot belongs to; -1: none
+    HubList hubs;
     int32_t *cand;        // [cap_seg, k] the offsets j of a segment's smallest keys, ascending
     int32_t *long_rows;   // [cap_long] rows of more than L and at most S entries
-    int64_t n_tiles, cap_hub, cap_seg, cap_long;
+    int64_t n_tiles, cap_long;
 };
 
 // bytes the carving takes from the first 256-byte boundary on; the query adds 256 for a workspace at any address
 size_t carve(int32_t n_rows, int64_t nnz, int32_t k, void *ws, Lists *out)
 {
     Lists w{};
-    w.n_tiles = (int64_t)n_rows / kScanTile + 1;                         // tiles that cover the n_rows + 1 values of rowptr_out
-    w.cap_hub = nnz / (kSeg + 1) < n_rows ? nnz / (kSeg + 1) : n_rows;   // rows of more than S entries
-    w.cap_seg = nnz / kSeg + w.cap_hub;                                  // sum of ceil(d / S) <= nnz / S + hubs
-    w.cap_long = nnz / (kLong + 1) < n_rows ? nnz / (kLong + 1) : n_rows;   // rows of more than L entries
-    char *p = ws ? aligned_base(ws) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t words) {
-        char *q = p ? p + off : nullptr;
-        off += 4 * words;
-        return reinterpret_cast<int32_t *>(q);
-    };
-    w.counters = take(kCounters);
-    w.tile_sum = take((size_t)w.n_tiles);
-    w.hub_rows = take((size_t)w.cap_hub);
-    w.hub_seg0 = take((size_t)w.cap_hub);
-    w.seg_hub = take((size_t)w.cap_seg);
-    w.cand = take((size_t)w.cap_seg * k);
-    w.long_rows = take((size_t)w.cap_long);
+    w.n_tiles = (int64_t)n_rows / kScanTile + 1;   // tiles that cover the n_rows + 1 values of rowptr_out
+    w.hubs.size(n_rows, nnz);
+    w.cap_long = cap_rows_longer(n_rows, nnz, kLong);
+    Carver c(ws ? aligned_base(ws) : nullptr);
+    w.counters = c.take<int32_t>(kCounters, 4);
+    w.tile_sum = c.take<int32_t>((size_t)w.n_tiles, 4);
+    w.hubs.take_hubs(c, w.counters);
+    w.hubs.take_slots(c);
+    w.cand = c.take<int32_t>((size_t)w.hubs.cap_seg * k, 4);
+    w.long_rows = c.take<int32_t>((size_t)w.cap_long, 4);
     if (out) *out = w;
-    return align256(off);
+    return c.bytes();
 }
 
 struct Args {
@@ -238,26 +227,6 @@ __device__ __forceinline__ void store_entry(const Args &a, int32_t row, int64_t 
     if (a.rowid_out) a.rowid_out[q] = row;
 }
 
-__device__ __forceinline__ int64_t listed(const int32_t *counter, int64_t cap)
-{
-    const int64_t n = *counter;
-    return n < cap ? n : cap;
-}
-
-// one lane per hub row: its slot in the list and its run of segment slots
-__device__ __forceinline__ void list_hub(const Lists &w, int32_t row, int64_t d)
-{
-    const int32_t nseg = (int32_t)((d + kSeg - 1) / kSeg);
-    const int32_t h = atomicAdd(&w.counters[0], 1);
-    const int32_t s0 = atomicAdd(&w.counters[1], nseg);
-    const bool fits = h < w.cap_hub && (int64_t)s0 + nseg <= w.cap_seg;   // holds on a valid CSR
-    if (h < w.cap_hub) {
-        w.hub_rows[h] = fits ? row : -1;
-        w.hub_seg0[h] = fits ? s0 : 0;
-    }
-    for (int64_t x = s0; x < (int64_t)s0 + nseg && x < w.cap_seg; x++) w.seg_hub[x] = fits ? h : -1;
-}
-
 // 256 / G rows per block
 template <int G>
 __global__ __launch_bounds__(256) void rows_kernel(Args a, Lists w)
@@ -271,7 +240,7 @@ __global__ __launch_bounds__(256) void rows_kernel(Args a, Lists w)
     const int64_t d = (int64_t)a.rowptr[row + 1] - b;
     const int64_t o = a.rowptr_out[row];
     if (d > kSeg) {
-        if (li == 0) list_hub(w, row, d);
+        if (li == 0) append(w.hubs, row, d);
         return;
     }
     if (d > kLong) {          // (L >= the largest k: such a row is never a copy)
@@ -310,23 +279,18 @@ __global__ __launch_bounds__(256) void long_rows_kernel(Args a, Lists w)
 __global__ __launch_bounds__(256) void seg_kernel(Args a, Lists w)
 {
     const int li = threadIdx.x & 63;
-    const int64_t n_slots = listed(&w.counters[1], w.cap_seg);
-    for (int64_t slot = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); slot < n_slots; slot += (int64_t)gridDim.x * 4) {
-        const int32_t h = w.seg_hub[slot];
-        if (h < 0) continue;
-        const int32_t row = w.hub_rows[h];
-        const int64_t d = (int64_t)a.rowptr[row + 1] - a.rowptr[row];
-        const int32_t j0 = (int32_t)((slot - w.hub_seg0[h]) * kSeg);
-        const int32_t len = d - j0 < kSeg ? (int32_t)(d - j0) : kSeg;
+    for_hub_segments(w.hubs, a.rowptr, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), (int64_t)gridDim.x * 4,
+                     [&](int32_t row, int32_t, int64_t s, int64_t, int64_t n, int64_t slot) {
+        const int32_t j0 = (int32_t)(s * kSeg), len = (int32_t)n;
         int32_t *out = w.cand + slot * a.k;
         auto j_of = [j0](int32_t x) { return j0 + x; };
         if (len <= a.k) {
             for (int32_t x = li; x < len; x += 64) out[x] = j0 + x;
-            continue;
+            return;
         }
         const uint64_t bound = kth_key<64>(a.s, (uint32_t)row, len, a.k, li, j_of);
         keep_below<64>(a.s, (uint32_t)row, len, bound, a.k, li, 0, j_of, [&](int32_t at, int32_t j) { out[at] = j; });
-    }
+    });
 }
 
 // a wavefront per hub: the k smallest of its candidates.  Every segment but the last holds exactly k (S > k), so the hub's candidates
@@ -334,9 +298,9 @@ __global__ __launch_bounds__(256) void seg_kernel(Args a, Lists w)
 __global__ __launch_bounds__(256) void combine_kernel(Args a, Lists w)
 {
     const int li = threadIdx.x & 63;
-    const int64_t n_hubs = listed(&w.counters[0], w.cap_hub);
+    const int64_t n_hubs = listed_hubs(w.hubs);
     for (int64_t h = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); h < n_hubs; h += (int64_t)gridDim.x * 4) {
-        const int32_t row = w.hub_rows[h];
+        const int32_t row = w.hubs.hub_rows[h];
         if (row < 0) continue;
         const int64_t b = a.rowptr[row];
         const int64_t d = (int64_t)a.rowptr[row + 1] - b;
@@ -344,7 +308,7 @@ __global__ __launch_bounds__(256) void combine_kernel(Args a, Lists w)
         const int64_t nseg = (d + kSeg - 1) / kSeg;
         const int64_t last = d - (nseg - 1) * kSeg;
         const int32_t n = (int32_t)((nseg - 1) * a.k + (last < a.k ? last : a.k));   // > k: a hub has at least two segments
-        const int32_t *cand = w.cand + (int64_t)w.hub_seg0[h] * a.k;
+        const int32_t *cand = w.cand + (int64_t)w.hubs.hub_seg0[h] * a.k;
         auto j_of = [cand](int32_t x) { return cand[x]; };
         const uint64_t bound = kth_key<64>(a.s, (uint32_t)row, n, a.k, li, j_of);
         keep_below<64>(a.s, (uint32_t)row, n, bound, a.k, li, 0, j_of, [&](int32_t at, int32_t j) { store_entry(a, row, o + at, b, j); });
@@ -423,10 +387,11 @@ GNNX_API int gnnx_csr_sample_neighbors(int32_t n_rows, int64_t nnz, const int32_
             hipLaunchKernelGGL(long_rows_kernel, dim3((uint32_t)ceil_div(w.cap_long < kSegWaves ? w.cap_long : kSegWaves, 4)), dim3(256), 0, st, a, w);
             GNNX_LAUNCH_CHECK();
         }
-        if (w.cap_hub > 0) {   // nnz > S: a row can be longer than S
-            hipLaunchKernelGGL(seg_kernel, dim3((uint32_t)ceil_div(w.cap_seg < kSegWaves ? w.cap_seg : kSegWaves, 4)), dim3(256), 0, st, a, w);
+        const HubList &hubs = w.hubs;
+        if (hubs.cap_hub > 0) {   // nnz > S: a row can be longer than S
+            hipLaunchKernelGGL(seg_kernel, dim3((uint32_t)ceil_div(hubs.cap_seg < kSegWaves ? hubs.cap_seg : kSegWaves, 4)), dim3(256), 0, st, a, w);
             GNNX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(combine_kernel, dim3((uint32_t)ceil_div(w.cap_hub < kSegWaves ? w.cap_hub : kSegWaves, 4)), dim3(256), 0, st, a, w);
+            hipLaunchKernelGGL(combine_kernel, dim3((uint32_t)ceil_div(hubs.cap_hub < kSegWaves ? hubs.cap_hub : kSegWaves, 4)), dim3(256), 0, st, a, w);
             GNNX_LAUNCH_CHECK();
         }
     }

@@ -120,18 +120,13 @@ hipError_t listed_ws(int64_t n_listed, char *base, ListedWs &w)
     hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)n_listed + 1,
                                            rocprim::plus<int64_t>());
     if (e != hipSuccess) return e;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + o : nullptr;
-        o += align256(bytes);
-        return p;
-    };
-    w.len = reinterpret_cast<int64_t *>(take(sizeof(int64_t) * ((size_t)n_listed + 1)));
-    w.off = reinterpret_cast<int64_t *>(take(sizeof(int64_t) * ((size_t)n_listed + 1)));
-    w.bad = reinterpret_cast<int32_t *>(take(256));
-    w.prim = take(scan_bytes);
+    Carver c(base);
+    w.len = c.take<int64_t>((size_t)n_listed + 1, 256);
+    w.off = c.take<int64_t>((size_t)n_listed + 1, 256);
+    w.bad = c.take<int32_t>(64, 256);
+    w.prim = c.take<char>(scan_bytes, 256);
     w.prim_bytes = scan_bytes;
-    w.total = o + 256;   // room to align the caller's pointer
+    w.total = c.bytes() + 256;   // room to align the caller's pointer
     return hipSuccess;
 }
 

@@ -265,22 +265,16 @@ struct CeWs {
 // bytes the loss needs; with `base` (any alignment) also the layout in *out
 size_t carve(int64_t n_listed, int32_t n_classes, bool want_colsum, void *base, CeWs *out)
 {
-    char *p = base ? aligned_base(base) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = p ? p + off : nullptr;
-        off += bytes;
-        return q;
-    };
+    Carver c(base ? aligned_base(base) : nullptr);
     CeWs w{};
-    w.row_loss = reinterpret_cast<float *>(take(sizeof(float) * (size_t)n_listed));
-    w.partial = reinterpret_cast<float *>(take(sizeof(float) * kSumBlocks));
-    w.bad = reinterpret_cast<int32_t *>(take(sizeof(int32_t)));
-    off = align256(off);
+    w.row_loss = c.take<float>((size_t)n_listed, 4);
+    w.partial = c.take<float>(kSumBlocks, 4);
+    w.bad = c.take<int32_t>(1, 4);
     const size_t parts = (size_t)(4 * ce_groups(n_listed) > kCeGenericParts ? 4 * ce_groups(n_listed) : kCeGenericParts);
-    if (want_colsum) w.cpart = reinterpret_cast<float *>(take(sizeof(float) * parts * (size_t)n_classes));
+    float *cpart = c.take<float>(want_colsum ? parts * (size_t)n_classes : 0, 256);
+    if (want_colsum) w.cpart = cpart;
     if (out) *out = w;
-    return off + 256;   // room to align the caller's pointer
+    return c.off + 256;   // room to align the caller's pointer (the end of cpart is not rounded up: the count callers have always got)
 }
 
 // The loss over every row of the matrix (rows == nullptr: n_listed == n_rows) or over the listed rows, divisor n_total: the same
