@@ -160,6 +160,9 @@ _SIGS = {
                                         _sz, _vp],
     "gnnx_edge_softmax_bwd_csr_heads_f32": [_i32, _i32, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp,
                                             _i64, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_gatv2_scores_csr_f32": [_i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _vp, _i64, _vp],
+    "gnnx_gatv2_scores_bwd_csr_f32": [_i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _f32, _vp, _i64,
+                                      _vp, _i64, _vp],
     "gnnx_spmm_csr_reduce_workspace": [_i32, _i64, _i32, C.POINTER(_sz)],
     "gnnx_spmm_csr_reduce_f32": [C.c_int, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
     "gnnx_spmm_csr_reduce_bwd_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _sz, _vp],

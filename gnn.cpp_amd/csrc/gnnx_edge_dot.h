@@ -3,6 +3,7 @@
 // features, a lane group of G = min(64, pow2 >= Q) lanes, lane l owns chunks l, l + G, ... and adds their products in ascending f
 // to ONE accumulator, each product rounded before the sum; the G accumulators meet in an xor butterfly (s = 1, 2, .., G / 2).
 // "Head h carries the bits of the single-head call on slab h" holds because both units take every step of that order from here.
+// The GATv2 score (gnnx_gatv2.hip) sums in the same order; only its chunk step differs (add_leaky_chunk).
 #pragma once
 #include "gnnx_common.h"
 
@@ -51,6 +52,27 @@ __device__ __forceinline__ float add_chunk(float acc, const float4 &l, const flo
     if (VEC || f + 1 < F) acc = acc + (l.y * r.y);
     if (VEC || f + 2 < F) acc = acc + (l.z * r.z);
     if (VEC || f + 3 < F) acc = acc + (l.w * r.w);
+    return acc;
+}
+
+// the GATv2 score's chunk step (gnnx_gatv2.hip): acc = acc + (a * leaky(l + r)) in the same feature order -- the sum u = l + r, the
+// slope product u * slope (u <= 0, a zero included) and the term a * e are each rounded before the add
+__device__ __forceinline__ float leaky(float u, float slope) { return u > 0.f ? u : u * slope; }
+__device__ __forceinline__ float4 leaky(float4 u, float slope)
+{
+    return make_float4(leaky(u.x, slope), leaky(u.y, slope), leaky(u.z, slope), leaky(u.w, slope));
+}
+__device__ __forceinline__ float leaky_term(float l, float r, float a, float slope) { return a * leaky(l + r, slope); }
+
+template <bool VEC>
+__device__ __forceinline__ float add_leaky_chunk(float acc, const float4 &l, const float4 &r, const float4 &a, float slope, int32_t q,
+                                                 int32_t F)
+{
+    const int32_t f = 4 * q;
+    acc = acc + leaky_term(l.x, r.x, a.x, slope);
+    if (VEC || f + 1 < F) acc = acc + leaky_term(l.y, r.y, a.y, slope);
+    if (VEC || f + 2 < F) acc = acc + leaky_term(l.z, r.z, a.z, slope);
+    if (VEC || f + 3 < F) acc = acc + leaky_term(l.w, r.w, a.w, slope);
     return acc;
 }
 

@@ -866,6 +866,61 @@ def sddmm_heads(rowptr, colidx, L, R, n_heads, out=None):
     return out
 
 
+def _gatv2_vector(a, F, where):
+    if a.dim() != 1 or int(a.numel()) != F or a.dtype != torch.float32 or not a.is_contiguous():
+        raise capi.GnnxError(-2, where, f"a must be a contiguous float32 [{F}] vector, got {tuple(a.shape)} {a.dtype}")
+
+
+def gatv2_scores(rowptr, colidx, L, R, a, n_heads, negative_slope=0.2, out=None):
+    """gnnx_gatv2_scores_csr_f32: out[p, h] = sum_k a[hD + k] * leaky_relu(L[i, hD + k] + R[c_p, hD + k]) for every stored entry p of row
+    i -- the GATv2 score, entry-major float32 [nnz, H], summed in the lane-group order of sddmm_heads.  L: [n_rows, H*D], R: [n_cols, H*D]
+    (column slabs of wider matrices are fine; L is R is allowed); a: float32 [H*D], head h's vector in its slab."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    n_cols = int(R.shape[0])
+    D = _heads_of(R, n_heads, "gatv2_scores")
+    if tuple(L.shape) != (n_rows, n_heads * D):
+        raise capi.GnnxError(-2, "gatv2_scores", f"L is {tuple(L.shape)}, the pattern has {n_rows} rows and R {n_heads * D} features")
+    _gatv2_vector(a, n_heads * D, "gatv2_scores")
+    if out is None:
+        out = torch.empty((nnz, n_heads), dtype=torch.float32, device=R.device)
+    ldo = _entry_major(out, nnz, n_heads, "out", "gatv2_scores")
+    capi.call("gnnx_gatv2_scores_csr_f32", n_rows, n_cols, n_heads, D, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(L), _ld(L),
+              _ptr(R), _ld(R), _ptr(a), float(negative_slope), _ptr(out) if nnz else None, ldo, _stream())
+    return out
+
+
+def gatv2_scores_bwd(rowptr, colidx, de, own, other, a, n_heads, negative_slope=0.2, entry_map=None, out=None, beta=0.0, want_T=False,
+                     T_out=None):
+    """gnnx_gatv2_scores_bwd_csr_f32: the gradient of gatv2_scores to the ROW-SIDE operand of the pattern it is handed,
+        out[i, f] = beta*out + sum_p de[m_p, h] * (u > 0 ? a[f] : a[f] * slope),  u = own[i, f] + other[c_p, f],  m_p = entry_map[p] or p,
+    one accumulator per element over the row's entries from the last down (spmm_heads' order).  On the forward pattern (own = L, other = R)
+    it is dL; on the transposed pattern with entry_map = the transpose map (de stays in the forward order) and beta = 1 it adds dR onto
+    `out`.  want_T: also T[i, f] = sum_p de[m_p, h] * leaky_relu(u), whose colsum is the gradient of a; returns (out, T) then, else out.
+    de: entry-major float32 [nnz, H]; own: [n_rows, H*D]; other: [n_cols, H*D]; out / T_out: [n_rows, H*D], column slabs allowed."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    n_cols = int(other.shape[0])
+    D = _heads_of(other, n_heads, "gatv2_scores_bwd")
+    F = n_heads * D
+    if tuple(own.shape) != (n_rows, F):
+        raise capi.GnnxError(-2, "gatv2_scores_bwd", f"own is {tuple(own.shape)}, the pattern has {n_rows} rows and other {F} features")
+    _gatv2_vector(a, F, "gatv2_scores_bwd")
+    ldd = _entry_major(de, nnz, n_heads, "de", "gatv2_scores_bwd")
+    if entry_map is not None and (entry_map.dtype != torch.int32 or int(entry_map.numel()) != nnz or not entry_map.is_contiguous()):
+        raise capi.GnnxError(-2, "gatv2_scores_bwd", f"entry_map must be a contiguous int32 [{nnz}] array")
+    if out is None:
+        if beta:
+            raise capi.GnnxError(-2, "gatv2_scores_bwd", "beta = 1 adds onto `out`, which was not given")
+        out = torch.empty((n_rows, F), dtype=torch.float32, device=own.device)
+    T = T_out
+    if want_T and T is None:
+        T = torch.empty((n_rows, F), dtype=torch.float32, device=own.device)
+    assert tuple(out.shape) == (n_rows, F) and (T is None or tuple(T.shape) == (n_rows, F))
+    capi.call("gnnx_gatv2_scores_bwd_csr_f32", n_rows, n_cols, n_heads, D, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None,
+              _ptr(de) if nnz else None, ldd, _ptr(entry_map) if nnz else None, _ptr(own), _ld(own), _ptr(other), _ld(other), _ptr(a),
+              float(negative_slope), float(beta), _ptr(out), _ld(out), _ptr(T), _ld(T) if T is not None else F, _stream())
+    return (out, T) if T is not None else out
+
+
 def _edge_terms_heads(t, n, H, what):
     """(pointer, row stride in elements) of a per-vertex, per-head term: float32 [n, H] with unit stride along the heads (one half of an
     [n, 2H] matrix is fine)."""
@@ -1875,7 +1930,49 @@ class GcnStack(_Stack):
         return _loss_and_accuracy(logits, t, field.compact_rows)
 
 
-class GatStack(_Stack):
+class _AttentionStack(_Stack):
+    """What the attention stacks (GatStack, Gatv2Stack) share beyond _Stack: the heads of every layer, the transpose map of the graph,
+    and the three steps that ask how many heads a layer has or which pattern a value array is ordered by."""
+
+    @staticmethod
+    def _heads_per_layer(dims, heads):
+        L = len(dims) - 1
+        heads = [1] * L if heads is None else list(heads)
+        if len(heads) != L or any(int(k) != k or k < 1 for k in heads):
+            raise ValueError(f"heads must list {L} positive integers, one per layer, got {heads}")
+        bad = [l for l in range(L) if dims[l + 1] % heads[l]]
+        if bad:
+            raise ValueError(f"layer {bad[0]}: {dims[bad[0] + 1]} features do not split into {heads[bad[0]]} heads")
+        return [int(k) for k in heads]
+
+    def _bind(self, g):
+        self.g = g
+        self.map_t = g.attention_map()
+        return self
+
+    def _aggregate(self, l, X, vals, transposed=False, **epilogue):
+        """sum_p vals[p, h] * X[c_p, slab h] over the rows of the pattern (of the transposed pattern: vals in its order).  One head: the
+        planned kernel, which splits hub rows; several: spmm_heads, which has no plan."""
+        g = self.g
+        rowptr, colidx, plan = (g.rowptr_t, g.colidx_t, g.plan_t) if transposed else (g.rowptr, g.colidx, g.plan)
+        if self.heads[l] == 1:
+            return spmm(rowptr, colidx, X, vals=vals.reshape(-1), plan=plan, **epilogue)
+        return spmm_heads(rowptr, colidx, X, vals, self.heads[l], **epilogue)
+
+    def _vals_grad(self, l, G, H):
+        """dL/dalpha [nnz, Hh], the aggregation's value gradient.  One head: sddmm, which prefetches the next batch of columns."""
+        g = self.g
+        if self.heads[l] == 1:
+            return spmm_vals_grad(g.rowptr, g.colidx, G, H).reshape(-1, 1)
+        return sddmm_heads(g.rowptr, g.colidx, G, H, self.heads[l])
+
+    def _to_transposed(self, vals, out):
+        if self.g.nnz:
+            gather_rows(vals.reshape(int(vals.shape[0]), -1), self.map_t, out=out.reshape(int(out.shape[0]), -1))
+        return out
+
+
+class GatStack(_AttentionStack):
     """L graph-attention layers (GAT, Velickovic et al. 2018) on one graph, the surface of GcnStack.  Layer l has heads[l] heads of width
     D = dims[l+1] / heads[l]; per head
         H = h W^T;   el = H a_l,  er = H a_r;   alpha_ic = softmax over the stored entries c of row i of leaky_relu(el_i + er_c);
@@ -1907,13 +2004,7 @@ class GatStack(_Stack):
         self.dims = list(dims)
         self.negative_slope = float(negative_slope)
         L = len(dims) - 1
-        heads = [1] * L if heads is None else list(heads)
-        if len(heads) != L or any(int(k) != k or k < 1 for k in heads):
-            raise ValueError(f"heads must list {L} positive integers, one per layer, got {heads}")
-        bad = [l for l in range(L) if dims[l + 1] % heads[l]]
-        if bad:
-            raise ValueError(f"layer {bad[0]}: {dims[bad[0] + 1]} features do not split into {heads[bad[0]]} heads")
-        self.heads = [int(k) for k in heads]
+        self.heads = self._heads_per_layer(dims, heads)
         self.W = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
         self.A, self.A_mask = [], []
         for l, Hh in enumerate(self.heads):   # [a_l; a_r] drawn as one [2, dims[l+1]] matrix, laid out in the blocks of the [2 Hh, Hh D] one
@@ -1931,11 +2022,6 @@ class GatStack(_Stack):
         self._buf = {}
         self._opt = [None]
 
-    def _bind(self, g):
-        self.g = g
-        self.map_t = g.attention_map()
-        return self
-
     def params(self):
         return self.W + self.A + self.b
 
@@ -1949,22 +2035,6 @@ class GatStack(_Stack):
         ER = gemm(H, self.A[l], transB=True)
         alpha = edge_softmax_heads(g.rowptr, g.colidx, Hh, rowterm=ER[:, :Hh], colterm=ER[:, Hh:], negative_slope=self.negative_slope)
         return ER, alpha
-
-    def _aggregate(self, l, X, vals, transposed=False, **epilogue):
-        """sum_p vals[p, h] * X[c_p, slab h] over the rows of the pattern (of the transposed pattern: vals in its order).  One head: the
-        planned kernel, which splits hub rows; several: spmm_heads, which has no plan."""
-        g = self.g
-        rowptr, colidx, plan = (g.rowptr_t, g.colidx_t, g.plan_t) if transposed else (g.rowptr, g.colidx, g.plan)
-        if self.heads[l] == 1:
-            return spmm(rowptr, colidx, X, vals=vals.reshape(-1), plan=plan, **epilogue)
-        return spmm_heads(rowptr, colidx, X, vals, self.heads[l], **epilogue)
-
-    def _vals_grad(self, l, G, H):
-        """dL/dalpha [nnz, Hh], the aggregation's value gradient.  One head: sddmm, which prefetches the next batch of columns."""
-        g = self.g
-        if self.heads[l] == 1:
-            return spmm_vals_grad(g.rowptr, g.colidx, G, H).reshape(-1, 1)
-        return sddmm_heads(g.rowptr, g.colidx, G, H, self.heads[l])
 
     def forward(self, X):
         L = len(self.W)
@@ -2009,10 +2079,108 @@ class GatStack(_Stack):
                 G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
         return G
 
-    def _to_transposed(self, vals, out):
-        if self.g.nnz:
-            gather_rows(vals.reshape(int(vals.shape[0]), -1), self.map_t, out=out.reshape(int(out.shape[0]), -1))
-        return out
+
+class Gatv2Stack(_AttentionStack):
+    """L GATv2 layers (Brody, Alon, Yahav 2022: dynamic attention) on one graph, the surface and the graph requirements of GatStack.
+    Layer l has heads[l] heads of width D = dims[l+1] / heads[l]; per head
+        Hl = h W_l^T,  Hr = h W_r^T;   e_ic = a . leaky_relu(Hl_i + Hr_c);   alpha_ic = softmax of e over the stored entries c of row i;
+        h' = act( sum_c alpha_ic Hr_c + b ),  ReLU between layers, none after the last,
+    the heads concatenated.  The non-linearity sits INSIDE the sum over features, so two rows that store the same columns may rank them
+    differently, which GAT's leaky_relu(el_i + er_c) cannot.  heads=None means one head in every layer.  share_weights: W_l is W_r, one
+    product, one weight whose gradient is the sum of both.
+
+    The two weights of a layer ride as ONE parameter W[l] = [W_l; W_r] of shape [2 out, in] (W_l(l) / W_r(l) are its halves; with
+    share_weights W[l] is [out, in] and both are W[l] itself): one product gives [Hl | Hr] as [n, 2 out], the score and the aggregation
+    take the halves with ld = 2 out, the backward writes [dHl | dHr] into one [n, 2 out] buffer, and dW[l] and dh are one product each
+    as in GatStack.  a[l] is a [dims[l+1]] vector, head h's vector in its slab.  The score and its two backward passes are gatv2_scores /
+    gatv2_scores_bwd; the softmax runs on the given scores with slope 1; the aggregation, its value gradient and the transposed order are
+    GatStack's own steps (a one-head layer keeps the planned spmm and the prefetching sddmm).  da = colsum(T) with T from the forward-
+    pattern backward pass.  No atomics; the same bits every run."""
+
+    def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda", heads=None, share_weights=False):
+        self._bind(g)
+        self.dims = list(dims)
+        self.negative_slope = float(negative_slope)
+        self.share_weights = bool(share_weights)
+        L = len(dims) - 1
+        self.heads = self._heads_per_layer(dims, heads)
+        k = 1 if self.share_weights else 2
+        self.W = [uniform_pm1(seed + 2 * l, (k * dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.a = [uniform_pm1(seed + 2 * l + 1, (dims[l + 1],), scale=(dims[l + 1] // self.heads[l]) ** -0.5, device=device) for l in range(L)]
+        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
+        self.dW = [torch.zeros_like(w) for w in self.W]
+        self.da = [torch.zeros_like(a) for a in self.a]
+        self.db = [torch.zeros_like(b) for b in self.b]
+        self._saved = None
+        self._buf = {}
+        self._opt = [None]
+
+    def params(self):
+        return self.W + self.a + self.b
+
+    def grads(self):
+        return self.dW + self.da + self.db
+
+    def _halves(self, M, l):
+        """(left, right) of a layer's [., out] or [., 2 out] matrix along its columns: the same matrix twice with share_weights."""
+        out = self.dims[l + 1]
+        return (M, M) if self.share_weights else (M[:, :out], M[:, out:])
+
+    def W_l(self, l):
+        return self.W[l] if self.share_weights else self.W[l][:self.dims[l + 1]]
+
+    def W_r(self, l):
+        return self.W[l] if self.share_weights else self.W[l][self.dims[l + 1]:]
+
+    def attention(self, Hl, Hr, l):
+        """(e, alpha) of layer l, both entry-major [nnz, Hh]: e = gatv2_scores(Hl, Hr, a[l]), alpha = edge_softmax_heads(scores = e)."""
+        g, Hh = self.g, self.heads[l]
+        e = gatv2_scores(g.rowptr, g.colidx, Hl, Hr, self.a[l], Hh, negative_slope=self.negative_slope)
+        return e, edge_softmax_heads(g.rowptr, g.colidx, Hh, scores=e, negative_slope=1.0)
+
+    def forward(self, X):
+        L = len(self.W)
+        saved, h = [], X
+        for l in range(L):
+            Hlr = linear_fwd(h, self.W[l])
+            Hl, Hr = self._halves(Hlr, l)
+            e, alpha = self.attention(Hl, Hr, l)
+            Y = self._aggregate(l, Hr, alpha, bias=self.b[l], relu_out=l + 1 < L)   # only relu(Z) is stored (its sign is the mask)
+            saved.append((h, Hlr, e, alpha, Y))
+            h = Y
+        self._saved = saved
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """dW, da and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).  have_last_bias_grad: db[L-1]
+        was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        g, L, n = self.g, len(self.W), self.g.n
+        G = dOut
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            h, Hlr, e, alpha, _ = self._saved[l]
+            Hl, Hr = self._halves(Hlr, l)
+            Hh, out = self.heads[l], self.dims[l + 1]
+            dalpha = self._vals_grad(l, G, Hr)
+            de, _ = edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, scores=e, negative_slope=1.0,
+                                           drowterm_out=self._tmp(("drow", Hh), (n, Hh)), dt_out=self._tmp(("de", Hh), (g.nnz, Hh)))
+            dHlr = self._tmp(("dH", l), tuple(Hlr.shape))                                  # [dHl | dHr]; one matrix with share_weights
+            dHl, dHr = self._halves(dHlr, l)
+            vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh))
+            self._to_transposed(alpha, vals_t)
+            self._aggregate(l, G, vals_t, transposed=True, out=dHr)                        # through the aggregated rows
+            gatv2_scores_bwd(g.rowptr_t, g.colidx_t, de, Hr, Hl, self.a[l], Hh, negative_slope=self.negative_slope, entry_map=self.map_t,
+                             out=dHr, beta=1.0)                                            # + through the score's column side
+            gatv2_scores_bwd(g.rowptr, g.colidx, de, Hl, Hr, self.a[l], Hh, negative_slope=self.negative_slope, out=dHl,
+                             beta=1.0 if self.share_weights else 0.0, T_out=self._tmp(("T", l), (n, out)))   # the row side, and T
+            colsum(self._buf[("T", l)], out=self.da[l])
+            gemm(dHlr, h, transA=True, out=self.dW[l])
+            if l == 0:
+                G = gemm(dHlr, self.W[l]) if input_grad else None
+            else:   # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue
+                G, _ = gemm_relu_colsum(dHlr, self.W[l], h, colsum_out=self.db[l - 1])
+        return G
 
 
 def relu_mask(Y, dY, out=None):

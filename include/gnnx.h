@@ -845,6 +845,62 @@ int gnnx_edge_softmax_bwd_csr_heads_f32(int32_t n_rows, int32_t n_cols, int64_t 
                                         int64_t lda, const float *d_dalpha, int64_t ldd, float *d_dt, int64_t ldt, float *d_drowterm,
                                         int64_t drowterm_stride, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ dynamic attention scores (GATv2) ---- */
+/*
+ * The score of GATv2 (Brody, Alon, Yahav, ICLR 2022): e(i, c) = a^T leaky_relu(W_l h_i + W_r h_c), the non-linearity INSIDE the sum.  The
+ * GAT score leaky_relu(el_i + er_c) is monotone in er_c, so every row that stores the same columns ranks them alike; this one does not.
+ * It is not a composition of the calls above (the SDDMM is a plain dot product, the softmax's terms are one scalar per vertex and head):
+ * a per-entry, per-feature non-linearity is a kernel with the memory traffic of an aggregation -- one gathered H D row per stored entry.
+ * Everything around it exists: the softmax over given scores with slope 1 (gnnx_edge_softmax_csr_heads_f32), the aggregation with vals =
+ * alpha, its value gradient, gnnx_csr_transpose_map.  The conventions are the multi-head section's: feature matrices [rows, H D], head h
+ * in columns h D .. h D + D - 1; per-entry arrays entry-major [nnz, H] with a leading dimension.  Every operation is a separately rounded
+ * fp32 operation (-ffp-contract=off); tests/gatv2_ref.py restates both calls in NumPy and the GPU tests hold the kernels to it bit for bit.
+ *
+ * gnnx_gatv2_scores_csr_f32 -- for entry p of row i with column c = colidx[p], head h, feature f = h D + k:
+ *   u_f    = L[i, f] + R[c, f]
+ *   e_f    = u_f > 0 ? u_f : u_f * negative_slope          (u_f == 0 takes the slope branch)
+ *   term_f = a[f] * e_f
+ *   out[p * ldo + h] = the sum over k of term_f in the SDDMM lane-group order of gnnx_sddmm_csr_f32 with F := head_dim: the chunk step is
+ *   acc = acc + term_f, term_f in the place of the product and rounded before the add; chunks, lanes and the butterfly as documented there.
+ *   L: [n_rows, H D] ld ldl.  R: [n_cols, H D] ld ldr.  a: [H D] contiguous, a head's slice is its attention vector.  out: [nnz, H] ld ldo.
+ *   Work is dealt in the non-zero domain (a fixed number of entries per lane group, the row by a search in rowptr: a hub row spreads
+ *   over the device, no plan); the lane's pieces of L and a stay in registers while the row lasts.  The result does not depend on
+ *   alignment: head_dim % 4 != 0, or a pointer (L, R, a) or leading dimension (ldl, ldr) that is not 16-byte aligned, takes scalar loads
+ *   with the same feature-to-lane assignment and the same bits.  L == R is allowed; out aliases nothing.  nnz == 0 is GNNX_OK with no
+ *   launch.
+ *
+ * gnnx_gatv2_scores_bwd_csr_f32 -- the gradient to the ROW-SIDE operand of whichever pattern it is handed.  For row i and feature
+ *   f = h D + k: ONE accumulator from +0 over the row's entries p in DESCENDING stored position (the order of gnnx_spmm_csr_heads_f32):
+ *     m   = entry_map ? entry_map[p] : p
+ *     u   = Own[i, f] + Other[c_p, f]
+ *     w   = u > 0 ? a[f] : a[f] * negative_slope           (rounded once)
+ *     acc = acc + (de[m * ldd + h] * w)                    (the product rounded, then the sum)
+ *   dOwn[i, f] = beta ? dOwn[i, f] + acc : acc             (beta is 0 or 1)
+ *   With d_T != NULL a second accumulator runs in the same order:
+ *     e    = u > 0 ? u : u * negative_slope
+ *     tacc = tacc + (de[m * ldd + h] * e);                 T[i, f] = tacc
+ *   and the gradient of the attention vector is da = gnnx_colsum_f32(T), a call with a fixed order: no atomics anywhere on the path.
+ *   On the forward pattern with Own = L, Other = R, entry_map = NULL the call gives dL and T.  On the transposed pattern with Own = R,
+ *   Other = L, entry_map = map_t (gnnx_csr_transpose_map: de stays in the forward order), T = NULL and beta = 1 it adds dR onto the buffer
+ *   that already holds the aggregation's gradient; IEEE addition commutes, so u has the forward's bits in both passes.
+ *   de: [nnz, H] ld ldd.  Own: [n_rows, H D] ld ld_own.  Other: [n_cols, H D] ld ld_other.  dOwn: [n_rows, H D] ld ld_down.  T: [n_rows, H D]
+ *   ld ldt or NULL.  Columns beyond H D of dOwn and T are never touched.  An empty row writes +0 (T too), or leaves dOwn unchanged with
+ *   beta = 1.  dOwn and T alias nothing.  There is NO PLAN, as in gnnx_spmm_csr_heads_f32: a row is one lane group's chain whatever its
+ *   length, G lanes per row with a 4-float (or 1-float) piece per lane, the Own and a pieces in registers for the whole row, several
+ *   Other rows in flight.  The alignment rule is the forward's, over Own, Other, a, dOwn, T and their leading dimensions.
+ *
+ * Both: null pointers, negative sizes, n_heads < 1, head_dim < 1, a leading dimension below its minimum (H D, or H for out / de), beta
+ * other than 0 or 1 and nnz >= 2^31 are GNNX_ERR_INVALID_ARG before any device call.  Asynchronous on `stream`; nothing is allocated or
+ * synchronised; the CSR and nnz (= rowptr[n_rows]) are trusted as in the aggregation.
+ */
+int gnnx_gatv2_scores_csr_f32(int32_t n_rows, int32_t n_cols, int32_t n_heads, int32_t head_dim, int64_t nnz, const int32_t *d_rowptr,
+                              const int32_t *d_colidx, const float *d_L, int64_t ldl, const float *d_R, int64_t ldr, const float *d_a,
+                              float negative_slope, float *d_out, int64_t ldo, void *stream);
+int gnnx_gatv2_scores_bwd_csr_f32(int32_t n_rows, int32_t n_cols, int32_t n_heads, int32_t head_dim, int64_t nnz, const int32_t *d_rowptr,
+                                  const int32_t *d_colidx, const float *d_de, int64_t ldd, const int32_t *d_entry_map, const float *d_Own,
+                                  int64_t ld_own, const float *d_Other, int64_t ld_other, const float *d_a, float negative_slope, float beta,
+                                  float *d_dOwn, int64_t ld_down, float *d_T, int64_t ldt, void *stream);
+
 /* ------------------------------------------------------------------ neighbourhood reductions ---- */
 /*
  * The reduce operators of message passing that are not a sum: an element-wise MAX / MIN over the stored entries of each row of a CSR
