@@ -186,6 +186,8 @@ _SIGS = {
     "gnnx_csr_extract_rows": [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _sz, _vp],
     "gnnx_csr_sample_workspace": [_i32, _i64, _i32, C.POINTER(_sz)],
     "gnnx_csr_sample_neighbors": [_i32, _i64, _vp, _vp, _i32, _u64, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _sz, _vp],
+    "gnnx_csr_sample_rows": [_i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _u64, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _sz, _vp],
+    "gnnx_csr_renumber_cols": [_i64, _vp, _vp, _i64, _vp, _sz, _vp],
     "gnnx_csr_sample_negatives": [_i32, _i32, _i64, _vp, _i64, _vp, _vp, _i32, _u64, _u32, _vp, C.POINTER(_i64), _vp, _sz, _vp],
     "gnnx_rank_counts_f32": [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnnx_comm_unique_id": [_vp],

@@ -21,6 +21,9 @@
 //     segment's slot; one wavefront per hub then selects the k smallest of the hub's candidates (every segment but the last gives
 //     exactly k, so they are one contiguous ascending run) and writes the row.  The k smallest of a row are among the k smallest of
 //     their segments.
+//   * a row list (gnnx_csr_sample_rows): the same kernels with a row indirection.  Output row x samples CSR row rows[x]; the key is
+//     formed from the CSR row, every offset, rowid and list entry from x.  The lists of long rows are sized for rows met once each:
+//     a listed row that repeats more often than they hold is selected by the row kernel's own lane group.
 // Integer work only.  Every loop is bounded by a row, segment or candidate length or by the 64 key bits; there is no spin wait.
 #include "gnnx_worklist.h"
 
@@ -30,7 +33,8 @@ namespace {
 
 constexpr int kLong = 256;         // L: rows longer than this (and not longer than S) get a wavefront of their own
 constexpr int kMaxFanout = 64;     // one wavefront holds a segment's candidates
-constexpr int kCounters = 16;      // int32 words in front of the workspace: [0], [1] the hub list's, [2] kept entries in all, [3] long rows
+constexpr int kCounters = 16;      // int32 words in front of the workspace: [0], [1] the hub list's, [2] kept entries in all, [3] long rows,
+                                   // [4] the range flag of a row list
 constexpr int kSegWaves = 8192;    // wavefronts of the long-row, segment and combine kernels (stride over their lists)
 constexpr int kScanTile = 1024;    // rows per block of the scan kernels: 4 per thread
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
@@ -78,17 +82,34 @@ size_t carve(int32_t n_rows, int64_t nnz, int32_t k, void *ws, Lists *out)
     return c.bytes();
 }
 
+// A call works on n_rows OUTPUT rows x.  Output row x samples row row_of(x) of the CSR: x itself for the whole graph, rows[x] with a
+// row list (gnnx_csr_sample_rows).  The key is formed from the CSR row; offsets in the outputs, rowid and every list in the
+// workspace are formed from x, so a row that the list repeats is two units of work with two outputs.
 struct Args {
     int32_t n_rows, k;
     uint64_t s;           // splitmix64(seed)
     const int32_t *rowptr, *colidx;
     int32_t *rowptr_out, *colidx_out, *pos_out, *rowid_out;
+    const int32_t *rows;  // [n_rows] the row list, or nullptr
+    int32_t n_csr_rows, n_cols;
+    uint8_t *col_mark;    // [n_cols] or nullptr: byte c becomes 1 for every kept entry of column c
+    int32_t *range_flag;  // counters + 4: set by the scan kernels when the list holds an id outside [0, n_csr_rows)
 };
 
+__device__ __forceinline__ int32_t row_of(const Args &a, int32_t x) { return a.rows ? a.rows[x] : x; }
+
 // ---- lengths and scan ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int32_t kept_of(const Args &a, int64_t row)
+__device__ __forceinline__ int32_t kept_of(const Args &a, int64_t x)
 {
-    if (row >= a.n_rows) return 0;
+    if (x >= a.n_rows) return 0;
+    int32_t row = (int32_t)x;
+    if (a.rows) {
+        row = a.rows[x];
+        if ((uint32_t)row >= (uint32_t)a.n_csr_rows) {   // refused on the host before anything is written
+            atomicOr(a.range_flag, 1);
+            return 0;
+        }
+    }
     const int32_t d = a.rowptr[row + 1] - a.rowptr[row];
     return d < 0 ? 0 : d < a.k ? d : a.k;   // (d < 0: a rowptr that gnnx_csr_validate would refuse)
 }
@@ -219,12 +240,14 @@ __device__ __forceinline__ void keep_below(uint64_t s, uint32_t row, int32_t n, 
     }
 }
 
-// kept entry q of `row` is its entry j
-__device__ __forceinline__ void store_entry(const Args &a, int32_t row, int64_t q, int64_t b, int32_t j)
+// kept entry q of output row x is entry j of its CSR row, which starts at b
+__device__ __forceinline__ void store_entry(const Args &a, int32_t x, int64_t q, int64_t b, int32_t j)
 {
-    a.colidx_out[q] = a.colidx[b + j];
+    const int32_t col = a.colidx[b + j];
+    a.colidx_out[q] = col;
     if (a.pos_out) a.pos_out[q] = (int32_t)(b + j);
-    if (a.rowid_out) a.rowid_out[q] = row;
+    if (a.rowid_out) a.rowid_out[q] = x;
+    if (a.col_mark && (uint32_t)col < (uint32_t)a.n_cols) a.col_mark[col] = 1;   // (many lanes storing the same 1 is the only race)
 }
 
 // 256 / G rows per block
@@ -235,28 +258,33 @@ __global__ __launch_bounds__(256) void rows_kernel(Args a, Lists w)
     const int gbase = (threadIdx.x & 63) - li;
     const int64_t row64 = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
     if (row64 >= a.n_rows) return;                // uniform in the lane group; shuffles and ballots only ever meet lanes of the own group
-    const int32_t row = (int32_t)row64;
+    const int32_t x = (int32_t)row64;
+    const int32_t row = row_of(a, x);
     const int64_t b = a.rowptr[row];
     const int64_t d = (int64_t)a.rowptr[row + 1] - b;
-    const int64_t o = a.rowptr_out[row];
-    if (d > kSeg) {
-        if (li == 0) append(w.hubs, row, d);
-        return;
-    }
+    const int64_t o = a.rowptr_out[x];
     if (d > kLong) {          // (L >= the largest k: such a row is never a copy)
+        // Listed by one lane.  The lists are sized for rows met once each; a row list may repeat a long row more often than they
+        // hold.  A row that found no slot is done right here by its lane group: slower, and the same entries.
+        int32_t listed_it = 0;
         if (li == 0) {
-            const int32_t x = atomicAdd(&w.counters[3], 1);
-            if (x < w.cap_long) w.long_rows[x] = row;   // holds on a valid CSR
+            if (d > kSeg) {
+                listed_it = append(w.hubs, x, d);
+            } else {
+                const int32_t at = atomicAdd(&w.counters[3], 1);
+                listed_it = at < w.cap_long;   // holds on a valid CSR without a row list
+                if (listed_it) w.long_rows[at] = x;
+            }
         }
-        return;
+        if (__shfl(listed_it, gbase, 64)) return;
     }
     if (d <= a.k) {
-        for (int32_t j = li; j < d; j += G) store_entry(a, row, o + j, b, j);
+        for (int32_t j = li; j < d; j += G) store_entry(a, x, o + j, b, j);
         return;
     }
-    auto j_of = [](int32_t x) { return x; };
+    auto j_of = [](int32_t t) { return t; };
     const uint64_t bound = kth_key<G>(a.s, (uint32_t)row, (int32_t)d, a.k, li, j_of);
-    keep_below<G>(a.s, (uint32_t)row, (int32_t)d, bound, a.k, li, gbase, j_of, [&](int32_t at, int32_t j) { store_entry(a, row, o + at, b, j); });
+    keep_below<G>(a.s, (uint32_t)row, (int32_t)d, bound, a.k, li, gbase, j_of, [&](int32_t at, int32_t j) { store_entry(a, x, o + at, b, j); });
 }
 
 // a wavefront per listed row of L < d <= S entries
@@ -265,13 +293,14 @@ __global__ __launch_bounds__(256) void long_rows_kernel(Args a, Lists w)
     const int li = threadIdx.x & 63;
     const int64_t n_long = listed(&w.counters[3], w.cap_long);
     auto j_of = [](int32_t x) { return x; };
-    for (int64_t x = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); x < n_long; x += (int64_t)gridDim.x * 4) {
-        const int32_t row = w.long_rows[x];
+    for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < n_long; t += (int64_t)gridDim.x * 4) {
+        const int32_t x = w.long_rows[t];
+        const int32_t row = row_of(a, x);
         const int64_t b = a.rowptr[row];
         const int32_t d = (int32_t)(a.rowptr[row + 1] - b);
-        const int64_t o = a.rowptr_out[row];
+        const int64_t o = a.rowptr_out[x];
         const uint64_t bound = kth_key<64>(a.s, (uint32_t)row, d, a.k, li, j_of);
-        keep_below<64>(a.s, (uint32_t)row, d, bound, a.k, li, 0, j_of, [&](int32_t at, int32_t j) { store_entry(a, row, o + at, b, j); });
+        keep_below<64>(a.s, (uint32_t)row, d, bound, a.k, li, 0, j_of, [&](int32_t at, int32_t j) { store_entry(a, x, o + at, b, j); });
     }
 }
 
@@ -279,8 +308,9 @@ __global__ __launch_bounds__(256) void long_rows_kernel(Args a, Lists w)
 __global__ __launch_bounds__(256) void seg_kernel(Args a, Lists w)
 {
     const int li = threadIdx.x & 63;
-    for_hub_segments(w.hubs, a.rowptr, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), (int64_t)gridDim.x * 4,
-                     [&](int32_t row, int32_t, int64_t s, int64_t, int64_t n, int64_t slot) {
+    for_hub_segments(w.hubs, a.rowptr, a.rows, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), (int64_t)gridDim.x * 4,
+                     [&](int32_t x, int32_t, int64_t s, int64_t, int64_t n, int64_t slot) {
+        const int32_t row = row_of(a, x);
         const int32_t j0 = (int32_t)(s * kSeg), len = (int32_t)n;
         int32_t *out = w.cand + slot * a.k;
         auto j_of = [j0](int32_t x) { return j0 + x; };
@@ -300,18 +330,19 @@ __global__ __launch_bounds__(256) void combine_kernel(Args a, Lists w)
     const int li = threadIdx.x & 63;
     const int64_t n_hubs = listed_hubs(w.hubs);
     for (int64_t h = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); h < n_hubs; h += (int64_t)gridDim.x * 4) {
-        const int32_t row = w.hubs.hub_rows[h];
-        if (row < 0) continue;
+        const int32_t x = w.hubs.hub_rows[h];
+        if (x < 0) continue;
+        const int32_t row = row_of(a, x);
         const int64_t b = a.rowptr[row];
         const int64_t d = (int64_t)a.rowptr[row + 1] - b;
-        const int64_t o = a.rowptr_out[row];
+        const int64_t o = a.rowptr_out[x];
         const int64_t nseg = (d + kSeg - 1) / kSeg;
         const int64_t last = d - (nseg - 1) * kSeg;
         const int32_t n = (int32_t)((nseg - 1) * a.k + (last < a.k ? last : a.k));   // > k: a hub has at least two segments
         const int32_t *cand = w.cand + (int64_t)w.hubs.hub_seg0[h] * a.k;
         auto j_of = [cand](int32_t x) { return cand[x]; };
         const uint64_t bound = kth_key<64>(a.s, (uint32_t)row, n, a.k, li, j_of);
-        keep_below<64>(a.s, (uint32_t)row, n, bound, a.k, li, 0, j_of, [&](int32_t at, int32_t j) { store_entry(a, row, o + at, b, j); });
+        keep_below<64>(a.s, (uint32_t)row, n, bound, a.k, li, 0, j_of, [&](int32_t at, int32_t j) { store_entry(a, x, o + at, b, j); });
     }
 }
 
@@ -331,51 +362,45 @@ int check_sizes(int32_t n_rows, int64_t nnz, int32_t k)
     return GNNX_OK;
 }
 
-}  // namespace
-
-GNNX_API int gnnx_csr_sample_workspace(int32_t n_rows, int64_t nnz, int32_t k, size_t *bytes)
+// Both entry points.  n_out: rows of the output (n_csr_rows, or the list's length); the workspace is carved for (n_out, nnz, k) and the
+// lane-group width comes from the CSR's mean row length.
+int sample(int32_t n_csr_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_rows, int32_t n_out,
+           int32_t k, uint64_t seed, int32_t *d_rowptr_out, int32_t *d_colidx_out, int32_t *d_pos_out, int32_t *d_rowid_out, uint8_t *d_col_mark,
+           int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    GNNX_REQUIRE(bytes, GNNX_ERR_INVALID_ARG, "null pointer");
-    if (int rc = check_sizes(n_rows, nnz, k)) return rc;
-    GNNX_REQUIRE(k <= kMaxFanout, GNNX_ERR_UNSUPPORTED, "fanout %d: at most %d (one wavefront holds a row's selection)", k, kMaxFanout);
-    *bytes = 256 + carve(n_rows, nnz, k, nullptr, nullptr);
-    return GNNX_OK;
-}
-
-GNNX_API int gnnx_csr_sample_neighbors(int32_t n_rows, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, int32_t k, uint64_t seed,
-                                       int32_t *d_rowptr_out, int32_t *d_colidx_out, int32_t *d_pos_out, int32_t *d_rowid_out,
-                                       int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace, size_t workspace_bytes, void *stream)
-{
-    if (int rc = check_sizes(n_rows, nnz, k)) return rc;
+    if (int rc = check_sizes(n_csr_rows, nnz, k)) return rc;
     GNNX_REQUIRE(nnz_capacity >= 0, GNNX_ERR_INVALID_ARG, "negative size");
     GNNX_REQUIRE(d_rowptr && d_rowptr_out && d_colidx_out && nnz_out && (d_colidx || nnz == 0), GNNX_ERR_INVALID_ARG, "null pointer");
     GNNX_REQUIRE(k <= kMaxFanout, GNNX_ERR_UNSUPPORTED, "fanout %d: at most %d (one wavefront holds a row's selection)", k, kMaxFanout);
     Lists w;
-    const size_t need = 256 + carve(n_rows, nnz, k, d_workspace, &w);
+    const size_t need = 256 + carve(n_out, nnz, k, d_workspace, &w);
     GNNX_REQUIRE(d_workspace && workspace_bytes >= need, GNNX_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
     *nnz_out = 0;
     hipStream_t st = as_stream(stream);
-    if (n_rows == 0) {   // a CSR of no rows: rowptr' = [0]
+    if (n_out == 0) {   // a CSR of no rows: rowptr' = [0]
         GNNX_HIP_CHECK(hipMemsetAsync(d_rowptr_out, 0, sizeof(int32_t), st));
         GNNX_HIP_CHECK(hipStreamSynchronize(st));
         return GNNX_OK;
     }
-    const Args a{n_rows, k, splitmix64(seed), d_rowptr, d_colidx, d_rowptr_out, d_colidx_out, d_pos_out, d_rowid_out};
+    const Args a{n_out,  k,          splitmix64(seed), d_rowptr,   d_colidx,      d_rowptr_out, d_colidx_out, d_pos_out, d_rowid_out,
+                 d_rows, n_csr_rows, n_cols,           d_col_mark, w.counters + 4};
     GNNX_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(int32_t) * kCounters, st));
     hipLaunchKernelGGL(tile_sums_kernel, dim3((uint32_t)w.n_tiles), dim3(256), 0, st, a, w);
     GNNX_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(256), 0, st, w);
     GNNX_LAUNCH_CHECK();
-    int32_t total = 0;
-    GNNX_HIP_CHECK(hipMemcpyAsync(&total, w.counters + 2, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    int32_t head[3] = {0, 0, 0};   // counters [2] the total, [3] (still 0), [4] the range flag
+    GNNX_HIP_CHECK(hipMemcpyAsync(head, w.counters + 2, sizeof(head), hipMemcpyDeviceToHost, st));
     GNNX_HIP_CHECK(hipStreamSynchronize(st));
+    GNNX_REQUIRE(!head[2], GNNX_ERR_INDEX_RANGE, "the row list holds an id outside [0, %d) (nothing was written)", n_csr_rows);
+    const int32_t total = head[0];
     *nnz_out = total;   // also when the capacity is refused: what the caller has to offer
     GNNX_REQUIRE(total <= nnz_capacity, GNNX_ERR_INVALID_ARG, "the sample holds %d entries, nnz_capacity is %lld (nothing was written)", total,
                  (long long)nnz_capacity);
     hipLaunchKernelGGL(rowptr_kernel, dim3((uint32_t)w.n_tiles), dim3(256), 0, st, a, w);
     GNNX_LAUNCH_CHECK();
     if (total > 0) {
-        const int64_t mean = nnz / n_rows;   // lanes per row: how the rows map to lanes is not in the result
+        const int64_t mean = nnz / n_csr_rows;   // lanes per row: how the rows map to lanes is not in the result
         int rc;
         if (mean > 32) rc = launch_rows<64>(a, w, st);
         else if (mean > 16) rc = launch_rows<32>(a, w, st);
@@ -397,4 +422,34 @@ GNNX_API int gnnx_csr_sample_neighbors(int32_t n_rows, int64_t nnz, const int32_
     }
     GNNX_HIP_CHECK(hipStreamSynchronize(st));
     return GNNX_OK;
+}
+}  // namespace
+
+GNNX_API int gnnx_csr_sample_workspace(int32_t n_rows, int64_t nnz, int32_t k, size_t *bytes)
+{
+    GNNX_REQUIRE(bytes, GNNX_ERR_INVALID_ARG, "null pointer");
+    if (int rc = check_sizes(n_rows, nnz, k)) return rc;
+    GNNX_REQUIRE(k <= kMaxFanout, GNNX_ERR_UNSUPPORTED, "fanout %d: at most %d (one wavefront holds a row's selection)", k, kMaxFanout);
+    *bytes = 256 + carve(n_rows, nnz, k, nullptr, nullptr);
+    return GNNX_OK;
+}
+
+GNNX_API int gnnx_csr_sample_neighbors(int32_t n_rows, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, int32_t k, uint64_t seed,
+                                       int32_t *d_rowptr_out, int32_t *d_colidx_out, int32_t *d_pos_out, int32_t *d_rowid_out,
+                                       int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return sample(n_rows, 0, nnz, d_rowptr, d_colidx, nullptr, n_rows, k, seed, d_rowptr_out, d_colidx_out, d_pos_out, d_rowid_out, nullptr,
+                  nnz_capacity, nnz_out, d_workspace, workspace_bytes, stream);
+}
+
+GNNX_API int gnnx_csr_sample_rows(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                  const int32_t *d_rows, int64_t n_listed, int32_t k, uint64_t seed, int32_t *d_rowptr_out, int32_t *d_colidx_out,
+                                  int32_t *d_pos_out, int32_t *d_rowid_out, uint8_t *d_col_mark, int64_t nnz_capacity, int64_t *nnz_out,
+                                  void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    GNNX_REQUIRE(n_listed >= 0 && n_cols >= 0, GNNX_ERR_INVALID_ARG, "negative size");
+    GNNX_REQUIRE(n_listed < (1ll << 31), GNNX_ERR_INVALID_ARG, "the row list does not fit int32 output rows");
+    GNNX_REQUIRE(d_rows || n_listed == 0, GNNX_ERR_INVALID_ARG, "null pointer");
+    return sample(n_rows, n_cols, nnz, d_rowptr, d_colidx, d_rows, (int32_t)n_listed, k, seed, d_rowptr_out, d_colidx_out, d_pos_out, d_rowid_out,
+                  d_col_mark, nnz_capacity, nnz_out, d_workspace, workspace_bytes, stream);   // (an empty list launches no kernel)
 }

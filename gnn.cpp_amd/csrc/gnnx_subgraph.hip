@@ -4,6 +4,7 @@
 //   position table     pos[R[k]] = k, -1 everywhere else
 //   row extraction     the CSR of the k listed rows: rowptr' = exclusive scan of their lengths, entries copied in STORED ORDER (the
 //                      summation order of the aggregation, also on a relabelled graph) with columns renumbered through a position table
+//   renumbering        colidx[q] = pos[colidx[q]] in place, for a block that was made with original column ids (gnnx_csr_sample_rows)
 // Marking and extraction work in the NON-ZERO domain of the LISTED rows, as restrict_* of gnnx_masked.hip does over the whole graph:
 // the listed lengths are scanned, the listed entries cut into chunks of 64, one wavefront a chunk; the owning listed row is found by
 // search in the scanned offsets (two wave-uniform searches bracket the chunk, one short search per lane inside the bracket).  A hub row
@@ -105,6 +106,17 @@ __global__ __launch_bounds__(256) void positions_kernel(const int32_t *rows, int
     const int32_t r = rows[k];
     if (r < 0 || r >= n || (k > 0 && rows[k - 1] >= r)) atomicOr(bad, kBadRowList);
     else pos[r] = (int32_t)k;
+}
+
+// colidx[q] = pos[colidx[q]] in place; an entry without a position (a column outside the table, or one that maps to -1) becomes -1
+__global__ __launch_bounds__(256) void renumber_cols_kernel(int64_t nnz, int32_t *colidx, const int32_t *pos, int64_t n_cols, int32_t *bad)
+{
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= nnz) return;
+    const int32_t c = colidx[q];
+    const int32_t p = c >= 0 && c < n_cols ? pos[c] : -1;
+    if (p < 0) atomicOr(bad, kBadColumn);
+    colidx[q] = p < 0 ? -1 : p;
 }
 
 struct ListedWs {
@@ -276,5 +288,25 @@ GNNX_API int gnnx_csr_extract_rows(int32_t n_rows, int32_t n_cols, const int32_t
     if (int rc = read_bad(w, st, &h_bad)) return rc;
     GNNX_REQUIRE(!h_bad, GNNX_ERR_INDEX_RANGE,
                  d_col_pos ? "a column of the listed rows is outside [0, n_cols) or not in the position table's set" : "column id outside [0, n_cols)");
+    return GNNX_OK;
+}
+
+GNNX_API int gnnx_csr_renumber_cols(int64_t nnz, int32_t *d_colidx, const int32_t *d_pos, int64_t n_cols, void *d_workspace, size_t workspace_bytes,
+                                    void *stream)
+{
+    GNNX_REQUIRE(nnz >= 0 && n_cols >= 0, GNNX_ERR_INVALID_ARG, "negative size");
+    GNNX_REQUIRE(nnz < (1ll << 31) && n_cols < (1ll << 31), GNNX_ERR_INVALID_ARG, "nnz and n_cols must be < 2^31 (int32 CSR)");
+    if (nnz == 0) return GNNX_OK;
+    GNNX_REQUIRE(d_colidx && (d_pos || n_cols == 0), GNNX_ERR_INVALID_ARG, "null pointer");
+    GNNX_REQUIRE(d_workspace && workspace_bytes >= 256, GNNX_ERR_WORKSPACE, "workspace %zu < required 256", workspace_bytes);
+    hipStream_t st = as_stream(stream);
+    int32_t *bad = reinterpret_cast<int32_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 3u) & ~(uintptr_t)3u);
+    GNNX_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(renumber_cols_kernel, dim3((uint32_t)ceil_div(nnz, 256)), dim3(256), 0, st, nnz, d_colidx, d_pos, n_cols, bad);
+    GNNX_LAUNCH_CHECK();
+    int32_t h_bad = 0;
+    GNNX_HIP_CHECK(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GNNX_HIP_CHECK(hipStreamSynchronize(st));
+    GNNX_REQUIRE(!h_bad, GNNX_ERR_INDEX_RANGE, "a column is outside [0, n_cols) or has no position in the table (such entries are now -1)");
     return GNNX_OK;
 }

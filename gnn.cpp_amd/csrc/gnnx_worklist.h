@@ -55,8 +55,10 @@ __device__ __forceinline__ int64_t listed(const int32_t *counter, int64_t cap)
 }
 __device__ __forceinline__ int64_t listed_hubs(const HubList &w) { return listed(&w.counters[0], w.cap_hub); }
 
-// one lane per hub row of d > S entries: its slot in the list and its run of segment slots
-__device__ __forceinline__ void append(const HubList &w, int32_t row, int64_t d)
+// one lane per hub row of d > S entries: its slot in the list and its run of segment slots.  Returns whether the hub was listed (always,
+// on a valid CSR whose rows are met once each).  `row` is whatever the unit wants back from hub_rows[]: gnnx_sample.hip lists the
+// position in its row list, which names the output row, and finds the CSR row through the list.
+__device__ __forceinline__ bool append(const HubList &w, int32_t row, int64_t d)
 {
     const int32_t nseg = (int32_t)((d + kSeg - 1) / kSeg);
     const int32_t h = atomicAdd(&w.counters[0], 1);
@@ -67,25 +69,35 @@ __device__ __forceinline__ void append(const HubList &w, int32_t row, int64_t d)
         w.hub_seg0[h] = fits ? s0 : 0;
     }
     for (int64_t s = s0; s < (int64_t)s0 + nseg && s < w.cap_seg; s++) w.seg_hub[s] = fits ? h : -1;
+    return fits;
 }
 
 // body(row, h, s, b, n, slot) for the slots first, first + stride, ... of the list: segment s of hub h, which is `row`, holds the n
 // entries b .. b + n - 1 of the CSR.  The caller's work unit (a wavefront, a lane group) picks `first` and `stride`; every lane of the
 // unit passes the same ones, so the body may shuffle.
+// The overload with `rows` is for a hub list that holds positions in a row list: hub_rows[h] = x is handed to the body as it is, and
+// the CSR row whose entries b .. b + n - 1 are meant is rows[x] (rows == nullptr: x itself).
 template <class Body>
-__device__ __forceinline__ void for_hub_segments(const HubList &w, const int32_t *__restrict__ rowptr, int64_t first, int64_t stride, Body body)
+__device__ __forceinline__ void for_hub_segments(const HubList &w, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ rows, int64_t first,
+                                                 int64_t stride, Body body)
 {
     const int64_t n_slots = listed(&w.counters[1], w.cap_seg);
     for (int64_t slot = first; slot < n_slots; slot += stride) {
         const int32_t h = w.seg_hub[slot];
         if (h < 0) continue;
-        const int32_t row = w.hub_rows[h];
+        const int32_t x = w.hub_rows[h];
+        const int32_t row = rows ? rows[x] : x;
         const int64_t s = slot - w.hub_seg0[h];
         const int64_t row_end = rowptr[row + 1];
         const int64_t b = (int64_t)rowptr[row] + s * kSeg;
         const int64_t e = b + kSeg < row_end ? b + kSeg : row_end;
-        body(row, h, s, b, e - b, slot);
+        body(x, h, s, b, e - b, slot);
     }
+}
+template <class Body>
+__device__ __forceinline__ void for_hub_segments(const HubList &w, const int32_t *__restrict__ rowptr, int64_t first, int64_t stride, Body body)
+{
+    for_hub_segments(w, rowptr, nullptr, first, stride, body);
 }
 
 }  // namespace gnnx

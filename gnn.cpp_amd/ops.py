@@ -269,6 +269,12 @@ class CsrGraph:
         query: 1-D integer tensor of VERTEX ids, any order, repeats allowed."""
         return ReceptiveField(self, query, n_layers)
 
+    def sampled_field(self, seeds, fanouts, seed):
+        """The sampled field of one mini-batch for SageStack.predict / batch_step: a SampledField.  seeds: 1-D integer tensor of VERTEX
+        ids, any order, repeats allowed; fanouts: neighbours kept per layer, first layer first; seed: an int (one per batch or epoch)
+        or one int per layer."""
+        return SampledField(self, seeds, fanouts, seed)
+
 
 class LabelledSet:
     """rows / n_labelled of a train mask, the row-restricted CSR(A) (entries whose row is labelled) and the column-restricted
@@ -420,6 +426,46 @@ def sample_neighbors(rowptr, colidx, k, seed, want_pos=False, want_rowid=False):
     return rowptr_o, shrink(colidx_o), shrink(pos_o), shrink(rowid_o)
 
 
+def sample_rows(rowptr, colidx, rows, k, seed, n_cols=None, want_pos=False, want_rowid=False, col_mark=None):
+    """gnnx_csr_sample_rows: sample_neighbors for a list of rows (int32 ids of the CSR, any order, repeats allowed) -- output row x is
+    row rows[x] of the whole-graph sample of the same (k, seed), at a cost of O(len(rows) + their entries).
+    -> (rowptr' [len(rows) + 1], colidx' (ORIGINAL column ids), pos or None, rowid or None): rowid[q] is the LIST position x of kept entry
+    q.  col_mark: a [n_cols] uint8 device tensor in which byte c is set to 1 for every kept column c (zeroed or preset by the caller).
+    GnnxError (status -3) with nothing written when the list holds an id outside [0, n_rows)."""
+    rows = _row_list(rows)
+    n_rows, nnz, m, dev = int(rowptr.numel() - 1), int(colidx.numel()), int(rows.numel()), rowptr.device
+    n_cols = n_rows if n_cols is None else int(n_cols)
+    k = int(k)
+    if col_mark is not None and (col_mark.dtype != torch.uint8 or int(col_mark.numel()) != n_cols or not col_mark.is_contiguous()):
+        raise capi.GnnxError(-2, "sample_rows", f"col_mark must be a contiguous uint8 vector of {n_cols} entries")
+    ws, _ = _scratch("gnnx_csr_sample_workspace", m, nnz, k, device=dev, tag="sample")   # refuses k < 1 and k > 64 before anything is sized
+    cap = 0
+    if m and n_rows:   # min(deg, k) of the listed rows: exact (an id outside the CSR is clamped here and refused by the call)
+        r = rows.long().clamp(0, n_rows - 1)
+        cap = int((rowptr[r + 1] - rowptr[r]).clamp(max=k).sum())
+    rowptr_o = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    colidx_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    pos_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_pos else None
+    rowid_o = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_rowid else None
+    out_nnz = C.c_int64(0)
+    capi.call("gnnx_csr_sample_rows", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(rows) if m else None, m, k,
+              int(seed) & (2 ** 64 - 1), _ptr(rowptr_o), _ptr(colidx_o), _ptr(pos_o), _ptr(rowid_o), _ptr(col_mark), cap, C.byref(out_nnz),
+              _ptr(ws), ws.numel(), _stream())
+    e = out_nnz.value
+    # (an empty result stays a view of its 1-element buffer, as csr_restrict's: the aggregation wants a device pointer)
+    shrink = lambda t: None if t is None else (t[:e] if e else t[:0])  # noqa: E731
+    return rowptr_o, shrink(colidx_o), shrink(pos_o), shrink(rowid_o)
+
+
+def renumber_cols(colidx, pos):
+    """gnnx_csr_renumber_cols: colidx[q] = pos[colidx[q]] IN PLACE (pos: a position table from rows_to_positions).  GnnxError (status
+    -3) when a column is outside the table or has no position.  Returns colidx."""
+    nnz, n_cols = int(colidx.numel()), int(pos.numel())
+    ws = _workspace(256, colidx.device, "renumber")
+    capi.call("gnnx_csr_renumber_cols", nnz, _ptr(colidx) if nnz else None, _ptr(pos) if n_cols else None, n_cols, _ptr(ws), ws.numel(), _stream())
+    return colidx
+
+
 NEG_EXCLUDE_SELF = 1
 
 
@@ -560,6 +606,91 @@ class ReceptiveField:
                 if big_rows is not None:
                     self.plan[l].set_big_row_threshold(big_rows)
         self.compact_rows = torch.arange(int(self.rows[L].numel()), dtype=torch.int32, device=dev)
+
+
+def _inv_deg(rowptr):
+    """1 / (entries of a row), 0 for an empty row: the division on the host -- IEEE, rounded once."""
+    deg = (rowptr[1:] - rowptr[:-1]).cpu().to(torch.float32)
+    return torch.where(deg > 0, 1.0 / deg, torch.zeros_like(deg)).to(rowptr.device)
+
+
+class SampledField:
+    """The sampled L-layer field of a batch of seed vertices on a CsrGraph -- what one mini-batch GraphSAGE step reads
+    (SageStack.predict / batch_step), at a cost of O(batch * product of the fanouts) plus one O(n) mark and one O(n) position table per
+    layer.  L = len(fanouts); layer l (1 .. L) keeps at most fanouts[l - 1] stored neighbours per row, drawn by sample_rows from the
+    layer's seed.  With Q_L = the seeds' rows and Q_{l-1} = Q_l united with the columns kept for rows Q_l (a layer reads the vertex
+    itself through W_s, so Q_l is a subset of Q_{l-1}):
+      rows[l]      l = 0..L   ascending int32 rows of the graph (row order, nid applied); a row's compact id is its position
+      nnz[l]       l = 1..L   kept entries of the block with rows Q_l (nnz[0] is 0)
+      block[l]     l = 1..L   (rowptr, colidx): row x is row rows[l][x] of g.sample_neighbors(fanouts[l - 1], seeds[l - 1]), entries in
+                              stored order, columns as positions in rows[l - 1]
+      self_pos[l]  l = 1..L   int32 [|Q_l|], the position of rows[l][x] in rows[l - 1]
+      inv_deg[l]   l = 1..L   1 / (entries of block row x), 0 for an empty one
+      block_t[l]   l = 1..L   (rowptr_t, colidx_t) of the transposed block, |Q_{l-1}| rows, built from the COO (column, list position)
+      map_t(l)                csr_transpose_map of block l, built on first use (aggr="max"); GnnxError on a relabelled graph
+      seeds                   the L layer seeds; n_query, query_rows (the seeds' rows in the caller's order), query_pos (their compact
+                              rows in rows[L])
+    seed: an int s gives layer l the seed s * L + (l - 1), so seed=epoch never reuses a layer seed across epochs; or a sequence of L
+    ints.  seeds: a 1-D integer tensor of VERTEX ids, any order; a repeated id counts once in rows[L].  No plans are built: a block row
+    has at most 64 entries."""
+
+    def __init__(self, g, seeds, fanouts, seed):
+        fan = [int(k) for k in fanouts]
+        L = len(fan)
+        if L < 1:
+            raise ValueError("fanouts must name at least one layer")
+        if isinstance(seed, (list, tuple)):
+            if len(seed) != L:
+                raise ValueError(f"{len(seed)} seeds for {L} layers")
+            self.seeds = [int(s) for s in seed]
+        else:
+            self.seeds = [int(seed) * L + l for l in range(L)]
+        q = seeds.reshape(-1)
+        if q.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or seeds.dim() != 1:
+            raise ValueError("seeds must be a 1-D integer tensor of vertex ids")
+        dev = g.rowptr.device
+        q = q.to(dev).long()
+        self.n_query = int(q.numel())
+        if self.n_query and (int(q.min()) < 0 or int(q.max()) >= g.n):
+            raise ValueError(f"seeds hold a vertex id outside [0, {g.n})")
+        r = q if g.nid is None else g.nid[q].long()
+        self.g, self.n, self.n_layers, self.fanouts = g, g.n, L, fan
+        member = torch.zeros(g.n, dtype=torch.uint8, device=dev)
+        member[r] = 1
+        self.rows = [None] * (L + 1)
+        self.rows[L] = rows_from_mask(member)
+        self.query_rows = r.to(torch.int32)
+        self.query_pos = rows_to_positions(self.rows[L], g.n)[r].contiguous()
+        self.nnz, self.block, self.block_t = [0] * (L + 1), [None] * (L + 1), [None] * (L + 1)
+        self.self_pos, self.inv_deg, self._map_t = [None] * (L + 1), [None] * (L + 1), [None] * (L + 1)
+        mark = member   # rows[L] are marked already
+        for l in range(L, 0, -1):
+            rows_l = self.rows[l]
+            rp, ci, _, rowid = sample_rows(g.rowptr, g.colidx, rows_l, fan[l - 1], self.seeds[l - 1], n_cols=g.n, want_rowid=True, col_mark=mark)
+            self.rows[l - 1] = rows_from_mask(mark)
+            pos = rows_to_positions(self.rows[l - 1], g.n)
+            renumber_cols(ci, pos)
+            m_in, e = int(self.rows[l - 1].numel()), int(ci.numel())
+            self.nnz[l], self.block[l] = e, (rp, ci)
+            self.self_pos[l] = pos[rows_l.long()].contiguous()
+            self.inv_deg[l] = _inv_deg(rp)
+            if e:   # the square builder suffices: |Q_l| <= |Q_{l-1}|; self loops and duplicates kept -- exactly the kept entries
+                self.block_t[l] = CsrGraph.csr_from_coo(ci, rowid, m_in, flags=3)
+            else:
+                self.block_t[l] = (torch.zeros(m_in + 1, dtype=torch.int32, device=dev), ci)
+            # (the marks stay: the next layer's rows are marked already, as Q_{l-1} contains Q_l)
+        self.compact_rows = torch.arange(int(self.rows[L].numel()), dtype=torch.int32, device=dev)
+
+    def map_t(self, l):
+        """csr_transpose_map of block l (built once): spmm_reduce's arg reaches the transposed block through it."""
+        if self.g.nid is not None:
+            raise capi.GnnxError(-7, "SampledField.map_t", "a relabelled graph keeps each row in original-id order, not ascending: the "
+                                 "transpose map cannot be built on it (build the graph without relabel)")
+        if self._map_t[l] is None:
+            (rp, ci), (rpt, cit) = self.block[l], self.block_t[l]
+            # (a rectangular pattern: |Q_l| rows against the |Q_{l-1}| rows of its transpose; no entries: nothing to map)
+            self._map_t[l] = csr_transpose_map(rp, ci, rpt, cit) if self.nnz[l] else ci
+        return self._map_t[l]
 
 
 def to_bf16(X, out=None):
@@ -2202,7 +2333,8 @@ class SageStack(_Stack):
     spmm_reduce_bwd through g.attention_map() backward -- which refuses a relabelled graph and one without a transposed CSR, with
     GatStack's GnnxError.  An empty row aggregates to zero: its output is h W_s^T + b.
     forward / backward / step / train_step / evaluate / grad_buffer, and on_graph for steps on a sampled graph; every operation of forward and backward is a C-ABI call (the
-    aggregation, the dense products, the bias add, the ReLU and its mask).  No atomics on any value; the same bits every run."""
+    aggregation, the dense products, the bias add, the ReLU and its mask).  No atomics on any value; the same bits every run.
+    predict / batch_step run on a SampledField (g.sampled_field(seeds, fanouts, seed)): a mini-batch at the cost of its field."""
 
     def __init__(self, g, dims, aggr="mean", seed=0, device="cuda"):
         if aggr not in ("mean", "max"):
@@ -2226,8 +2358,7 @@ class SageStack(_Stack):
         if self.aggr == "max":
             self.map_t = g.attention_map()
         else:
-            deg = (g.rowptr[1:] - g.rowptr[:-1]).cpu().to(torch.float32)      # the division on the host: IEEE, rounded once
-            self.inv_deg = torch.where(deg > 0, 1.0 / deg, torch.zeros_like(deg)).to(g.rowptr.device)
+            self.inv_deg = _inv_deg(g.rowptr)
         return self
 
     def params(self):
@@ -2300,6 +2431,73 @@ class SageStack(_Stack):
             G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l])))           # h = relu output of the layer below
             colsum(G, out=self.db[l - 1])
         return G
+
+    # ---- mini-batch steps on a SampledField: compact matrices of their own, neither _saved nor _buf is touched ----
+    def _field_forward(self, X, field):
+        """[(h, Hs, M, arg, Y)] per layer on the field's compact matrices: h the layer's input on rows[l], Hs = its rows self_pos (the
+        vertices themselves), M / arg the aggregation over block l + 1, Y the output on rows[l + 1].  The operations are forward's,
+        row for row: a block row holds the entries of the sampled graph's row in stored order and every product is row-local."""
+        L = len(self.W_s)
+        if not isinstance(field, SampledField) or field.n_layers != L:
+            raise ValueError(f"the stack has {L} layers, the sampled field was built for {getattr(field, 'n_layers', None)}")
+        if field.n != self.g.n or X.shape[0] != self.g.n or X.shape[1] != self.dims[0]:
+            raise ValueError("X must be the full [n, d0] input of the graph the field was built on")
+        if field.n_query == 0:
+            raise ValueError("the field has no seeds")
+        h = gather_rows(X, field.rows[0])     # the only read of the input: rows Q_0
+        saved = []
+        for l in range(L):
+            (rp, ci), m_out = field.block[l + 1], int(field.rows[l + 1].numel())
+            if self.aggr == "mean":
+                M, arg = spmm(rp, ci, h, rowscale=field.inv_deg[l + 1], n_rows=m_out), None
+            else:
+                M, arg = spmm_reduce(rp, ci, h, op="max")
+            Hs = gather_rows(h, field.self_pos[l + 1])
+            Z = gemm(Hs, self.W_s[l], transB=True)
+            gemm(M, self.W_n[l], transB=True, out=Z, beta=1.0)
+            Y = bias_add(Z, self.b[l], out=Z)
+            if l + 1 < L:
+                bn_relu_fwd(Y, relu=True, out=Y)
+            saved.append((h, Hs, M, arg, Y))
+            h = Y
+        return saved
+
+    def predict(self, X, field):
+        """Logits [len(seeds), C] of a SampledField's seeds, one row per seed in the caller's order, from the field's compact matrices.
+        X: the full [n, d0] input in row order; only rows field.rows[0] are read.  With per-layer seeds [s] * L and fanouts [k] * L the
+        field is the L-hop field of g.sample_neighbors(k, s) and the result is bit for bit on_graph(that graph).forward(X) at the seeds.
+        Buffers of its own: a call between forward and backward leaves the step's results as they are."""
+        return gather_rows(self._field_forward(X, field)[-1][4], field.query_pos)
+
+    def batch_step(self, X, target, field, lr, weight_decay=0.0):
+        """One step of the model's optimiser on a mini-batch: forward on the field, softmax_ce over all compact rows of rows[L] (the
+        batch's unique vertices; db[L-1] from the loss kernel), backward on the blocks into dW_s / dW_n / db, step.  X and target in the
+        graph's ROW order; target is read at rows[L] only.  Returns the loss tensor.  The training surface of mini-batches:
+            for it, batch in enumerate(batches): net.batch_step(X, target, g.sampled_field(batch, [10, 10], seed=it), lr)
+        The gradients are those of the loss on the sampled field, summed over its compact rows -- another split-K sum than a full-graph
+        step's, so no bits are shared with train_step; every run of the same schedule gives the same bits."""
+        L = len(self.W_s)
+        saved = self._field_forward(X, field)
+        t = target.reshape(-1)[field.rows[L].long()].to(torch.int32).contiguous()
+        loss, G = softmax_ce(saved[-1][4], t, colsum_out=self.db[L - 1])
+        for l in reversed(range(L)):
+            h, Hs, M, arg, _ = saved[l]
+            gemm(G, Hs, transA=True, out=self.dW_s[l])
+            gemm(G, M, transA=True, out=self.dW_n[l])
+            if l == 0:
+                break
+            dM = gemm(G, self.W_n[l])
+            dh = torch.zeros_like(h)
+            scatter_add_rows(gemm(G, self.W_s[l]), field.self_pos[l + 1], dh)         # through the vertex itself (self_pos is injective)
+            rpt, cit = field.block_t[l + 1]
+            if self.aggr == "mean":                                                      # + through its sampled neighbourhood
+                spmm(rpt, cit, dM, out=dh, colscale=field.inv_deg[l + 1], beta=1.0)
+            else:
+                spmm_reduce_bwd(rpt, cit, field.map_t(l + 1), arg, dM, out=dh, beta=1.0)
+            G = relu_mask(h, dh)                                                         # h = relu output of the layer below
+            colsum(G, out=self.db[l - 1])
+        self.step(lr, weight_decay)
+        return loss
 
 
 # ---- graph readout: segment pooling, graph batches, a classifier head (include/gnnx.h "graph readout") ----------------------------------

@@ -676,6 +676,13 @@ int gnnx_csr_extract_rows(int32_t n_rows, int32_t n_cols, const int32_t *d_rowpt
                           const int32_t *d_rows, int64_t n_listed, const int32_t *d_col_pos, int32_t *d_rowptr_out,
                           int32_t *d_colidx_out, float *d_vals_out, int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace,
                           size_t workspace_bytes, void *stream);
+/* gnnx_csr_renumber_cols: d_colidx[q] = d_pos[d_colidx[q]] IN PLACE for q in [0, nnz) -- the columns of a block that was made with
+ * original column ids (gnnx_csr_sample_rows) become positions in a row list through its position table (gnnx_rows_to_positions over
+ * [0, n_cols)).  A column outside [0, n_cols), or one whose position is -1, is GNNX_ERR_INDEX_RANGE; such entries are then -1, every
+ * other entry is renumbered: never a wrong index.  The workspace is a fixed 256 bytes at any address (no query, as for
+ * gnnx_csr_sample_negatives); nnz == 0 returns GNNX_OK and touches nothing.  Synchronises `stream`. */
+int gnnx_csr_renumber_cols(int64_t nnz, int32_t *d_colidx, const int32_t *d_pos, int64_t n_cols, void *d_workspace, size_t workspace_bytes,
+                           void *stream);
 
 /* ------------------------------------------------------------------ edge scores (SDDMM) ---------- */
 /*
@@ -1074,6 +1081,36 @@ int gnnx_csr_sample_workspace(int32_t n_rows, int64_t nnz, int32_t k, size_t *by
 int gnnx_csr_sample_neighbors(int32_t n_rows, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, int32_t k, uint64_t seed,
                               int32_t *d_rowptr_out, int32_t *d_colidx_out, int32_t *d_pos_out, int32_t *d_rowid_out,
                               int64_t nnz_capacity, int64_t *nnz_out, void *d_workspace, size_t workspace_bytes, void *stream);
+/*
+ * gnnx_csr_sample_rows: the same sample for a LIST of rows -- the sampler of a mini-batch, whose cost is O(n_listed + entries of the
+ * listed rows) and reads nothing else of the graph.  d_rows [n_listed] holds row ids of the CSR in any order, repeats allowed.
+ * Output row x is, entry for entry, row d_rows[x] of what gnnx_csr_sample_neighbors(..., k, seed) writes for the whole graph: the key
+ * is formed from the CSR's row id i = d_rows[x], never from x, and a repeated row gives the same sample twice.
+ *   d_rowptr_out    n_listed + 1 values, the exclusive scan of min(d_{rows[x]}, k).
+ *   d_colidx_out[q] the ORIGINAL column id of kept entry q (gnnx_csr_renumber_cols makes it a position in a row list).
+ *   d_pos_out[q]    (may be NULL) the absolute position of kept entry q in the input CSR.
+ *   d_rowid_out[q]  (may be NULL) x, the LIST position of kept entry q: (colidx_out, rowid_out) is the COO of the transposed block.
+ *   d_col_mark      (may be NULL) one byte per column, n_cols bytes: byte c is set to 1 for every kept entry of column c and no other
+ *                   byte is written -- the frontier of the sampled block, as gnnx_frontier_mark marks that of the full rows.  The
+ *                   caller zeroes or presets the array; many lanes storing the same 1 is the only race.  (A stored column outside
+ *                   [0, n_cols) is not marked; gnnx_csr_renumber_cols refuses it.)
+ *   *nnz_out        (HOST) = rowptr_out[n_listed], valid on return.
+ * Statuses, capacity, k <= 64 and synchronisation are those of gnnx_csr_sample_neighbors; in addition a negative n_cols or n_listed,
+ * n_listed >= 2^31 and a null d_rows with n_listed > 0 are GNNX_ERR_INVALID_ARG before any device call, and an id of d_rows outside
+ * [0, n_rows) is GNNX_ERR_INDEX_RANGE with nothing written to any output.  n_listed == 0 is a valid result: rowptr_out = [0].
+ *
+ * Workspace: there is no query of its own.  The call carves as the whole-graph call does, with the list's length in the place of the
+ * row count: at least gnnx_csr_sample_workspace(n_listed, nnz, k) bytes, nnz that of the whole CSR.  The range flag is one of the 16
+ * counter words.  The lists of long rows are sized for rows met once each; a list that repeats rows of more than 256 entries more
+ * often than they hold has the surplus rows selected by the row kernel's own lane group: slower, and the same entries.
+ *
+ * Kernels: those of gnnx_csr_sample_neighbors with a row indirection (CSR row = d_rows[x], output row = x; the long-row and hub lists
+ * hold x).  The lane-group width comes from nnz / n_rows of the CSR; the result does not depend on it.
+ */
+int gnnx_csr_sample_rows(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                         const int32_t *d_rows, int64_t n_listed, int32_t k, uint64_t seed, int32_t *d_rowptr_out, int32_t *d_colidx_out,
+                         int32_t *d_pos_out, int32_t *d_rowid_out, uint8_t *d_col_mark, int64_t nnz_capacity, int64_t *nnz_out,
+                         void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ negative sampling, ranking --- */
 /*
