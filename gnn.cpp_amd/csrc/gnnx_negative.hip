@@ -11,22 +11,14 @@
 // Integer work, 64-bit offsets.  Every loop is a binary search or bounded by m; there is no rejection loop and no spin wait.  The one
 // atomic is the counter of unfilled draws.
 #include "gnnx_common.h"
+#include "gnnx_rng.h"
 
 using namespace gnnx;
 
 namespace {
 
 constexpr int kRun = GNNX_NEG_RUN;   // consecutive positives of one wavefront
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 constexpr uint64_t kDomain = 0x6E65676174697665ull;   // "negative": the draw is independent of the neighbour sampler's under one seed
-
-__host__ __device__ inline uint64_t splitmix64(uint64_t x)
-{
-    uint64_t z = x + kGolden;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // the smallest row r of lo .. hi with rowptr[r + 1] > p: the row that stores entry p when it lies in lo .. hi, empty rows skipped
 __device__ __forceinline__ int32_t row_between(const int32_t *rowptr, int32_t lo, int32_t hi, int64_t p)

@@ -25,6 +25,7 @@
 //     formed from the CSR row, every offset, rowid and list entry from x.  The lists of long rows are sized for rows met once each:
 //     a listed row that repeats more often than they hold is selected by the row kernel's own lane group.
 // Integer work only.  Every loop is bounded by a row, segment or candidate length or by the 64 key bits; there is no spin wait.
+#include "gnnx_rng.h"
 #include "gnnx_worklist.h"
 
 using namespace gnnx;
@@ -37,15 +38,6 @@ constexpr int kCounters = 16;      // int32 words in front of the workspace: [0]
                                    // [4] the range flag of a row list
 constexpr int kSegWaves = 8192;    // wavefronts of the long-row, segment and combine kernels (stride over their lists)
 constexpr int kScanTile = 1024;    // rows per block of the scan kernels: 4 per thread
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ inline uint64_t splitmix64(uint64_t x)
-{
-    uint64_t z = x + kGolden;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // u_j of the contract; s = splitmix64(seed)
 __device__ __forceinline__ uint64_t key_of(uint64_t s, uint32_t row, uint32_t j)

@@ -3,20 +3,11 @@
 #include <cmath>
 
 #include "gnnx_common.h"
+#include "gnnx_rng.h"
 
 using namespace gnnx;
 
 namespace {
-
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ inline uint64_t splitmix64(uint64_t x)
-{
-    uint64_t z = x + kGolden;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __global__ __launch_bounds__(256) void rmat_kernel(uint64_t key, int32_t n_nodes, int64_t n_edges, int64_t first_edge,
                                                     int scale, uint32_t ta, uint32_t tb, uint32_t tc, int32_t *src,

@@ -248,6 +248,20 @@ class CsrGraph:
         return sample_negatives(rowptr, m, seed, excluded=(self.rowptr, self.colidx), n_cols=self.n, exclude_self=exclude_self,
                                 nnz=None if colidx is None else int(colidx.numel()))
 
+    def random_walk(self, starts, length, seed, p=1.0, q=1.0, walks_per_start=1):
+        """int32 [len(starts) * walks_per_start, length + 1]: random walks on this graph's forward CSR (random_walk).  starts: rows of
+        this graph (g.nid[v] of vertex ids on a relabelled graph), any order, repeats allowed; walks_per_start repeats the LIST
+        block-wise (walk x starts at starts[x % len(starts)]), each repeat an independent walk.  GnnxError on a relabelled graph when
+        (p, q) != (1, 1), with attention_map's reasoning: its rows are not ascending, and the second-order step searches the previous
+        vertex's row; uniform walks read no order and run on any graph."""
+        if self.nid is not None and (float(p), float(q)) != (1.0, 1.0):
+            raise capi.GnnxError(-7, "random_walk", "a relabelled graph keeps each row in original-id order, not ascending: the "
+                                 "second-order step cannot search it (build the graph without relabel, or walk with p = q = 1)")
+        starts = _row_list(starts)
+        if int(walks_per_start) != 1:
+            starts = starts.repeat(max(int(walks_per_start), 0))
+        return random_walk(self.rowptr, self.colidx, starts, length, seed, p, q)
+
     def mask_in_row_order(self, mask):
         """A vertex-order mask ([n] bool / uint8, vertex v at position v) as uint8 in this graph's row order (vertex v at nid[v])."""
         if int(mask.numel()) != self.n:
@@ -560,6 +574,46 @@ def link_metrics(pos_scores, neg_scores, neg=None, ks=(10, 50, 100)):
     return out
 
 
+def random_walk(rowptr, colidx, starts, length, seed, p=1.0, q=1.0, walk_base=0, out=None):
+    """gnnx_csr_random_walk: one walk of `length` steps from every entry of `starts` (int32 row ids of the square CSR, any order, repeats
+    allowed) -> int32 [n_walks, length + 1], walk-major: column 0 the start, column t + 1 the result of step t; -1 from the step on
+    that left a vertex without neighbours (a start outside the CSR: from column 0 on).  p = q = 1: uniform steps (DeepWalk); otherwise
+    node2vec's second-order steps with return parameter p and in-out parameter q, which need strictly ascending rows.  Walk x draws from
+    (seed, walk_base + x), never from its start: repeated starts walk independently, and slices of a list with walk_base = the slice's
+    offset give the slices of one call.  out: an int32 [n_walks, >= length + 1] row-major tensor or view; columns behind length + 1 are
+    not written.  The same arguments give the same walks on every run; use one seed per epoch."""
+    starts = _row_list(starts)
+    n_rows, nnz, m, L = int(rowptr.numel() - 1), int(colidx.numel()), int(starts.numel()), int(length)
+    if out is None:
+        out = torch.empty((m, max(L, 0) + 1), dtype=torch.int32, device=rowptr.device)
+    elif out.dtype != torch.int32 or out.dim() != 2 or int(out.shape[0]) != m or int(out.shape[1]) < L + 1 or \
+            (int(out.shape[1]) > 1 and out.stride(1) != 1):
+        raise capi.GnnxError(-2, "random_walk", f"out must be a row-major int32 matrix of {m} rows and at least {L + 1} columns")
+    ldw = out.stride(0) if m > 1 else max(int(out.shape[1]), 1)
+    capi.call("gnnx_csr_random_walk", n_rows, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(starts) if m else None, m, int(walk_base), L,
+              float(p), float(q), int(seed) & (2 ** 64 - 1), _ptr(out) if m else None, ldw, _stream())
+    return out[:, :L + 1] if int(out.shape[1]) != L + 1 else out
+
+
+def walk_pairs(walks, window):
+    """The co-occurrence pairs of walks [n_walks, L + 1] within `window` positions -> (src, dst) int32: for every offset o = 1 .. window,
+    every position a = 0 .. L - o and every walk x the pair (walks[x, a], walks[x, a + o]) and, straight behind it, its reverse; pairs
+    with a -1 (an ended walk) are dropped.  ORDER: offset-major, then position, then walk, then (forward, reverse) -- a reference can
+    equal it entry for entry.  Plain slicing, no kernel; repeated pairs and (v, v) stay (EdgeSet.from_walks collapses them)."""
+    L = int(walks.shape[1]) - 1
+    src, dst = [], []
+    for o in range(1, min(int(window), L) + 1):
+        a, b = walks[:, :L + 1 - o].t().reshape(-1), walks[:, o:].t().reshape(-1)      # position-major, then walk
+        keep = (a >= 0) & (b >= 0)
+        a, b = a[keep], b[keep]
+        src.append(torch.stack([a, b], 1).reshape(-1))
+        dst.append(torch.stack([b, a], 1).reshape(-1))
+    if not src:
+        e = torch.empty(0, dtype=torch.int32, device=walks.device)
+        return e, e.clone()
+    return torch.cat(src).to(torch.int32), torch.cat(dst).to(torch.int32)
+
+
 class ReceptiveField:
     """The L-hop receptive field of a query set on a CsrGraph, built once and reusable (a validation mask evaluated every epoch).
     With Q_L = the query's rows and Q_{l-1} = the columns stored in rows Q_l of CSR(A) (no self term: the diagonal is not stored):
@@ -823,7 +877,7 @@ def bce_logits(scores, target, want_grad=True, n_total=None, grad_out=None):
 
 class EdgeSet:
     """Labelled vertex pairs as a sparse pattern: the CSR of the pairs (rowptr, colidx) with the per-entry targets `target`, the
-    transposed pattern (rowptr_t, colidx_t) and map_t (csr_transpose_map) -- what GcnStack.link_scores / link_train_step score, and what
+    transposed pattern (rowptr_t, colidx_t) and map_t (csr_transpose_map) -- what a stack's link_scores / link_train_step score, and what
     sends the score gradient back to both endpoints without atomics."""
 
     def __init__(self, n, rowptr, colidx, target, rowptr_t, colidx_t, map_t):
@@ -865,6 +919,17 @@ class EdgeSet:
         label = torch.cat([torch.zeros(nsrc.numel(), dtype=torch.float32, device=rows.device),
                            torch.ones(rows.numel(), dtype=torch.float32, device=rows.device)])
         return cls.from_pairs(torch.cat([nsrc, rows]), torch.cat([ndst, colidx.to(torch.int32)]), label, g.n)
+
+    @classmethod
+    def from_walks(cls, g, walks, window, m, seed):
+        """The co-occurrence pairs of random walks on g as positives, m negatives per positive off g: the unsupervised objective of
+        DeepWalk / node2vec and of GraphSAGE section 3.2.  The positives pattern is walk_pairs(walks, window) through
+        CsrGraph.csr_from_coo with its default flags -- repeated pairs collapse into one entry, (v, v) is dropped, rows are ascending --
+        and the result is from_graph(g, m, seed, positives=pattern): a negative is never an edge of g nor the row itself, but may be a
+        walk partner that is not an edge, and loses a collision with a positive as from_pairs prescribes.
+        net.link_train_step(X, EdgeSet.from_walks(g, g.random_walk(batch, 5, seed=ep), 2, 1, seed=ep), lr) is one unsupervised epoch."""
+        src, dst = walk_pairs(walks, window)
+        return cls.from_graph(g, m, seed, positives=CsrGraph.csr_from_coo(src, dst, g.n))
 
     def to_transposed(self, vals, out=None):
         """Per-entry values of the pattern in the transposed pattern's order: out[q] = vals[map_t[q]]."""
@@ -1774,12 +1839,14 @@ class _Model:
 class _Stack(_Model):
     """What the three graph stacks share.  A subclass has forward(X) / backward(dOut, input_grad, have_last_bias_grad), the bias
     gradients `db`, and _bind(g): the ONE method that derives everything the class takes from its graph (g itself included) and returns
-    self -- __init__ and every rebinding to another graph call it (SageStack.on_graph, GraphClassifier).
+    self -- __init__ and every rebinding to another graph call it (SageStack.on_graph, GraphClassifier).  On those rest train_step /
+    evaluate and the link-prediction calls (link_scores, link_grad, link_train_step, link_evaluate: an inner-product decoder on the
+    stack's output), the same for every stack.
 
     The top gradient's buffer carries a mark in `_buf`, next to it: the selection object (a row list, a LabelledSet) outside whose rows
     the buffer is known to be zero, which is what softmax_ce_rows needs of it.  masked_grad_buffer zeroes the buffer only when the mark
     names another object; the mark is dropped when the buffer is reallocated and whenever grad_buffer() hands the buffer to a caller,
-    who may write every row (softmax_ce, GraphClassifier.backward, GcnStack.link_grad).  Models that share `_buf` share the mark."""
+    who may write every row (softmax_ce, GraphClassifier.backward, link_grad).  Models that share `_buf` share the mark."""
 
     _ZERO_OUTSIDE = "zero outside"   # the mark's key in _buf; the entry keeps the selection alive, so `is` cannot match a recycled id
 
@@ -1792,10 +1859,12 @@ class _Stack(_Model):
             self._buf.pop(self._ZERO_OUTSIDE, None)
         return G
 
-    def grad_buffer(self):
-        """Where the loss should write dlogits ([n, dims[-1]]): softmax_ce(..., grad_out=net.grad_buffer())."""
+    def grad_buffer(self, n=None):
+        """Where the loss should write dlogits ([n (default: the graph's), dims[-1]]): softmax_ce(..., grad_out=net.grad_buffer()).  On
+        the gather pitch when the model's graph wants it (GcnStack._bind): the top gradient is gathered by the last layer's backward
+        aggregation."""
         self._buf.pop(self._ZERO_OUTSIDE, None)
-        return self._grad()
+        return self._grad(n)
 
     def masked_grad_buffer(self, selection):
         """The gradient buffer, zero everywhere outside the rows softmax_ce_rows writes for `selection`: zeroed when the object is first
@@ -1826,6 +1895,46 @@ class _Stack(_Model):
         """Full forward, then (loss over `rows` as a 1-element tensor, correct predictions among them, len(rows)).  rows: ascending
         int32 rows of the graph (g.rows_of(mask) for a vertex-order validation / test mask)."""
         return _loss_and_accuracy(self.forward(X), target, rows)
+
+    def link_scores(self, X, edges):
+        """Inner-product decoder on the stack's embeddings Z = forward(X): the logit <Z[i], Z[c]> of every pair (i, c) of the EdgeSet, in
+        the order of its pattern (edges.rowptr / edges.colidx) -- sddmm(edges.rowptr, edges.colidx, Z, Z)."""
+        Z = self.forward(X)
+        return sddmm(edges.rowptr, edges.colidx, Z, Z)
+
+    def link_grad(self, Z, edges, ds, out=None):
+        """dZ of sum_p loss_p(<Z[i_p], Z[c_p]>) from ds = dloss/dscores: row i collects ds[p] * Z[c_p] over its own entries (an
+        aggregation on the pattern with vals = ds), then ds[p] * Z[i_p] over the entries that name it as a column (the transposed
+        pattern with the mapped values, beta = 1).  No atomics; the order is the aggregation's own contract, the same bits every run."""
+        if out is None:
+            out = self.grad_buffer(Z.shape[0])
+        spmm(edges.rowptr, edges.colidx, Z, out=out, vals=ds)
+        spmm(edges.rowptr_t, edges.colidx_t, Z, out=out, vals=edges.to_transposed(ds), beta=1.0)
+        return out
+
+    def link_train_step(self, X, edges, lr, weight_decay=0.0):
+        """One link-prediction step of the model's optimiser (plain SGD by default): forward -> pair scores (sddmm) -> bce_logits
+        against edges.target -> dZ (link_grad, into grad_buffer()) -> backward without an input gradient -> step.  X in the graph's
+        ROW order.  Returns the loss tensor."""
+        Z = self.forward(X)
+        scores = sddmm(edges.rowptr, edges.colidx, Z, Z)
+        loss, ds = bce_logits(scores, edges.target)
+        dZ = self.link_grad(Z, edges, ds)
+        self.backward(dZ, input_grad=False)
+        self.step(lr, weight_decay)
+        return loss
+
+    def link_evaluate(self, X, g, positives, m, seed, ks=(10, 50, 100)):
+        """link_metrics of held-out edges: every positive (an EdgeSet or a (rowptr, colidx) pair on g's rows) against m negatives drawn
+        by g.sample_negatives(m, seed, positives).  Z = forward(X); the positive scores are sddmm on the positives' pattern, the
+        negative scores sddmm on (rowptr * m, neg): the entry-major layout makes a row's draws one contiguous row of that pattern, so
+        the scores carry sddmm's bit contract.  An unfilled draw (-1) is scored at column 0 and skipped by the rank counts."""
+        rowptr, colidx = _pattern_of(positives, "link_evaluate")
+        neg, _ = g.sample_negatives(m, seed, (rowptr, colidx))
+        Z = self.forward(X)
+        pos_scores = sddmm(rowptr, colidx, Z, Z)
+        neg_scores = sddmm(rowptr * int(m), neg.reshape(-1).clamp(min=0), Z, Z)
+        return link_metrics(pos_scores, neg_scores.reshape(-1, int(m)), neg, ks)
 
 
 class GcnStack(_Stack):
@@ -1878,12 +1987,6 @@ class GcnStack(_Stack):
 
     def grads(self):
         return self.dWp + self.db
-
-    def grad_buffer(self, n=None):
-        """_Stack.grad_buffer for n rows (default: the graph's), on the gather pitch when the graph wants it: the top gradient is
-        gathered by the last layer's backward aggregation."""
-        self._buf.pop(self._ZERO_OUTSIDE, None)
-        return self._grad(n)
 
     def _selected(self, labelled):
         return labelled.rows, {"labelled": labelled}
@@ -1968,46 +2071,6 @@ class GcnStack(_Stack):
                 G, _, _ = bn_relu_bwd(hl, hl, G, relu=True)
                 colsum(G, out=self.db[l - 1])
         return G
-
-    def link_scores(self, X, edges):
-        """Inner-product decoder on the stack's embeddings Z = forward(X): the logit <Z[i], Z[c]> of every pair (i, c) of the EdgeSet, in
-        the order of its pattern (edges.rowptr / edges.colidx) -- sddmm(edges.rowptr, edges.colidx, Z, Z)."""
-        Z = self.forward(X)
-        return sddmm(edges.rowptr, edges.colidx, Z, Z)
-
-    def link_grad(self, Z, edges, ds, out=None):
-        """dZ of sum_p loss_p(<Z[i_p], Z[c_p]>) from ds = dloss/dscores: row i collects ds[p] * Z[c_p] over its own entries (an
-        aggregation on the pattern with vals = ds), then ds[p] * Z[i_p] over the entries that name it as a column (the transposed
-        pattern with the mapped values, beta = 1).  No atomics; the order is the aggregation's own contract, the same bits every run."""
-        if out is None:
-            out = self.grad_buffer(Z.shape[0])
-        spmm(edges.rowptr, edges.colidx, Z, out=out, vals=ds)
-        spmm(edges.rowptr_t, edges.colidx_t, Z, out=out, vals=edges.to_transposed(ds), beta=1.0)
-        return out
-
-    def link_train_step(self, X, edges, lr, weight_decay=0.0):
-        """One link-prediction step of the model's optimiser (plain SGD by default): forward -> pair scores (sddmm) -> bce_logits
-        against edges.target -> dZ (link_grad, into grad_buffer()) -> backward without an input gradient -> step.  X in the graph's
-        ROW order.  Returns the loss tensor."""
-        Z = self.forward(X)
-        scores = sddmm(edges.rowptr, edges.colidx, Z, Z)
-        loss, ds = bce_logits(scores, edges.target)
-        dZ = self.link_grad(Z, edges, ds)
-        self.backward(dZ, input_grad=False)
-        self.step(lr, weight_decay)
-        return loss
-
-    def link_evaluate(self, X, g, positives, m, seed, ks=(10, 50, 100)):
-        """link_metrics of held-out edges: every positive (an EdgeSet or a (rowptr, colidx) pair on g's rows) against m negatives drawn
-        by g.sample_negatives(m, seed, positives).  Z = forward(X); the positive scores are sddmm on the positives' pattern, the
-        negative scores sddmm on (rowptr * m, neg): the entry-major layout makes a row's draws one contiguous row of that pattern, so
-        the scores carry sddmm's bit contract.  An unfilled draw (-1) is scored at column 0 and skipped by the rank counts."""
-        rowptr, colidx = _pattern_of(positives, "link_evaluate")
-        neg, _ = g.sample_negatives(m, seed, (rowptr, colidx))
-        Z = self.forward(X)
-        pos_scores = sddmm(rowptr, colidx, Z, Z)
-        neg_scores = sddmm(rowptr * int(m), neg.reshape(-1).clamp(min=0), Z, Z)
-        return link_metrics(pos_scores, neg_scores.reshape(-1, int(m)), neg, ks)
 
     def _field_logits(self, X, field):
         """[len(field.rows[L]), C] logits of the field's unique query rows (compact row k = graph row field.rows[L][k]), each layer a

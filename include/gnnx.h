@@ -1173,6 +1173,70 @@ int gnnx_csr_sample_negatives(int32_t n_rows, int32_t n_cols, int64_t nnz_pos, c
 int gnnx_rank_counts_f32(int64_t n_pos, int32_t m, const float *d_pos_scores, const float *d_neg_scores, const int32_t *d_neg,
                          int32_t *d_greater, int32_t *d_equal, int32_t *d_valid, void *stream);
 
+/* ------------------------------------------------------------------ random walks ---------------- */
+/*
+ * Seeded random walks on a CSR: uniform (DeepWalk, Perozzi et al. 2014) and second-order (node2vec, Grover & Leskovec 2016) -- the
+ * sampler of the unsupervised objectives (co-occurrence pairs within a window; the loss of GraphSAGE section 3.2).  The contract is this
+ * comment, restated with Python integers and plain loops by tests/walk_ref.py.
+ *
+ * gnnx_csr_random_walk.  The CSR (d_rowptr, d_colidx; n_rows rows, nnz entries) is SQUARE: its columns index its rows.  d_starts
+ * [n_walks] holds the start vertices, any order, repeats allowed.  d_walks is walk-major: row x (ldw >= walk_length + 1 elements; all
+ * offsets are 64-bit) holds the walk_length + 1 vertices of walk x and nothing behind them is written.  Position 0 is d_starts[x], or
+ * -1 when that is outside [0, n_rows); position t + 1 is the result of step t, t = 0 .. walk_length - 1.
+ *
+ * Random numbers.  fin = splitmix64, the finaliser of the other samplers; G = 0x9E3779B97F4A7C15; products wrap in 64 bits.
+ *   s          = fin(seed ^ 0x77616C6B73746570)       "walkstep", a domain constant: independent of the neighbour and the negative
+ *                                                     sampler's draws under the same seed
+ *   w          = walk_base + x                        the GLOBAL walk number
+ *   h(w, t, a) = fin( fin( s ^ (((uint64)w << 32 | (uint64)t) * G) ) ^ ((uint64)a * G) )
+ * The key holds w, never the start vertex: repeated starts give independent walks, and a list walked in slices, walk_base set to each
+ * slice's offset, gives the slices of one call.
+ *
+ * Ending.  A step from the current vertex v with d = rowptr[v+1] - rowptr[v]: if v < 0, v >= n_rows or d == 0 the walk has ended and
+ * the step's result and every later position are -1 (-1 is absorbing).  So a start outside [0, n_rows) gives a row of -1 from position 0
+ * on, a start without neighbours the start followed by -1.  No access is out of range.
+ *
+ * Uniform step -- step 0 of every walk, and every step when p == 1 && q == 1:
+ *   r = floor(h(w, t, 0) * d / 2^64)  (the high 64 bits of the product),   next = colidx[rowptr[v] + r].
+ *
+ * node2vec step -- otherwise (t >= 1, previous vertex u).  Rows must be STRICTLY ASCENDING, as gnnx_csr_from_coo builds them.  A
+ * candidate x of row v belongs to one of three classes with the weights of the paper, turned into integer thresholds on the HOST from
+ * doubles:
+ *   wa = 1 / p  (x == u)      wb = 1  (x != u and x stored in row u: ONE binary search)      wc = 1 / q  (otherwise)
+ *   M = max(wa, wb, wc)       thr_k = min(2^32, (uint64)floor(w_k / M * 4294967296.0))        the largest class gets exactly 2^32
+ * Rejection (KnightKing, Yang et al. 2019), attempts a = 0 .. GNNX_WALK_TRIES - 1:
+ *   x = colidx[rowptr[v] + floor(h(w, t, 2a) * d / 2^64)],   accepted iff (h(w, t, 2a + 1) >> 32) < thr_class(x);
+ * the first accepted candidate is the step.  If none is accepted, the exact fallback -- bounded, no spin:
+ *   W = sum over the row's entries j of thr_class(colidx_j), in uint64;
+ *   W == 0: the uniform formula with a = 2 * GNNX_WALK_TRIES;
+ *   else r = floor(h(w, t, 2 * GNNX_WALK_TRIES) * W / 2^64) and the step is the first entry whose prefix sum of thresholds exceeds r.
+ * Both samplers draw from the node2vec distribution up to the 2^-32 quantum of the thresholds, so the trade between them is cost alone.
+ * The result is a function of (seed, w, start, graph, p, q) alone, however walks map to lanes.  With p = q = 1 every threshold is 2^32,
+ * attempt 0 always accepts and its candidate is the uniform step's: the same bits.
+ *
+ * Cost.  A uniform step is three dependent loads.  An attempt adds a search of O(log d_u) loads unless wb == wc (q == 1: skipped, the
+ * result cannot depend on it).  With min(w) / max(w) >= 1/4 (p, q in [0.5, 2]) a step reaches the fallback with probability
+ * <= 0.75^64 ~ 1e-8; at p = 0.25, q = 4 on a sparse graph (most candidates at weight 1/16) it is about (15/16)^64 ~ 1.6 % of the steps,
+ * and each such step costs O(d log d_u): the wavefront of the walk stops and scans the row together, 64 entries per pass, one pending
+ * walk at a time -- on a power-law graph these steps, not the attempts, set the time.  Results stay exact;
+ * scripts/bench_walks.py reports the rate.
+ *
+ * Statuses.  GNNX_ERR_INVALID_ARG before any device call: negative sizes, walk_length < 0, ldw < walk_length + 1, walk_base < 0 or
+ * walk_base + n_walks > 2^32, nnz >= 2^31, p or q not finite or <= 0 (or so small that the reciprocal is not finite), a null rowptr, a
+ * null starts or walks with n_walks > 0, a null colidx with nnz > 0.  n_walks == 0 is a valid empty result with no launch;
+ * walk_length == 0 copies the starts (those outside [0, n_rows) become -1).  The CSR and nnz (= rowptr[n_rows]) are TRUSTED, as
+ * everywhere else.  Asynchronous on `stream`; no workspace, no atomics: the same bits on every run.
+ *
+ * Kernel (gnnx_walk.hip): one lane per walk, one wavefront per 64 consecutive walks, a grid-stride loop over the walk blocks.  The
+ * wavefront stages GNNX_WALK_CHUNK positions of its 64 walks in LDS and stores each walk's piece with adjacent lanes on adjacent words.
+ * The attempts run lane by lane; the fallback scans of a step run after them, by all 64 lanes on one walk's row at a time.
+ */
+#define GNNX_WALK_TRIES 64
+#define GNNX_WALK_CHUNK 16
+int gnnx_csr_random_walk(int32_t n_rows, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_starts,
+                         int64_t n_walks, int64_t walk_base, int32_t walk_length, double p, double q, uint64_t seed, int32_t *d_walks,
+                         int64_t ldw, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */
