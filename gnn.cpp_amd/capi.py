@@ -191,6 +191,7 @@ _SIGS = {
     "gnnx_csr_sample_negatives": [_i32, _i32, _i64, _vp, _i64, _vp, _vp, _i32, _u64, _u32, _vp, C.POINTER(_i64), _vp, _sz, _vp],
     "gnnx_rank_counts_f32": [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gnnx_csr_random_walk": [_i32, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _u64, _vp, _i64, _vp],
+    "gnnx_knn_f32": [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _u32, _vp, _i64, _vp, _i64, _vp],
     "gnnx_comm_unique_id": [_vp],
     "gnnx_comm_init": [C.POINTER(_vp), C.c_int, C.c_int, _vp],
     "gnnx_comm_init_local": [C.POINTER(_vp), C.c_int],

@@ -2563,6 +2563,106 @@ class SageStack(_Stack):
         return loss
 
 
+class EdgeConvStack(_Stack):
+    """L EdgeConv layers (Wang et al. 2019, DGCNN) with the surface of SageStack.  The paper's layer is
+        h'_i = max_j ReLU( Theta (h_j - h_i) + Phi h_i )          over the neighbours j of i.
+    ReLU is monotone and Phi h_i - Theta h_i does not depend on j, so this equals ReLU( (Phi - Theta) h_i + max_j Theta h_j ): the stack
+    holds W_s = Phi - Theta and W_n = Theta, and the transform runs once per VERTEX, not once per edge:
+        T = h W_n^T;   M, arg = spmm_reduce(g_l, T, "max")  (an empty row gives 0);   Y = h W_s^T + M + b,
+    ReLU between layers, none after the last.  Backward per layer: db = colsum(dY), dW_s = dY^T h, dh = dY W_s,
+    dT = spmm_reduce_bwd(g_l^T, map_t, arg, dY), dW_n = dT^T h, dh += dT W_n.
+    k=None: every layer runs on the bound graph (its attention_map() must build: no relabelling, a transposed CSR).  An integer k
+    (1 .. 64): the graph of layer l is rebuilt from that layer's INPUT, knn_graph(h, k, g.graph_ptr, loop=False) -- the bound graph
+    only says which rows belong together (GraphBatch.of_points) -- and the graphs of the last forward are kept in net.graphs.  No
+    gradient flows through the selection, as in DGCNN.
+    forward / backward / step / train_step / evaluate / grad_buffer / on_graph, and use under GraphClassifier / on_batch.  Every
+    operation is a C-ABI call; no atomics on any value; the same bits every run."""
+
+    def __init__(self, g, dims, k=None, seed=0, device="cuda"):
+        if k is not None and not 1 <= int(k) <= KNN_MAX_K:
+            raise ValueError(f"k must be None or 1 .. {KNN_MAX_K}, got {k!r}")
+        self.dims, self.k = list(dims), None if k is None else int(k)
+        L = len(dims) - 1
+        self.graphs = None
+        self._bind(g)
+        self.W_s = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.W_n = [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
+        self.dW_s = [torch.zeros_like(w) for w in self.W_s]
+        self.dW_n = [torch.zeros_like(w) for w in self.W_n]
+        self.db = [torch.zeros_like(b) for b in self.b]
+        self._saved = None
+        self._buf = {}
+        self._opt = [None]
+
+    def _bind(self, g):
+        """What the stack holds of the graph itself: the transpose map of a fixed graph; of a dynamic one only the row ownership."""
+        self.g = g
+        self.graphs = None
+        self.map_t = g.attention_map() if self.k is None else None
+        return self
+
+    def params(self):
+        return self.W_s + self.W_n + self.b
+
+    def grads(self):
+        return self.dW_s + self.dW_n + self.db
+
+    def on_graph(self, g):
+        """This stack on another graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch buffers."""
+        if g.n != self.g.n:
+            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
+        return self._view(share_buf=True)._bind(g)
+
+    def _layer_graph(self, h):
+        if self.k is None:
+            return self.g
+        return knn_graph(h, self.k, getattr(self.g, "graph_ptr", None), loop=False, transpose=True, norm=False)
+
+    def forward(self, X):
+        L, n = len(self.W_s), self.g.n
+        saved, graphs, h = [], [], X
+        for l in range(L):
+            gl = self._layer_graph(h)
+            T = gemm(h, self.W_n[l], transB=True, out=self._tmp(("T", l), (n, self.dims[l + 1])))
+            M, arg = spmm_reduce(gl.rowptr, gl.colidx, T, op="max", out=self._tmp(("M", l), (n, self.dims[l + 1])),
+                                 arg_out=self._tmp(("arg", l), (n, self.dims[l + 1]), torch.int32))
+            Z = gemm(h, self.W_s[l], transB=True, out=self._tmp(("Z", l), (n, self.dims[l + 1])))
+            axpy(1.0, M, Z)
+            Y = bias_add(Z, self.b[l], out=self._tmp(("Y", l), (n, self.dims[l + 1])))
+            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
+                bn_relu_fwd(Y, relu=True, out=Y)
+            saved.append((h, M, arg, Y))
+            graphs.append(gl)
+            h = Y
+        self._saved, self.graphs = saved, graphs
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """dW_s, dW_n and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        L, n = len(self.W_s), self.g.n
+        G = dOut
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            h, _, arg, _ = self._saved[l]
+            gl = self.graphs[l]
+            map_t = self.map_t if self.k is None else gl.attention_map()
+            gemm(G, h, transA=True, out=self.dW_s[l])
+            dT = spmm_reduce_bwd(gl.rowptr_t, gl.colidx_t, map_t, arg, G, out=self._tmp(("dT", l), (n, self.dims[l + 1])))
+            gemm(dT, h, transA=True, out=self.dW_n[l])
+            if l == 0 and not input_grad:
+                return None
+            dh = gemm(G, self.W_s[l], out=self._tmp(("dh", l), (n, self.dims[l])))     # through the vertex itself
+            gemm(dT, self.W_n[l], out=dh, beta=1.0)                                    # + through its neighbourhood
+            if l == 0:
+                return dh
+            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l])))           # h = relu output of the layer below
+            colsum(G, out=self.db[l - 1])
+        return G
+
+
 # ---- graph readout: segment pooling, graph batches, a classifier head (include/gnnx.h "graph readout") ----------------------------------
 POOL_OPS = {"sum": 0, "mean": 1, "max": 2}   # GNNX_POOL_SUM / GNNX_POOL_MEAN / GNNX_POOL_MAX
 POOL_CHUNK = 256                             # GNNX_POOL_CHUNK
@@ -2637,6 +2737,80 @@ def segment_pool_bwd(segptr, G, op, arg=None, out=None, beta=0.0, n_rows=None):
     return out
 
 
+# ---- nearest neighbours (include/gnnx.h "nearest neighbours") ----------------------------------------------------------------------------
+KNN_MAX_K = 64                                # GNNX_KNN_MAX_K
+KNN_EXCLUDE_SELF, KNN_NEAREST_FIRST = 1, 2    # GNNX_KNN_EXCLUDE_SELF / GNNX_KNN_NEAREST_FIRST
+
+
+def _row_pitch(t):
+    """Row stride of a 2-D matrix for the C-ABI; a matrix of at most one row has none worth the name."""
+    return t.stride(0) if int(t.shape[0]) > 1 else max(int(t.shape[1]), 1)
+
+
+def knn(X, k, Q=None, segptr=None, qsegptr=None, exclude_self=False, nearest_first=False, want_dist=True):
+    """gnnx_knn_f32: (idx int32 [m, k], dist float32 [m, k] or None).  Row i of idx holds the rows of X nearest to query i -- a row of Q,
+    or of X itself without Q -- among the candidates of its own segment (segptr / qsegptr: int32 [n_seg + 1], e.g. a GraphBatch's
+    graph_ptr; neither: one segment), by squared Euclidean distance with ties to the smaller row and NaN last; -1 (dist: +inf) where
+    the segment has fewer than k candidates.  exclude_self drops the candidate with the query's own row number (meant for Q=None).
+    The kept entries stand in ascending ROW order (a strictly ascending CSR row), with nearest_first in ascending distance order.
+    X and Q may be strided views.  The result is a function of the inputs alone, bit for bit."""
+    k = int(k)
+    n, F = _pool_matrix(X, None, torch.float32, "X", "knn").shape
+    m = n if Q is None else int(_pool_matrix(Q, None, torch.float32, "Q", "knn").shape[0])
+    if Q is not None and int(Q.shape[1]) != F:
+        raise capi.GnnxError(-2, "knn", f"Q has {int(Q.shape[1])} columns, X has {F}")
+    n_seg = 1 if segptr is None else _pool_sizes(segptr, "knn")
+    if Q is not None and (segptr is None) != (qsegptr is None):
+        raise capi.GnnxError(-2, "knn", "segptr and qsegptr come together")
+    if Q is not None and qsegptr is not None and _pool_sizes(qsegptr, "knn") != n_seg:
+        raise capi.GnnxError(-2, "knn", f"qsegptr must have {n_seg + 1} entries like segptr")
+    idx = torch.empty((m, max(k, 0)), dtype=torch.int32, device=X.device)
+    dist = torch.empty((m, max(k, 0)), dtype=torch.float32, device=X.device) if want_dist else None
+    if Q is not None and m == 0:
+        return idx, dist
+    flags = (KNN_EXCLUDE_SELF if exclude_self else 0) | (KNN_NEAREST_FIRST if nearest_first else 0)
+    capi.call("gnnx_knn_f32", n, m, F, n_seg, _ptr(X) if n else None, _row_pitch(X), _ptr(segptr), _ptr(Q), 0 if Q is None else _row_pitch(Q),
+              _ptr(qsegptr) if Q is not None else None, k, flags, _ptr(idx) if m else None, max(k, 1), _ptr(dist) if m else None, max(k, 1),
+              _stream())
+    return idx, dist
+
+
+def knn_graph(X, k, graph_ptr=None, loop=False, transpose=True, norm=True):
+    """The k-nearest-neighbour graph of the rows of X (knn with exclude_self = not loop): row i stores its k nearest rows, ascending, so
+    messages flow from neighbour to vertex (SageStack's convention).  graph_ptr (int32 [B + 1]): X holds B clouds, cloud b the rows
+    graph_ptr[b] .. graph_ptr[b + 1] - 1, no edge joins two clouds and the result is a GraphBatch; without it a CsrGraph.  A cloud of
+    k points or fewer gives short rows, a cloud of one point an empty row.  The CSR is the flattened idx (short rows masked out); the
+    transposed CSR is built from the COO (column, row) with self loops and duplicates kept -- exactly the transposed entries.  Plans
+    are not made."""
+    n, dev = int(X.shape[0]), X.device
+    if graph_ptr is not None:
+        graph_ptr = torch.as_tensor(graph_ptr).to(device=dev, dtype=torch.int32).contiguous()
+    idx, _ = knn(X, k, segptr=graph_ptr, exclude_self=not loop, want_dist=False)
+    k = int(k)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    if n == 0 or int(idx[:, k - 1].min()) >= 0:        # no row is short
+        rowptr = torch.arange(n + 1, dtype=torch.int32, device=dev) * k
+        colidx, rowid = idx.reshape(-1), rows.repeat_interleave(k)
+    else:
+        keep = idx >= 0
+        rowptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        rowptr[1:] = torch.cumsum(keep.sum(1), 0).to(torch.int32)
+        colidx, rowid = idx[keep].contiguous(), rows.repeat_interleave(keep.sum(1))
+    if graph_ptr is None:
+        g = CsrGraph(n, rowptr, colidx)
+    else:
+        g = GraphBatch(n, rowptr, colidx)
+        g.graph_ptr, g.n_graphs = graph_ptr, int(graph_ptr.numel()) - 1
+    if transpose:
+        if g.nnz:
+            g.rowptr_t, g.colidx_t = CsrGraph.csr_from_coo(colidx, rowid, n, flags=3)   # keep self loops and duplicates
+        else:
+            g.rowptr_t, g.colidx_t = torch.zeros_like(rowptr), colidx.clone()
+    if norm:
+        g.compute_norm()
+    return g
+
+
 class GraphBatch(CsrGraph):
     """A batch of B small graphs as ONE block-diagonal CsrGraph that every stack takes unchanged: graph k owns the consecutive vertices
     graph_ptr[k] .. graph_ptr[k+1] - 1 and no edge joins two graphs.  graph_ptr: device int32 [B + 1] (segment_pool's segptr); n_graphs;
@@ -2693,6 +2867,25 @@ class GraphBatch(CsrGraph):
         g = cls.from_coo(src, dst, n, transpose=transpose, norm=norm, relabel=None)
         g.graph_ptr = graph_ptr.contiguous()
         g.n_graphs = int(graph_ptr.numel()) - 1
+        return g
+
+    @classmethod
+    def of_points(cls, graph_ptr, device=None):
+        """An EDGELESS batch whose rows are owned as graph_ptr says: what a stack that builds its own graphs (EdgeConvStack with k) and
+        GraphClassifier bind to when the data is B point clouds.  Both CSRs are empty; s / norm are not made."""
+        ptr = torch.as_tensor(graph_ptr)
+        dev = device if device is not None else (ptr.device if ptr.is_cuda else "cuda")
+        host = ptr.to(torch.int64).cpu().reshape(-1)
+        if host.numel() < 2 or int(host[0]) != 0 or bool((host[1:] < host[:-1]).any()):
+            raise ValueError("graph_ptr must be non-decreasing from 0, with one entry more than there are graphs")
+        n = int(host[-1])
+        if n >= 2 ** 31:
+            raise ValueError("the batch does not fit int32 vertex ids")
+        rowptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        colidx = torch.empty(0, dtype=torch.int32, device=dev)
+        g = cls(n, rowptr, colidx, rowptr.clone(), colidx.clone())
+        g.graph_ptr = host.to(torch.int32).to(dev).contiguous()
+        g.n_graphs = int(host.numel()) - 1
         return g
 
     @property

@@ -1237,6 +1237,66 @@ int gnnx_csr_random_walk(int32_t n_rows, int64_t nnz, const int32_t *d_rowptr, c
                          int64_t n_walks, int64_t walk_base, int32_t walk_length, double p, double q, uint64_t seed, int32_t *d_walks,
                          int64_t ldw, void *stream);
 
+/* ------------------------------------------------------------------ nearest neighbours ---------- */
+/*
+ * The k nearest neighbours of every query among the candidates of its segment, by exact all-pairs squared Euclidean distances -- the
+ * edges of data that arrives as coordinates or features (point clouds; the per-layer graphs of DGCNN, Wang et al. 2019).  The contract is
+ * this comment, restated with NumPy float32 steps and Python integer keys by tests/knn_ref.py.
+ *
+ * gnnx_knn_f32.  Candidates d_X [n, ldx], n_feat used columns.  Queries d_Q [m, ldq]; d_Q == NULL: the queries are the candidates
+ * (m == n required, ldq and d_qsegptr ignored).  d_segptr [n_seg + 1] splits the candidates into consecutive groups (the graph_ptr of
+ * a graph batch), d_qsegptr [n_seg + 1] the queries; a query of segment b sees the candidates of segment b only.  Both NULL with
+ * n_seg == 1: one segment that covers everything.  The arrays are TRUSTED to be non-decreasing from 0 to n (m), like every CSR here.
+ *
+ * Distance.  Every operation rounded once to float32, ascending feature order, no fused multiply-add (the unit switches contraction
+ * off itself, whatever the build's flags):
+ *   acc = +0;   for f = 0 .. n_feat - 1:   t = q[f] - c[f];   p = t * t;   acc = acc + p
+ * The chain cannot give a negative value or -0.
+ *
+ * Order.  ukey(d) = 0xFFFFFFFF for a NaN d, else the bit pattern of d;  key(d, c) = (uint64)ukey(d) << 32 | c  with c the candidate's
+ * GLOBAL row.  A query keeps the L = min(k, the candidates of its segment -- one fewer with GNNX_KNN_EXCLUDE_SELF when the query's own
+ * index lies in the candidate segment) candidates with the smallest keys: a total order, equal distances go to the smaller index, NaN
+ * distances come last.  GNNX_KNN_EXCLUDE_SELF drops the candidate whose row equals the query's row; it is meant for d_Q == NULL
+ * (pointer identity is not checked).
+ *
+ * Output.  Row i of d_idx (ldi >= k) holds the L kept rows at positions 0 .. L - 1 and -1 behind them up to k - 1; row i of d_dist
+ * (optional, ldd >= k) their distances -- the bits of acc, a NaN as 0x7FC00000 -- and +inf behind them.  Nothing behind position k - 1
+ * is written.  The kept entries stand in ASCENDING INDEX order (flattened: a strictly ascending CSR row, what csr_transpose_map and the
+ * node2vec step need); with GNNX_KNN_NEAREST_FIRST in ascending key order.  The result is a function of the inputs alone, bit for bit.
+ *
+ * Statuses.  GNNX_ERR_INVALID_ARG before any device call: negative n or m, n_feat < 1, k < 1 or k > GNNX_KNN_MAX_K, n_seg < 1, unknown
+ * flag bits, ldx < n_feat, ldq < n_feat (d_Q given), ldi < k, ldd < k (d_dist given), exactly one segment array NULL while d_Q is given,
+ * NULL segment arrays with n_seg != 1, d_Q == NULL with m != n, a NULL d_X with n > 0, a NULL d_idx with m > 0.  m == 0 is a valid
+ * empty result with no launch; n == 0 (or an empty segment) fills the rows with -1 / +inf.  Asynchronous on `stream`; no workspace, no
+ * atomics.
+ *
+ * Kernel and dispatch (gnnx_knn.hip) -- a function of the call's arguments alone:
+ *   form   n_feat <= GNNX_KNN_REG_FEAT: the query row in NF registers, NF the smallest of {2, 3, 4, 8, 16, 32, 64} >= n_feat, candidate
+ *          tiles of GNNX_KNN_TILE rows in LDS.  Beyond: the LDS form, tiles of GNNX_KNN_TILE_LDS rows, 64 features of the tile and of
+ *          the queries staged at a time.
+ *   group  G lanes per query, each taking every G-th row of a tile, their lists merged at the end:
+ *            G = min(Gm, Gs, Gw)   Gm = the smallest power of two <= 64 with m * Gm >= GNNX_KNN_FULL_LANES (four wavefronts per SIMD)
+ *                                  Gs = the largest power of two <= 64 with Gs * 2k <= n / n_seg (integer division), at least 1
+ *                                  Gw = the largest power of two <= 64 with Gw * NF <= GNNX_KNN_GROUP_FLOATS (NF = 64 in the LDS form)
+ *          Gw is a measured bound: only G = 1 reads a tile row as a broadcast, and rows of 64 features are bound by those reads
+ *          (G = 2 is the best there, G = 8 slower than G = 1; at n_feat = 3 the best G is Gm's: DESIGN.md section 5.12).
+ *   LDS    k * 512 bytes of lists (64 lanes, k keys of 8 bytes) + the tile: (NF + 4) * 256 bytes (NF * 256 below NF = 4), or 21 kB
+ *          in the LDS form -- at most 52.5 KiB, checked against the device at the first launch.
+ * One wavefront per workgroup and 64 / G consecutive queries; queries of one workgroup in different segments are served one segment
+ * after the other.  Numbers: DESIGN.md section 5.12, scripts/bench_knn.py.
+ */
+#define GNNX_KNN_MAX_K 64
+#define GNNX_KNN_EXCLUDE_SELF 1u
+#define GNNX_KNN_NEAREST_FIRST 2u
+#define GNNX_KNN_REG_FEAT 64
+#define GNNX_KNN_TILE 64
+#define GNNX_KNN_TILE_LDS 16
+#define GNNX_KNN_FULL_LANES 262144
+#define GNNX_KNN_GROUP_FLOATS 128
+int gnnx_knn_f32(int32_t n, int32_t m, int32_t n_feat, int32_t n_seg, const float *d_X, int64_t ldx, const int32_t *d_segptr,
+                 const float *d_Q, int64_t ldq, const int32_t *d_qsegptr, int32_t k, uint32_t flags, int32_t *d_idx, int64_t ldi,
+                 float *d_dist, int64_t ldd, void *stream);
+
 /* ------------------------------------------------------------------ halo (multi-GPU) ------------- */
 /* Pack rows for the all-to-all-v send buffer: out[k,:] = X[idx[k],:]; and the reverse for backward:
  * Y[idx[k],:] += in[k,:] (idx may repeat across calls but NOT within one call => no atomics, deterministic). */
