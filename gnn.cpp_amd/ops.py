@@ -215,6 +215,32 @@ class CsrGraph:
             self._map_t = csr_transpose_map(self.rowptr, self.colidx, self.rowptr_t, self.colidx_t)
         return self._map_t
 
+    edge_attr = entry_edge = _entry_edge_t = None   # set_edge_attr
+
+    def set_edge_attr(self, src, dst, attr):
+        """Attach a feature vector per edge: attr float32 [E, Fe], row x belonging to the edge (src[x], dst[x]) of the caller's list (the
+        list the graph was built from, or any list over its stored pairs).  Keeps g.edge_attr (the caller's order, never permuted),
+        g.entry_edge = csr_entry_edges(...) -- int32 [nnz], the edge row of each stored entry; of duplicate edges the last in the list,
+        self loops ignored, as the build treats them -- and, when first asked for, g.entry_edge_t = entry_edge[attention_map()], the
+        same in the order of CSR(A^T).  GnnxError on a relabelled graph, with attention_map's reasoning: its rows are not ascending,
+        and the search needs them so.  Returns the graph; a GraphBatch takes it unchanged."""
+        if self.nid is not None:
+            raise capi.GnnxError(-7, "set_edge_attr", "a relabelled graph keeps each row in original-id order, not ascending: the "
+                                 "entries cannot be searched on it (build the graph without relabel)")
+        if attr.dim() != 2 or attr.dtype != torch.float32 or not attr.is_contiguous() or int(attr.shape[0]) != int(src.numel()):
+            raise ValueError(f"attr must be a contiguous float32 matrix with one row per edge ({int(src.numel())})")
+        self.entry_edge = csr_entry_edges(self.rowptr, self.colidx, src, dst)
+        self.edge_attr, self._entry_edge_t = attr, None
+        return self
+
+    @property
+    def entry_edge_t(self):
+        if self.entry_edge is None:
+            raise capi.GnnxError(-1, "entry_edge_t", "the graph has no edge attributes (set_edge_attr)")
+        if self._entry_edge_t is None:
+            self._entry_edge_t = self.entry_edge[self.attention_map().long()].contiguous()
+        return self._entry_edge_t
+
     def sample_neighbors(self, k, seed, transpose=True, norm=True):
         """A new CsrGraph on the same vertices whose forward CSR keeps at most k stored neighbours per row (gnnx_csr_sample_neighbors:
         uniform without replacement from `seed`, stored order kept; one seed per epoch).  The transposed CSR is built from the sampled
@@ -1219,6 +1245,78 @@ def spmm_reduce_bwd(rowptr_t, colidx_t, map_t, arg, G, vals=None, out=None, beta
               _ptr(map_t) if nnz else None, _ptr(vals) if nnz else None, _ptr(arg) if arg.numel() else None, _ld(arg),
               _ptr(G) if G.numel() else None, _ld(G), float(beta), _ptr(out), _ld(out), _ptr(ws), ws.numel(), _stream())
     return out
+
+
+EDGE_MSGS = {"add": 0, "relu": 1}   # GNNX_EDGE_MSG_ADD / GNNX_EDGE_MSG_RELU
+
+
+def _edge_args(where, rowptr, colidx, X, E, eidx, msg):
+    """(n_rows, nnz, F) of an edge aggregation after the checks both directions share."""
+    if msg not in EDGE_MSGS:
+        raise capi.GnnxError(-1, where, f"msg must be 'add' or 'relu', got {msg!r}")
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    if E.dim() != 2 or E.dtype != torch.float32 or (X is not None and (X.dim() != 2 or X.shape[1] != E.shape[1] or X.dtype != torch.float32)):
+        raise capi.GnnxError(-2, where, "X [n_cols, F] and E [edge rows, F] must be float32 matrices of one width")
+    if eidx is not None and (eidx.dtype != torch.int32 or int(eidx.numel()) != nnz or not eidx.is_contiguous()):
+        raise capi.GnnxError(-2, where, f"eidx must be a contiguous int32 vector of {nnz} entries")
+    return n_rows, nnz, int(E.shape[1])
+
+
+def spmm_edge(rowptr, colidx, X, E, eidx=None, msg="relu", out=None, beta=0.0, n_cols=None):
+    """gnnx_spmm_csr_edge_f32: Y[i] = beta * Y[i] + sum over the stored entries p of row i of act(X[c_p] + E[e_p]) with e_p = eidx[p]
+    (p itself without eidx) and act the identity ("add") or ReLU ("relu"); X=None sums act(E[e_p]) (n_cols then names the pattern's
+    column count, default n_rows).  One pass, no [nnz, F] intermediate, no atomics: a documented order (include/gnnx.h "edge
+    features"), the same bits every run."""
+    n_rows, nnz, F = _edge_args("spmm_edge", rowptr, colidx, X, E, eidx, msg)
+    if out is None:
+        if beta != 0.0:
+            raise capi.GnnxError(-1, "spmm_edge", "beta = 1 needs the matrix to add to (out)")
+        out = torch.empty((n_rows, F), dtype=torch.float32, device=E.device)
+    assert tuple(out.shape) == (n_rows, F)
+    n_cols = int(X.shape[0]) if X is not None else (n_rows if n_cols is None else int(n_cols))
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, F, device=E.device, tag="reduce")   # the reductions' workspace serves
+    capi.call("gnnx_spmm_csr_edge_f32", n_rows, n_cols, F, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(eidx) if nnz else None,
+              int(E.shape[0]), _ptr(X) if X is not None and X.numel() else None, _ld(X) if X is not None else 0,
+              _ptr(E) if E.numel() else None, _ld(E), EDGE_MSGS[msg], float(beta), _ptr(out), _ld(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def spmm_edge_bwd(rowptr, colidx, X, E, G, eidx=None, msg="relu", out=None):
+    """gnnx_spmm_csr_edge_bwd_f32: dE [edge rows, F] of spmm_edge for G = dL/dY -- row e_p gets G[i] where the message X[c_p] + E[e_p]
+    was positive ("relu") or G[i] itself ("add"); rows that no entry names keep what `out` held (zeros in a new matrix).  dX is
+    spmm_edge(rowptr_t, colidx_t, None, dE, eidx=eidx[map_t], msg="add") on the transposed pattern."""
+    n_rows, nnz, F = _edge_args("spmm_edge_bwd", rowptr, colidx, X, E, eidx, msg)
+    if tuple(G.shape) != (n_rows, F) or G.dtype != torch.float32:
+        raise capi.GnnxError(-2, "spmm_edge_bwd", f"G must be float32 {(n_rows, F)}")
+    if out is None:
+        out = torch.zeros((int(E.shape[0]), F), dtype=torch.float32, device=E.device)
+    assert tuple(out.shape) == (int(E.shape[0]), F)
+    n_cols = int(X.shape[0]) if X is not None else n_rows
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, F, device=E.device, tag="reduce")   # the reductions' workspace serves
+    capi.call("gnnx_spmm_csr_edge_bwd_f32", n_rows, n_cols, F, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(eidx) if nnz else None,
+              int(E.shape[0]), _ptr(X) if X is not None and X.numel() else None, _ld(X) if X is not None else 0,
+              _ptr(E) if E.numel() else None, _ld(E), EDGE_MSGS[msg], _ptr(G) if G.numel() else None, _ld(G),
+              _ptr(out) if out.numel() else None, _ld(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def csr_entry_edges(rowptr, colidx, src, dst):
+    """gnnx_csr_entry_edges: int32 [nnz], the row of the edge list (src, dst) that each stored entry takes its attributes from -- of
+    duplicate edges the last, self loops ignored.  GnnxError (status -3) when an edge names a pair the pattern does not store;
+    ValueError when an entry is named by no edge."""
+    n_rows, nnz, n_edges = int(rowptr.numel() - 1), int(colidx.numel()), int(src.numel())
+    if int(dst.numel()) != n_edges or src.dtype != torch.int32 or dst.dtype != torch.int32:
+        raise capi.GnnxError(-2, "csr_entry_edges", "src and dst must be int32 vectors of one length")
+    eidx = torch.empty(nnz, dtype=torch.int32, device=rowptr.device)
+    missing = torch.empty(1, dtype=torch.int32, device=rowptr.device)
+    capi.call("gnnx_csr_entry_edges", n_rows, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(src.contiguous()) if n_edges else None,
+              _ptr(dst.contiguous()) if n_edges else None, n_edges, _ptr(eidx) if nnz else None, _ptr(missing), _stream())
+    n_missing = int(missing.item())
+    if n_missing:
+        raise capi.GnnxError(-3, "csr_entry_edges", f"{n_missing} edges name a pair that the pattern does not store")
+    if nnz and int(eidx.min()) < 0:
+        raise ValueError(f"{int((eidx < 0).sum())} stored entries are named by no edge of the list")
+    return eidx
 
 
 def transpose(X, out=None):
@@ -2659,6 +2757,114 @@ class EdgeConvStack(_Stack):
             if l == 0:
                 return dh
             G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l])))           # h = relu output of the layer below
+            colsum(G, out=self.db[l - 1])
+        return G
+
+
+class GineStack(_Stack):
+    """L GINE layers (Hu et al. 2020: GIN with edge features, eps fixed at 0) with the surface of SageStack, on a graph that carries
+    edge attributes (g.set_edge_attr):
+        E_l = edge_attr W_e^T + b_e  [E, dims[l]];   M_i = sum_j relu(h_j + E_l[edge of (i, j)])  over the stored columns j of row i;
+        U = h + M;   h' = act( relu(U W_1^T + b_1) W_2^T + b_2 ),   ReLU between layers, none after the last.
+    M is ONE spmm_edge call: no [nnz, F] message matrix exists in the forward.  Backward per layer: the dense products through the MLP,
+    dE_l = spmm_edge_bwd(dU) (the ReLU mask recomputed from h and E_l), dW_e = dE_l^T edge_attr, db_e = colsum(dE_l), and
+    dh = dU + spmm_edge on CSR(A^T) over dE_l through g.entry_edge_t -- which refuses what attention_map refuses.  An empty row has
+    M = 0.  forward / backward / step / train_step / evaluate / grad_buffer / on_graph, and use under GraphClassifier / on_batch (the
+    attributes travel with the batch).  Every operation is a C-ABI call; no atomics on any value; the same bits every run."""
+
+    def __init__(self, g, dims, edge_dim, seed=0, device="cuda"):
+        self.dims, self.edge_dim = list(dims), int(edge_dim)
+        L = len(dims) - 1
+        self._bind(g)
+
+        def weights(k, rows, cols):
+            return [uniform_pm1(seed + 3 * l + k, (rows(l), cols(l)), scale=cols(l) ** -0.5, device=device) for l in range(L)]
+
+        def zeros(width):
+            return [torch.zeros(width(l), dtype=torch.float32, device=device) for l in range(L)]
+
+        self.W_e = weights(0, lambda l: dims[l], lambda l: self.edge_dim)
+        self.W_1 = weights(1, lambda l: dims[l + 1], lambda l: dims[l])
+        self.W_2 = weights(2, lambda l: dims[l + 1], lambda l: dims[l + 1])
+        self.b_e, self.b_1, self.b = zeros(lambda l: dims[l]), zeros(lambda l: dims[l + 1]), zeros(lambda l: dims[l + 1])
+        self.dW_e, self.dW_1, self.dW_2 = ([torch.zeros_like(w) for w in ws] for ws in (self.W_e, self.W_1, self.W_2))
+        self.db_e, self.db_1, self.db = ([torch.zeros_like(b) for b in bs] for bs in (self.b_e, self.b_1, self.b))
+        self._saved = None
+        self._buf = {}
+        self._opt = [None]
+
+    def _bind(self, g):
+        """What the stack holds of the graph itself: its edge attributes and the entry -> edge maps of both patterns."""
+        if getattr(g, "edge_attr", None) is None:
+            raise capi.GnnxError(-1, "GineStack", "the graph has no edge attributes (g.set_edge_attr(src, dst, attr))")
+        if int(g.edge_attr.shape[1]) != self.edge_dim:
+            raise ValueError(f"the graph's edge attributes have {int(g.edge_attr.shape[1])} columns, the stack was built for {self.edge_dim}")
+        self.g = g
+        self.entry_edge, self.entry_edge_t = g.entry_edge, g.entry_edge_t
+        return self
+
+    def params(self):
+        return self.W_e + self.W_1 + self.W_2 + self.b_e + self.b_1 + self.b
+
+    def grads(self):
+        return self.dW_e + self.dW_1 + self.dW_2 + self.db_e + self.db_1 + self.db
+
+    def on_graph(self, g):
+        """This stack on another attributed graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch
+        buffers."""
+        if g.n != self.g.n:
+            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
+        return self._view(share_buf=True)._bind(g)
+
+    def forward(self, X):
+        L, g = len(self.W_1), self.g
+        n, ne = g.n, int(g.edge_attr.shape[0])
+        saved, h = [], X
+        for l in range(L):
+            d0, d1 = self.dims[l], self.dims[l + 1]
+            El = gemm(g.edge_attr, self.W_e[l], transB=True, out=self._tmp(("E", l), (ne, d0)))
+            bias_add(El, self.b_e[l], out=El)
+            U = spmm_edge(g.rowptr, g.colidx, h, El, eidx=self.entry_edge, msg="relu", out=self._tmp(("U", l), (n, d0)))
+            axpy(1.0, h, U)                                                      # GIN-0: the vertex itself with weight 1
+            A = gemm(U, self.W_1[l], transB=True, out=self._tmp(("A", l), (n, d1)))
+            bias_add(A, self.b_1[l], out=A)
+            bn_relu_fwd(A, relu=True, out=A)
+            Y = gemm(A, self.W_2[l], transB=True, out=self._tmp(("Y", l), (n, d1)))
+            bias_add(Y, self.b[l], out=Y)
+            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
+                bn_relu_fwd(Y, relu=True, out=Y)
+            saved.append((h, El, U, A))
+            h = Y
+        self._saved = saved
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """The gradient of every parameter from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        L, g = len(self.W_1), self.g
+        n, ne = g.n, int(g.edge_attr.shape[0])
+        G = dOut
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            d0, d1 = self.dims[l], self.dims[l + 1]
+            h, El, U, A = self._saved[l]
+            gemm(G, A, transA=True, out=self.dW_2[l])
+            dA = gemm(G, self.W_2[l], out=self._tmp(("dA", l), (n, d1)))
+            dZ = relu_mask(A, dA, out=self._tmp(("dZ", l), (n, d1)))             # A = relu output of the first linear map
+            colsum(dZ, out=self.db_1[l])
+            gemm(dZ, U, transA=True, out=self.dW_1[l])
+            dU = gemm(dZ, self.W_1[l], out=self._tmp(("dU", l), (n, d0)))
+            # rows of dE that no entry names (duplicate edges, self loops) are never written: they stay the zeros they were made as
+            dE = spmm_edge_bwd(g.rowptr, g.colidx, h, El, dU, eidx=self.entry_edge, msg="relu", out=self._tmp(("dE", l), (ne, d0), zero=True))
+            gemm(dE, g.edge_attr, transA=True, out=self.dW_e[l])
+            colsum(dE, out=self.db_e[l])
+            if l == 0 and not input_grad:
+                return None
+            dh = spmm_edge(g.rowptr_t, g.colidx_t, None, dE, eidx=self.entry_edge_t, msg="add", out=dU, beta=1.0, n_cols=n)   # self + neighbours
+            if l == 0:
+                return dh
+            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, d0)))               # h = relu output of the layer below
             colsum(G, out=self.db[l - 1])
         return G
 

@@ -967,6 +967,73 @@ int gnnx_spmm_csr_reduce_bwd_f32(int32_t n_rows_t, int32_t n_cols_t, int32_t n_f
                                  int64_t lda, const float *d_G, int64_t ldg, float beta, float *d_dX, int64_t ldx, void *d_workspace,
                                  size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ edge features --------------- */
+/*
+ * Message passing whose message carries a feature vector per EDGE -- GINE (Hu et al. 2020) and the attributed-graph classifiers built
+ * on it: the aggregation of act(x_j + e_ij) over the stored entries of each CSR row in one pass, with no [nnz, n_feat] intermediate, its
+ * backward to the edge rows, and the map from stored entries to the rows of a caller's edge list.  The reference keeps edge_attr as a
+ * scalar weight at most (reference graph.h:35); the contract is this comment, restated in NumPy by tests/edge_ref.py.
+ *
+ * Forward, gnnx_spmm_csr_edge_f32, for entry p of row i with c = colidx[p] and e = eidx[p] (e = p with d_eidx == NULL):
+ *   m_p,f = X[c, f] + E[e, f]                  ONE rounded fp32 add; with d_X == NULL m_p,f = E[e, f] with its own bits.
+ *   t_p,f = m_p,f                              GNNX_EDGE_MSG_ADD
+ *   t_p,f = m_p,f > 0 ? m_p,f : +0             GNNX_EDGE_MSG_RELU: NaN and -0 become +0, as the ReLU of gnnx_spmm_csr_fused_f32 does.
+ *   ORDER of the row sum, with S = 4096, exactly that of gnnx_spmm_csr_reduce_bwd_f32: the row is cut into segments of S consecutive
+ *   entries (the last may be short); a segment is summed by ONE accumulator per feature starting from +0 and walking the segment from
+ *   its LAST entry to its FIRST; the row sum is ((seg_0 + seg_1) + seg_2) + ... in ascending segment order.
+ *   Y[i, f] = acc with beta == 0 (Y is never read), Y[i, f] + acc with beta == 1.  An empty row gives acc = +0.
+ * X: [n_cols, n_feat] ld ldx or NULL; E: [n_edge_rows, n_feat] ld lde; Y: [n_rows, n_feat] ld ldy; columns beyond n_feat are not touched.
+ * eidx: int32 [nnz] or NULL, TRUSTED like colidx (every value in [0, n_edge_rows)); n_edge_rows is only validated: it must be >= nnz
+ * with d_eidx == NULL.  X, E and Y do not alias.  No atomics on any value: the bits are a function of the inputs alone, however rows,
+ * segments and features map to lanes.
+ *
+ * Backward to the edge rows, gnnx_spmm_csr_edge_bwd_f32, with G = dL/dY [n_rows, n_feat] ld ldg and dE [n_edge_rows, n_feat] ld ldde:
+ *   dE[e_p, f] = G[i, f]                       GNNX_EDGE_MSG_ADD (X and E are not read and may be NULL)
+ *   dE[e_p, f] = m_p,f > 0 ? G[i, f] : +0      GNNX_EDGE_MSG_RELU, m recomputed from X and E as above: a select, no rounding.
+ *   Rows of dE that no entry names are not touched.  There is no sum, so no order; two entries that name one edge row race (a caller's
+ *   eidx from gnnx_csr_entry_edges never does that).  dE aliases no input.
+ * Backward to X needs no third kernel: dX (+)= the FORWARD call on the transposed pattern with d_X = NULL, d_E = dE, d_eidx =
+ * eidx[map_t] (gnnx_csr_transpose_map; map_t itself without eidx) and GNNX_EDGE_MSG_ADD -- row c of CSR(A^T) sums the dE rows of the
+ * entries that name column c, in the order above, and a hub column spreads over the device like a hub row.
+ *
+ * gnnx_csr_entry_edges: eidx for a caller's edge list (src[x], dst[x]), x < n_edges, on a CSR whose rows are STRICTLY ASCENDING (as
+ * gnnx_csr_from_coo builds them).  eidx[p] = -1 for every entry and *d_missing = 0 first, on the stream; then one lane per edge finds
+ * the entry (src, dst) by binary search in row src and keeps the LARGEST x that names it (an atomic maximum on an index: the result is
+ * the same on every run): of duplicate edges the LAST in the list wins, as in gnnx_csr_from_coo_weighted.  An edge with src == dst is
+ * ignored (the build removes self loops); any other edge whose pair is not stored, or whose src is outside [0, n_rows), adds 1 to
+ * *d_missing (device int32).  An entry that no edge names keeps -1.  n_edges >= 2^31, a negative size or a null d_rowptr / d_missing /
+ * edge list is GNNX_ERR_INVALID_ARG.
+ *
+ * The two aggregation calls are asynchronous on `stream` (a chain of launches on that one stream); they allocate nothing and
+ * synchronise nothing and TRUST the CSR and nnz (= rowptr[n_rows]).  Negative sizes, a leading dimension < n_feat, a msg outside the
+ * enum, a beta other than 0 or 1, n_edge_rows < nnz without eidx and nnz >= 2^31 are GNNX_ERR_INVALID_ARG before any device call, and
+ * so is a null pointer (d_X and d_eidx may be NULL; d_colidx / d_E / d_G / d_dE may be NULL with nnz == 0).  n_feat == 0 or n_rows == 0
+ * returns GNNX_OK and writes nothing; nnz == 0 still writes the forward's per-row outputs.  The workspace is the neighbourhood
+ * reductions': a workspace that is NULL or smaller than gnnx_spmm_csr_reduce_workspace(n_rows, nnz, n_feat) bytes is GNNX_ERR_WORKSPACE
+ * with nothing written.  It serves either call (and the dX call, which passes the transposed pattern's n_rows), holds nothing between
+ * calls and may sit at any address.  The edge calls lay out its front only -- 16 counter words, per (segment slot, feature) the
+ * segment's sum, the hub list with each hub's first slot and the hub of each slot: 4 * (16 + 2 * hubs + segs + segs * n_feat) bytes of
+ * the 4 * (16 + 2 * hubs + segs + 2 * segs * n_feat) that query counts -- so one buffer sized once serves a layer's reductions and its
+ * edge aggregations alike.
+ *
+ * Kernels (gnnx_edge.hip): rows of at most S entries take lane groups of 4 .. 64 lanes per row, one 16-byte piece per lane, feature
+ * tiles in the grid's y; a group fetches its entries' columns and edge rows with one coalesced load each, hands them out by shuffle
+ * and requests four X rows and four E rows before the first add.  n_feat % 4 != 0, or an X / E / Y / G / dE pointer or leading
+ * dimension that is not 16-byte aligned, takes scalar lanes with the same bits.  Longer rows are listed in the workspace by the row
+ * kernel (a counter atomic reserves slots, never an atomic on a value), a fixed grid strides over their segments -- the backward
+ * writes their dE rows from there -- and a combine kernel adds the forward's segment sums in ascending order.
+ */
+enum { GNNX_EDGE_MSG_ADD = 0, GNNX_EDGE_MSG_RELU = 1 };
+int gnnx_spmm_csr_edge_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                           const int32_t *d_eidx, int64_t n_edge_rows, const float *d_X, int64_t ldx, const float *d_E, int64_t lde,
+                           int msg, float beta, float *d_Y, int64_t ldy, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_spmm_csr_edge_bwd_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t nnz, const int32_t *d_rowptr,
+                               const int32_t *d_colidx, const int32_t *d_eidx, int64_t n_edge_rows, const float *d_X, int64_t ldx,
+                               const float *d_E, int64_t lde, int msg, const float *d_G, int64_t ldg, float *d_dE, int64_t ldde,
+                               void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_csr_entry_edges(int32_t n_rows, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_src, const int32_t *d_dst,
+                         int64_t n_edges, int32_t *d_eidx, int32_t *d_missing, void *stream);
+
 /* ------------------------------------------------------------------ graph readout --------------- */
 /*
  * One row of output per GRAPH of a batch: the SUM, MEAN or MAX of each segment of consecutive rows of X, and the backward that hands a
