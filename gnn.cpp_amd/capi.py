@@ -166,6 +166,10 @@ _SIGS = {
     "gnnx_spmm_csr_reduce_workspace": [_i32, _i64, _i32, C.POINTER(_sz)],
     "gnnx_spmm_csr_reduce_f32": [C.c_int, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
     "gnnx_spmm_csr_reduce_bwd_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_spmm_csr_pna_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_pna_bwd_coeff_f32": [_i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
+    "gnnx_spmm_csr_pna_bwd_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                  _f32, _vp, _i64, _vp, _sz, _vp],
     "gnnx_spmm_csr_edge_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_int, _f32, _vp, _i64, _vp, _sz, _vp],
     "gnnx_spmm_csr_edge_bwd_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, _sz,
                                    _vp],

@@ -1247,6 +1247,72 @@ def spmm_reduce_bwd(rowptr_t, colidx_t, map_t, arg, G, vals=None, out=None, beta
     return out
 
 
+def _arg_matrix(t, shape, what, where):
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.int32:
+        raise capi.GnnxError(-2, where, f"{what} must be int32 {tuple(shape)}")
+    return t
+
+
+def spmm_pna(rowptr, colidx, X, eps=1e-5, out=None, argmin_out=None, argmax_out=None, want_arg=True):
+    """gnnx_spmm_csr_pna_f32: (M, argmin, argmax) from ONE gather of every row's neighbours.  M [n_rows, 4 F] = mean | min | max | std over
+    the stored entries of the row (std = sqrt(max(E[x^2] - E[x]^2, 0) + eps)); argmin / argmax int32 [n_rows, F], absolute positions in
+    colidx, the ones spmm_reduce gives.  An empty row gives +0 everywhere and -1.  want_arg=False: both args are None and not computed.
+    The bits are a function of the inputs alone (include/gnnx.h "principal neighbourhood aggregation")."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    n_cols, F = X.shape
+    dev = X.device
+    if out is None:
+        out = torch.empty((n_rows, 4 * F), dtype=torch.float32, device=dev)
+    assert tuple(out.shape) == (n_rows, 4 * F)
+    args = [None, None]
+    if want_arg:
+        args = [torch.empty((n_rows, F), dtype=torch.int32, device=dev) if t is None else _arg_matrix(t, (n_rows, F), "an arg output", "spmm_pna")
+                for t in (argmin_out, argmax_out)]
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, 3 * F, device=dev, tag="reduce")
+    capi.call("gnnx_spmm_csr_pna_f32", n_rows, n_cols, F, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, _ptr(X) if X.numel() else None,
+              _ld(X), float(eps), _ptr(out), _ld(out), _ptr(args[0]), _ld(args[0]) if want_arg else 0, _ptr(args[1]),
+              _ld(args[1]) if want_arg else 0, _ptr(ws), ws.numel(), _stream())
+    return out, args[0], args[1]
+
+
+def spmm_pna_bwd(rowptr_t, colidx_t, map_t, rowptr, X, M, argmin, argmax, dM, out=None, beta=0.0, _coeff=None):
+    """dX = beta * dX + the gradient of spmm_pna with respect to X from dM = dL/dM [n, 4 F], on the TRANSPOSED pattern: first
+    gnnx_pna_bwd_coeff_f32 -- per row B = (dstd / d) / std and A = dmean / d - B * mean from the saved M, into scratch -- then
+    gnnx_spmm_csr_pna_bwd_f32: row c collects A_i + X[c] * B_i and the dmax / dmin of the rows whose winner it was, over its entries
+    i = colidx_t[q].  rowptr: of the forward pattern (the row lengths); map_t: csr_transpose_map.  The derivative of the standard
+    deviation is taken without the variance's clamp at 0.  No atomics: a documented order (include/gnnx.h), the same bits every run.
+    _coeff = (A, B): precomputed coefficient matrices instead of the coefficient kernel (tests)."""
+    n_rows_t, nnz = int(rowptr_t.numel() - 1), int(colidx_t.numel())
+    n_cols_t, F = int(dM.shape[0]), int(X.shape[1])
+    dev = X.device
+    if tuple(dM.shape) != (n_cols_t, 4 * F) or tuple(M.shape) != (n_cols_t, 4 * F) or int(rowptr.numel()) != n_cols_t + 1:
+        raise capi.GnnxError(-2, "spmm_pna_bwd", f"M and dM must be {(n_cols_t, 4 * F)} and rowptr have {n_cols_t + 1} entries")
+    if int(X.shape[0]) != n_rows_t or int(map_t.numel()) != nnz:
+        raise capi.GnnxError(-2, "spmm_pna_bwd", f"X must have {n_rows_t} rows and map_t {nnz} entries")
+    _arg_matrix(argmin, (n_cols_t, F), "argmin", "spmm_pna_bwd")
+    _arg_matrix(argmax, (n_cols_t, F), "argmax", "spmm_pna_bwd")
+    if out is None:
+        if beta != 0.0:
+            raise capi.GnnxError(-1, "spmm_pna_bwd", "beta = 1 needs the matrix to add to (out)")
+        out = torch.empty((n_rows_t, F), dtype=torch.float32, device=dev)
+    assert tuple(out.shape) == (n_rows_t, F)
+    if _coeff is None:
+        words = n_cols_t * F
+        A, B = _workspace(8 * words, dev, "pna_coeff")[:8 * words].view(torch.float32).view(2, n_cols_t, F)
+        capi.call("gnnx_pna_bwd_coeff_f32", n_cols_t, F, _ptr(rowptr), _ptr(M) if words else None, _ld(M), _ptr(dM) if words else None, _ld(dM),
+                  _ptr(A) if words else None, F, _ptr(B) if words else None, F, _stream())
+    else:
+        A, B = _coeff
+        assert tuple(A.shape) == (n_cols_t, F) and tuple(B.shape) == (n_cols_t, F)
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows_t, nnz, F, device=dev, tag="reduce")
+    have = bool(nnz)
+    capi.call("gnnx_spmm_csr_pna_bwd_f32", n_rows_t, n_cols_t, F, nnz, _ptr(rowptr_t), _ptr(colidx_t) if have else None, _ptr(map_t) if have else None,
+              _ptr(A) if have else None, _ld(A), _ptr(B) if have else None, _ld(B), _ptr(argmin) if have else None, _ld(argmin),
+              _ptr(argmax) if have else None, _ld(argmax), _ptr(dM) if have else None, _ld(dM), _ptr(X) if X.numel() else None, _ld(X), float(beta),
+              _ptr(out), _ld(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
 EDGE_MSGS = {"add": 0, "relu": 1}   # GNNX_EDGE_MSG_ADD / GNNX_EDGE_MSG_RELU
 
 
@@ -2865,6 +2931,124 @@ class GineStack(_Stack):
             if l == 0:
                 return dh
             G = relu_mask(h, dh, out=self._tmp(("G", l), (n, d0)))               # h = relu output of the layer below
+            colsum(G, out=self.db[l - 1])
+        return G
+
+
+PNA_SCALERS = ("identity", "amplification", "attenuation")
+
+
+def _log_degrees(rowptr):
+    """log(deg + 1) per row, float32 on the device: O(n) plumbing at bind time."""
+    return torch.log((rowptr[1:] - rowptr[:-1]).to(torch.float32) + 1.0)
+
+
+class PnaStack(_Stack):
+    """L PNA layers (Corso et al. 2020; PyG's PNAConv without towers and pre / post MLPs) with the surface of SageStack:
+        M = spmm_pna(h) = mean | min | max | std of the STORED columns of each row   [n, 4 F_l], ONE gather of the neighbourhood;
+        h' = act( h W_s^T  +  sum over the scalers k of  s_k (.) (M W_k^T)  +  b ),   ReLU between layers, none after the last,
+    W_k [F_{l+1}, 4 F_l] per scaler.  The scaler vectors, per row, with delta = the mean of log(deg + 1) over the rows of the graph the
+    stack was BUILT on:  identity s = 1;  amplification s = log(deg + 1) / delta;  attenuation s = delta / log(deg + 1), 0 for an empty
+    row.  on_graph and GraphClassifier's views keep delta and recompute the vectors from the new graph's degrees (self.scale[k], None
+    for identity).  s_k (.) (M W_k^T) is computed as (s_k (.) M) W_k^T: a rowscale and a gemm with beta = 1.
+    Backward: spmm_pna_bwd through g.attention_map(), which refuses a relabelled graph and one without a transposed CSR, with
+    SageStack(aggr="max")'s GnnxError.  An empty row aggregates to zero: its output is h W_s^T + b.
+    forward / backward / step / train_step / evaluate / grad_buffer / on_graph; every operation of forward and backward is a C-ABI call
+    (spmm_pna, spmm_pna_bwd, gemm, rowscale, bias_add, the ReLU and its mask, colsum).  No atomics on any value; the same bits every run."""
+
+    def __init__(self, g, dims, scalers=PNA_SCALERS, eps=1e-5, seed=0, device="cuda"):
+        scalers = tuple(scalers)
+        if not scalers or any(k not in PNA_SCALERS for k in scalers) or len(set(scalers)) != len(scalers):
+            raise ValueError(f"scalers must be distinct names out of {PNA_SCALERS}, got {scalers!r}")
+        self.dims, self.scalers, self.eps = list(dims), scalers, float(eps)
+        L, K = len(dims) - 1, len(scalers)
+        logd = _log_degrees(g.rowptr)
+        self.delta = float(logd.double().mean()) if g.n else 0.0
+        if not self.delta > 0.0:     # a graph without entries: every scaler is the identity's
+            self.delta = 1.0
+        self._bind(g)
+        self.W_s = [uniform_pm1(seed + (K + 1) * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        # W_n[l][k]: the weight of scaler k; the stack's parameter list holds them layer by layer
+        self.W_n = [[uniform_pm1(seed + (K + 1) * l + 1 + k, (dims[l + 1], 4 * dims[l]), scale=(4 * K * dims[l]) ** -0.5, device=device)
+                     for k in range(K)] for l in range(L)]
+        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
+        self.dW_s = [torch.zeros_like(w) for w in self.W_s]
+        self.dW_n = [[torch.zeros_like(w) for w in ws] for ws in self.W_n]
+        self.db = [torch.zeros_like(b) for b in self.b]
+        self._saved = None
+        self._buf = {}
+        self._opt = [None]
+
+    def _bind(self, g):
+        """What the stack holds of the graph itself: the transpose map and the scaler vectors of ITS degrees under the stack's delta."""
+        self.map_t = g.attention_map()
+        self.g = g
+        logd = _log_degrees(g.rowptr)
+        made = {"identity": lambda: None,
+                "amplification": lambda: (logd / self.delta).contiguous(),
+                "attenuation": lambda: torch.where(logd > 0, self.delta / logd.clamp(min=1e-30), torch.zeros_like(logd)).contiguous()}
+        self.scale = [made[k]() for k in self.scalers]
+        return self
+
+    def params(self):
+        return self.W_s + [w for ws in self.W_n for w in ws] + self.b
+
+    def grads(self):
+        return self.dW_s + [w for ws in self.dW_n for w in ws] + self.db
+
+    def on_graph(self, g):
+        """This stack on another graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch buffers;
+        delta stays, the scaler vectors follow the new graph's degrees."""
+        if g.n != self.g.n:
+            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
+        return self._view(share_buf=True)._bind(g)
+
+    def forward(self, X):
+        L, g, n = len(self.W_s), self.g, self.g.n
+        saved, h = [], X
+        for l in range(L):
+            d0, d1 = self.dims[l], self.dims[l + 1]
+            M, amin, amax = spmm_pna(g.rowptr, g.colidx, h, eps=self.eps, out=self._tmp(("M", l), (n, 4 * d0)),
+                                     argmin_out=self._tmp(("argmin", l), (n, d0), torch.int32),
+                                     argmax_out=self._tmp(("argmax", l), (n, d0), torch.int32))
+            Z = gemm(h, self.W_s[l], transB=True, out=self._tmp(("Z", l), (n, d1)))
+            for k, s in enumerate(self.scale):
+                Ms = M if s is None else rowscale(M, s, out=self._tmp(("Ms", l), (n, 4 * d0)))
+                gemm(Ms, self.W_n[l][k], transB=True, out=Z, beta=1.0)
+            Y = self._tmp(("Y", l), (n, d1))
+            bias_add(Z, self.b[l], out=Y)
+            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
+                bn_relu_fwd(Y, relu=True, out=Y)
+            saved.append((h, M, amin, amax))
+            h = Y
+        self._saved = saved
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """dW_s, dW_n and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        L, g, n = len(self.W_s), self.g, self.g.n
+        G = dOut
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            d0, d1 = self.dims[l], self.dims[l + 1]
+            h, M, amin, amax = self._saved[l]
+            gemm(G, h, transA=True, out=self.dW_s[l])
+            need_dh = l > 0 or input_grad
+            dM = self._tmp(("dM", l), (n, 4 * d0)) if need_dh else None
+            for k, s in enumerate(self.scale):       # s_k (.) G serves both products of scaler k
+                Gs = G if s is None else rowscale(G, s, out=self._tmp(("Gs", l), (n, d1)))
+                gemm(Gs, M, transA=True, out=self.dW_n[l][k])
+                if need_dh:
+                    gemm(Gs, self.W_n[l][k], out=dM, beta=1.0 if k else 0.0)
+            if not need_dh:
+                return None
+            dh = gemm(G, self.W_s[l], out=self._tmp(("dh", l), (n, d0)))                  # through the vertex itself
+            spmm_pna_bwd(g.rowptr_t, g.colidx_t, self.map_t, g.rowptr, h, M, amin, amax, dM, out=dh, beta=1.0)   # + its neighbourhood
+            if l == 0:
+                return dh
+            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, d0)))                       # h = relu output of the layer below
             colsum(G, out=self.db[l - 1])
         return G
 

@@ -967,6 +967,75 @@ int gnnx_spmm_csr_reduce_bwd_f32(int32_t n_rows_t, int32_t n_cols_t, int32_t n_f
                                  int64_t lda, const float *d_G, int64_t ldg, float beta, float *d_dX, int64_t ldx, void *d_workspace,
                                  size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ principal neighbourhood aggregation ---- */
+/*
+ * The four aggregators of PNA (Corso et al. 2020; PyG's PNAConv) -- mean, min, max and standard deviation over the stored entries of
+ * each row of an UNWEIGHTED CSR pattern -- from ONE gather of the row, and the backward of all four from one walk of the transposed
+ * row.  The reference has GCN's sum only (reference graph.h:114-115); the contract is this comment.
+ *
+ * Forward, gnnx_spmm_csr_pna_f32.  Y: [n_rows, 4 * n_feat] ld ldy, four slabs of n_feat columns in PyG's order  mean | min | max | std
+ * (the following dense product reads it as one matrix).  For a row with d > 0 entries at positions b .. e - 1, per feature, with
+ * x_p = X[colidx[p], f] and S = 4096:
+ *   s1   = ((+0 + x_b) + x_{b+1}) + ...        ONE accumulator in ascending position;
+ *   s2   = the same chain over x_p * x_p        the product rounded first, then added;
+ *          d > S: one such chain per segment of S consecutive entries (the last may be short), the segment sums added in ascending
+ *          order, (seg_0 + seg_1) + seg_2 + ...;
+ *   r    = 1.0f / (float)d;   mean = s1 * r;   msq = s2 * r;
+ *   var  = msq - mean * mean  where that is > 0, +0 otherwise (the product rounded first);
+ *   std  = sqrtf(var + eps)
+ * -- one float32 rounding per written operation.  The division and the square root are correctly rounded: the library is built with
+ * hipcc's defaults (-fhip-fp32-correctly-rounded-divide-sqrt is on, no fast-math flag, -ffp-contract=off).
+ *   min, max, argmin, argmax: the bits and positions gnnx_spmm_csr_reduce_f32 gives on the same input with vals == NULL -- the first
+ *   entry that nothing beats wins, +0 and -0 tie, MIN is MAX on sign-flipped values, the running value starts from the first entry.
+ *   The args are ABSOLUTE positions in colidx; int32 [n_rows, n_feat], each with a leading dimension of its own; either may be NULL.
+ * An empty row writes +0 to all four slabs (std too: not sqrt(eps)) and -1 to both args.  Columns of Y beyond 4 * n_feat and of the args
+ * beyond n_feat are not touched.  X aliases no output.  No atomics on any value: the bits depend on the inputs alone, however rows,
+ * segments and features map to lanes.  The variance is the plain E[x^2] - E[x]^2 of float32 sums: where |mean| >> std it cancels (a
+ * shifted or Welford form is not implemented).
+ *
+ * Backward.  With dM [n_rows, 4 * n_feat] ld ldm the gradient of Y in the same slab order,
+ *   gnnx_pna_bwd_coeff_f32, per row i and feature:   B_i = (dstd_i * r_i) / std_i;   A_i = dmean_i * r_i - B_i * mean_i
+ *   (mean and std read from the saved Y, r_i = 1.0f / (float)d_i from rowptr; one rounding per written operation, the two products
+ *   of A before the subtraction).  A row with d == 0 has A = B = +0.  A, B: [n_rows, n_feat] with ld lda / ldb.
+ *   gnnx_spmm_csr_pna_bwd_f32, on the TRANSPOSED pattern like gnnx_spmm_csr_reduce_bwd_f32 (entry q of row c of CSR(A^T) is the entry
+ *   (i, c) of A with i = colidx_t[q] and p = map_t[q] its position in CSR(A)):
+ *     dX[c, f] (+)= sum over q of   A_i + x_c * B_i + (argmax[i, f] == p ? dmax_i : nothing) + (argmin[i, f] == p ? dmin_i : nothing)
+ *   This is the derivative of sqrt(var + eps) WITHOUT the clamp of var at 0: where the clamp acts every x_j of the row equals the mean
+ *   to within rounding, so the dropped term is rounding noise (PyG's ReLU would zero it).
+ *   ORDER, with S = 4096: per output row c and feature TWO accumulators from +0 -- `a` takes, per entry, A_i, then the routed dmax_i,
+ *   then the routed dmin_i (a term that is not routed adds nothing, not +0); `b` takes B_i -- walking each segment of S entries from
+ *   its LAST entry to its FIRST, the segment sums of a and of b added in ascending segment order (the reduce backward's order).  Then
+ *     dX[c, f] = (beta ? dX[c, f] : +0) + (a + x_c * b)         the product rounded first; beta in {0, 1}.
+ *   dmax and dmin are read in place from dM's slabs (columns 2 * n_feat .. and n_feat ..).  d_X: [n_rows_t, n_feat] ld ldx, the
+ *   forward's input; d_dX: [n_rows_t, n_feat] ld lddx, aliasing no input.  No atomics on any value.
+ *
+ * All three calls are asynchronous on `stream`, allocate nothing, synchronise nothing and TRUST the CSR and nnz.  Negative sizes, a
+ * leading dimension < n_feat, ldy or ldm < 4 * n_feat, eps < 0, a beta other than 0 or 1 and nnz >= 2^31 are GNNX_ERR_INVALID_ARG before
+ * any device call, and so is a null pointer (the forward's args may be NULL; d_colidx / d_X, and the backward's per-entry inputs, may
+ * be NULL with nnz == 0).  n_rows == 0 or n_feat == 0 returns GNNX_OK and writes nothing; nnz == 0 still writes the per-row outputs.
+ * There is no workspace query of their own: the forward needs gnnx_spmm_csr_reduce_workspace(n_rows, nnz, 3 * n_feat) bytes -- that
+ * counts 16 counter words + 2 * hubs + segs + 2 * segs * 3 * n_feat words, and the forward keeps SIX words per (segment slot, feature):
+ * s1, s2, maxval, minval, maxpos, minpos -- and the backward gnnx_spmm_csr_reduce_workspace(n_rows_t, nnz, n_feat) bytes (TWO words
+ * per slot and feature: a and b).  A workspace that is NULL or smaller is GNNX_ERR_WORKSPACE with nothing written; it holds nothing
+ * between calls and may sit at any address.
+ *
+ * Kernels (gnnx_pna.hip): the lane groups of gnnx_reduce.hip -- 4 .. 64 lanes per row, one 16-byte piece per lane, feature tiles in the
+ * grid's y, the group's entries fetched with one coalesced load and handed out by shuffle, four entries' rows requested before the
+ * first is consumed.  n_feat % 4 != 0, or any pointer or leading dimension that is not 16-byte aligned, takes scalar lanes with the
+ * same bits (n_feat % 4 == 0 and an aligned ldy keep Y's four slabs aligned).  Rows longer than S are listed in the workspace by the
+ * row kernel, a fixed grid strides over their segments, a combine kernel finishes each (hub, feature) in ascending segment order.
+ */
+int gnnx_spmm_csr_pna_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                          const float *d_X, int64_t ldx, float eps, float *d_Y, int64_t ldy, int32_t *d_argmin, int64_t ld_argmin,
+                          int32_t *d_argmax, int64_t ld_argmax, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_pna_bwd_coeff_f32(int32_t n_rows, int32_t n_feat, const int32_t *d_rowptr, const float *d_Y, int64_t ldy, const float *d_dM,
+                           int64_t ldm, float *d_A, int64_t lda, float *d_B, int64_t ldb, void *stream);
+int gnnx_spmm_csr_pna_bwd_f32(int32_t n_rows_t, int32_t n_cols_t, int32_t n_feat, int64_t nnz, const int32_t *d_rowptr_t,
+                              const int32_t *d_colidx_t, const int32_t *d_map_t, const float *d_A, int64_t lda, const float *d_B,
+                              int64_t ldb, const int32_t *d_argmin, int64_t ld_argmin, const int32_t *d_argmax, int64_t ld_argmax,
+                              const float *d_dM, int64_t ldm, const float *d_X, int64_t ldx, float beta, float *d_dX, int64_t lddx,
+                              void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ edge features --------------- */
 /*
  * Message passing whose message carries a feature vector per EDGE -- GINE (Hu et al. 2020) and the attributed-graph classifiers built
