@@ -174,6 +174,9 @@ _SIGS = {
     "gnnx_spmm_csr_edge_bwd_f32": [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, _sz,
                                    _vp],
     "gnnx_csr_entry_edges": [_i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "gnnx_spmm_csr_typed_f32": [_i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_spmm_csr_typed_bwd_f32": [_i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_typed_coeff_grad_f32": [_i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_segment_pool_workspace": [_i32, _i32, _i32, C.POINTER(_sz)],
     "gnnx_segment_pool_f32": [C.c_int, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
     "gnnx_segment_pool_bwd_f32": [C.c_int, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp],

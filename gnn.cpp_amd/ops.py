@@ -241,6 +241,52 @@ class CsrGraph:
             self._entry_edge_t = self.entry_edge[self.attention_map().long()].contiguous()
         return self._entry_edge_t
 
+    n_relations = 0
+    entry_type = typed_norm = type_order = _entry_type_t = _typed_norm_t = None   # set_edge_type
+
+    def set_edge_type(self, src, dst, etype, n_relations):
+        """Attach a relation type per edge: etype int32 [E] in [0, n_relations), entry x belonging to the edge (src[x], dst[x]) of the
+        caller's list.  It goes through csr_entry_edges: of duplicate edges the last in the list gives the stored entry its type and
+        self loops are ignored, exactly as set_edge_attr documents -- the graph's build collapses a pair (i, j) that several relations
+        name into ONE entry (the C-ABI calls themselves take any CSR, duplicates included; a multigraph needs a pattern of its own).
+        Keeps g.n_relations, g.entry_type (int32 [nnz]), g.typed_norm (float32 [nnz]: 1 / |N_r(i)|, one correctly rounded division by
+        the count of row i's entries of the entry's type), g.type_order (_entry_type_order: the type-sorted entries and their offsets)
+        and, when first asked for, g.entry_type_t / g.typed_norm_t = the same in the order of CSR(A^T) through attention_map(), which
+        refuses what it already refuses.  One-off O(nnz log nnz) set-up in torch ops.  GnnxError on a relabelled graph and on a type
+        outside [0, n_relations).  Returns the graph; a GraphBatch takes it unchanged."""
+        if self.nid is not None:
+            raise capi.GnnxError(-7, "set_edge_type", "a relabelled graph keeps each row in original-id order, not ascending: the "
+                                 "entries cannot be searched on it (build the graph without relabel)")
+        R = int(n_relations)
+        if etype.dim() != 1 or etype.dtype != torch.int32 or int(etype.numel()) != int(src.numel()):
+            raise capi.GnnxError(-2, "set_edge_type", f"etype must be an int32 vector with one entry per edge ({int(src.numel())})")
+        if R < 1 or (etype.numel() and (int(etype.min()) < 0 or int(etype.max()) >= R)):
+            raise capi.GnnxError(-3, "set_edge_type", f"a relation type lies outside [0, {R})")
+        entry_edge = csr_entry_edges(self.rowptr, self.colidx, src, dst)
+        self.entry_type = etype[entry_edge.long()].contiguous()
+        rows = torch.repeat_interleave(torch.arange(self.n, device=etype.device), (self.rowptr[1:] - self.rowptr[:-1]).long())
+        _, inverse, counts = torch.unique(rows * R + self.entry_type.long(), return_inverse=True, return_counts=True)
+        self.typed_norm = (torch.ones(self.nnz, dtype=torch.float32, device=etype.device) / counts[inverse].to(torch.float32)).contiguous()
+        self.type_order = _entry_type_order(self.entry_type, R)
+        self.n_relations, self._entry_type_t, self._typed_norm_t = R, None, None
+        return self
+
+    @property
+    def entry_type_t(self):
+        if self.entry_type is None:
+            raise capi.GnnxError(-1, "entry_type_t", "the graph has no relation types (set_edge_type)")
+        if self._entry_type_t is None:
+            self._entry_type_t = self.entry_type[self.attention_map().long()].contiguous()
+        return self._entry_type_t
+
+    @property
+    def typed_norm_t(self):
+        if self.entry_type is None:
+            raise capi.GnnxError(-1, "typed_norm_t", "the graph has no relation types (set_edge_type)")
+        if self._typed_norm_t is None:
+            self._typed_norm_t = self.typed_norm[self.attention_map().long()].contiguous()
+        return self._typed_norm_t
+
     def sample_neighbors(self, k, seed, transpose=True, norm=True):
         """A new CsrGraph on the same vertices whose forward CSR keeps at most k stored neighbours per row (gnnx_csr_sample_neighbors:
         uniform without replacement from `seed`, stored order kept; one seed per epoch).  The transposed CSR is built from the sampled
@@ -1383,6 +1429,92 @@ def csr_entry_edges(rowptr, colidx, src, dst):
     if nnz and int(eidx.min()) < 0:
         raise ValueError(f"{int((eidx < 0).sum())} stored entries are named by no edge of the list")
     return eidx
+
+
+def _typed_args(where, rowptr, colidx, etype, n_types, coeff, vals):
+    """(n_rows, nnz, R, B) of a relation-typed call after the checks all three share; B = R in one-hot mode (coeff None)."""
+    n_rows, nnz, R = int(rowptr.numel() - 1), int(colidx.numel()), int(n_types)
+    if etype.dtype != torch.int32 or int(etype.numel()) != nnz or not etype.is_contiguous():
+        raise capi.GnnxError(-2, where, f"etype must be a contiguous int32 vector of {nnz} entries")
+    if vals is not None and (vals.dtype != torch.float32 or int(vals.numel()) != nnz or not vals.is_contiguous()):
+        raise capi.GnnxError(-2, where, f"vals must be a contiguous float32 vector of {nnz} entries")
+    if coeff is not None and (coeff.dim() != 2 or coeff.dtype != torch.float32 or not coeff.is_contiguous() or int(coeff.shape[0]) != R):
+        raise capi.GnnxError(-2, where, f"coeff must be a contiguous float32 matrix with one row per relation ({R})")
+    return n_rows, nnz, R, (R if coeff is None else int(coeff.shape[1]))
+
+
+def spmm_typed(rowptr, colidx, etype, X, n_types, coeff=None, vals=None, out=None):
+    """gnnx_spmm_csr_typed_f32: M [n_rows, B F], slab b = sum over the stored entries p of row i of (coeff[etype[p], b] * vals[p]) *
+    X[colidx[p]] -- ONE gather of every neighbour row feeding B accumulators.  coeff=None is one-hot mode, B = n_types: slab r sums the
+    neighbours of relation r alone (no 0 * x ever reaches another slab).  vals: per-entry weights (CsrGraph.typed_norm), None = 1.
+    `out` is overwritten, never read.  No atomics: a documented order (include/gnnx.h "relation-typed aggregation"), the same bits
+    every run."""
+    n_rows, nnz, R, B = _typed_args("spmm_typed", rowptr, colidx, etype, n_types, coeff, vals)
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise capi.GnnxError(-2, "spmm_typed", "X must be a float32 matrix [n_cols, F]")
+    F = int(X.shape[1])
+    if out is None:
+        out = torch.empty((n_rows, B * F), dtype=torch.float32, device=X.device)
+    elif out.dim() != 2 or out.dtype != torch.float32 or tuple(out.shape) != (n_rows, B * F):
+        raise capi.GnnxError(-2, "spmm_typed", f"out must be float32 {(n_rows, B * F)}: {B} slabs of {F} columns"
+                                               + (" (one-hot mode has one slab per relation)" if coeff is None else ""))
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, B * F, device=X.device, tag="reduce")   # the reductions' workspace serves
+    capi.call("gnnx_spmm_csr_typed_f32", n_rows, int(X.shape[0]), F, nnz, R, B, _ptr(rowptr), _ptr(colidx) if nnz else None,
+              _ptr(etype) if nnz else None, _ptr(vals) if nnz else None, _ptr(coeff), _ptr(X) if X.numel() else None, _ld(X),
+              _ptr(out) if out.numel() else None, _ld(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def spmm_typed_bwd(rowptr_t, colidx_t, etype_t, dM, n_types, n_feat, coeff=None, vals_t=None, out=None, beta=0.0):
+    """gnnx_spmm_csr_typed_bwd_f32: dX [n_rows_t, F] (+)= the gradient of spmm_typed with respect to X from dM [n, B F], on the
+    TRANSPOSED pattern: etype_t and vals_t are the forward's per-entry arrays in the order of CSR(A^T) (CsrGraph.entry_type_t /
+    typed_norm_t).  Per entry the B slab terms are chained in ascending b, then the entries are summed in the forward's order."""
+    n_rows, nnz, R, B = _typed_args("spmm_typed_bwd", rowptr_t, colidx_t, etype_t, n_types, coeff, vals_t)
+    F = int(n_feat)
+    if dM.dim() != 2 or dM.dtype != torch.float32 or int(dM.shape[1]) != B * F:
+        raise capi.GnnxError(-2, "spmm_typed_bwd", f"dM must be a float32 matrix of {B} slabs of {F} columns")
+    if out is None:
+        if beta != 0.0:
+            raise capi.GnnxError(-1, "spmm_typed_bwd", "beta = 1 needs the matrix to add to (out)")
+        out = torch.empty((n_rows, F), dtype=torch.float32, device=dM.device)
+    elif out.dim() != 2 or out.dtype != torch.float32 or tuple(out.shape) != (n_rows, F):
+        raise capi.GnnxError(-2, "spmm_typed_bwd", f"out must be float32 {(n_rows, F)}")
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, F, device=dM.device, tag="reduce")
+    capi.call("gnnx_spmm_csr_typed_bwd_f32", n_rows, int(dM.shape[0]), F, nnz, R, B, _ptr(rowptr_t), _ptr(colidx_t) if nnz else None,
+              _ptr(etype_t) if nnz else None, _ptr(vals_t) if nnz else None, _ptr(coeff), _ptr(dM) if dM.numel() else None, _ld(dM),
+              float(beta), _ptr(out) if out.numel() else None, _ld(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def _entry_type_order(etype, n_types):
+    """(order, type_ptr) of a per-entry relation vector: the entries sorted by type (stable: ascending position inside a type) as
+    int32 [nnz], and the int32 [R + 1] offsets of each type's run -- what typed_coeff_grad sums over.  Built once per graph."""
+    order = torch.argsort(etype.long(), stable=True).to(torch.int32)
+    counts = torch.bincount(etype.long(), minlength=int(n_types))
+    ptr = torch.zeros(int(n_types) + 1, dtype=torch.int64, device=etype.device)
+    ptr[1:] = torch.cumsum(counts, 0)
+    return order, ptr.to(torch.int32)
+
+
+def typed_coeff_grad(rowptr, colidx, etype, dM, X, n_types, coeff, vals=None, type_order=None, out=None):
+    """dC [R, B], the gradient of spmm_typed(..., coeff) with respect to coeff: gnnx_typed_coeff_grad_f32 writes the per-entry slab
+    dots D[p, b] = vals[p] * <dM[i_p, slab b], X[colidx[p]]>, then dC[r] is the sum of the rows of D whose entry has type r --
+    gather_rows through the type-sorted entry order and segment_pool(..., "sum") over the type offsets, both deterministic.
+    type_order: g.type_order of set_edge_type, kept per graph (CsrGraph.type_order); built here without one.  out: where dC is written."""
+    n_rows, nnz, R, B = _typed_args("typed_coeff_grad", rowptr, colidx, etype, n_types, coeff, vals)
+    if coeff is None:
+        raise capi.GnnxError(-1, "typed_coeff_grad", "one-hot mode has no coefficients")
+    F = int(X.shape[1])
+    if X.dtype != torch.float32 or dM.dtype != torch.float32 or tuple(dM.shape) != (n_rows, B * F):
+        raise capi.GnnxError(-2, "typed_coeff_grad", f"dM must be float32 {(n_rows, B * F)} and X float32 [n_cols, {F}]")
+    D = torch.empty((nnz, B), dtype=torch.float32, device=X.device)
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, B, device=X.device, tag="reduce")
+    capi.call("gnnx_typed_coeff_grad_f32", n_rows, int(X.shape[0]), F, nnz, R, B, _ptr(rowptr), _ptr(colidx) if nnz else None,
+              _ptr(etype) if nnz else None, _ptr(vals) if nnz else None, _ptr(dM) if dM.numel() else None, _ld(dM),
+              _ptr(X) if X.numel() else None, _ld(X), _ptr(D) if nnz else None, _ptr(ws), ws.numel(), _stream())
+    order, ptr = type_order if type_order is not None else _entry_type_order(etype, R)
+    dC, _ = segment_pool(ptr, gather_rows(D, order), "sum", out=out)
+    return dC
 
 
 def transpose(X, out=None):
@@ -2931,6 +3063,115 @@ class GineStack(_Stack):
             if l == 0:
                 return dh
             G = relu_mask(h, dh, out=self._tmp(("G", l), (n, d0)))               # h = relu output of the layer below
+            colsum(G, out=self.db[l - 1])
+        return G
+
+
+class RgcnStack(_Stack):
+    """L R-GCN layers (Schlichtkrull et al. 2018) with the surface of SageStack, on a graph whose entries carry a relation type
+    (g.set_edge_type), R = n_relations:
+        M = spmm_typed(h) [n, B d_l]: slab b = sum_j w_ijb h_j over the stored columns j of row i;   h' = act( h W_0^T + M V^T + b ),
+    ReLU between layers, none after the last.  Without n_bases B = R, slab r sums the neighbours of relation r (one-hot mode) and
+    V = [W_1 | .. | W_R] holds a weight per relation; with n_bases B = n_bases, w_ijb = C[r_ij, b] * norm_ij and V = [V_1 | .. | V_B]
+    the bases, W_r = sum_b C[r, b] V_b.  norm="mean": norm_ij = 1 / |N_r(i)| (g.typed_norm); "sum": no weight.  M is ONE spmm_typed
+    call: every neighbour row is gathered once, no [n R, d] or per-relation intermediate exists.  Backward per layer: dV = G^T M,
+    dM = G V and dW_0 = G^T h (gemm), dh = G W_0 + spmm_typed_bwd(dM) on CSR(A^T) through g.entry_type_t -- which refuses what
+    attention_map refuses -- dC = typed_coeff_grad(dM, h), db by colsum.  Parameters W_0, V, b and, with n_bases, C [R, B] per layer.
+    forward / backward / step / train_step / evaluate / grad_buffer / on_graph, the link_* calls, and use under GraphClassifier /
+    on_batch (the types travel with the batch).  Every operation is a C-ABI call; no atomics on any value; the same bits every run."""
+
+    def __init__(self, g, dims, n_relations, n_bases=None, norm="mean", seed=0, device="cuda"):
+        if norm not in ("mean", "sum"):
+            raise ValueError(f"norm must be 'mean' or 'sum', got {norm!r}")
+        if n_bases is not None and int(n_bases) < 1:
+            raise ValueError("n_bases must be positive")
+        self.dims, self.n_relations, self.norm = list(dims), int(n_relations), norm
+        self.n_bases = None if n_bases is None else int(n_bases)
+        self.n_slabs = B = self.n_relations if n_bases is None else self.n_bases
+        L = len(dims) - 1
+        self._bind(g)
+        self.W_0 = [uniform_pm1(seed + 3 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.V = [uniform_pm1(seed + 3 * l + 1, (dims[l + 1], B * dims[l]), scale=(B * dims[l]) ** -0.5, device=device) for l in range(L)]
+        self.C = [] if n_bases is None else [uniform_pm1(seed + 3 * l + 2, (self.n_relations, B), device=device) for l in range(L)]
+        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
+        self.dW_0, self.dV, self.dC = ([torch.zeros_like(w) for w in ws] for ws in (self.W_0, self.V, self.C))
+        self.db = [torch.zeros_like(b) for b in self.b]
+        self._saved = None
+        self._buf = {}
+        self._opt = [None]
+
+    def _bind(self, g):
+        """What the stack holds of the graph itself: the entry types and weights of both patterns and the type-sorted entry order."""
+        if getattr(g, "entry_type", None) is None:
+            raise capi.GnnxError(-1, "RgcnStack", "the graph has no relation types (g.set_edge_type(src, dst, etype, n_relations))")
+        if g.n_relations != self.n_relations:
+            raise capi.GnnxError(-2, "RgcnStack", f"the graph has {g.n_relations} relations, the stack was built for {self.n_relations}")
+        self.g = g
+        self.etype, self.etype_t = g.entry_type, g.entry_type_t
+        self.vals, self.vals_t = (g.typed_norm, g.typed_norm_t) if self.norm == "mean" else (None, None)
+        return self
+
+    def params(self):
+        return self.W_0 + self.V + self.b + self.C
+
+    def grads(self):
+        return self.dW_0 + self.dV + self.db + self.dC
+
+    def on_graph(self, g):
+        """This stack on another typed graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch
+        buffers."""
+        if g.n != self.g.n:
+            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
+        return self._view(share_buf=True)._bind(g)
+
+    def _coeff(self, l):
+        return self.C[l] if self.C else None
+
+    def forward(self, X):
+        L, g, B = len(self.W_0), self.g, self.n_slabs
+        saved, h = [], X
+        for l in range(L):
+            d0, d1 = self.dims[l], self.dims[l + 1]
+            M = spmm_typed(g.rowptr, g.colidx, self.etype, h, self.n_relations, coeff=self._coeff(l), vals=self.vals,
+                           out=self._tmp(("M", l), (g.n, B * d0)))
+            Z = gemm(h, self.W_0[l], transB=True, out=self._tmp(("Z", l), (g.n, d1)))
+            gemm(M, self.V[l], transB=True, out=Z, beta=1.0)
+            Y = self._tmp(("Y", l), (g.n, d1))
+            bias_add(Z, self.b[l], out=Y)
+            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
+                bn_relu_fwd(Y, relu=True, out=Y)
+            saved.append((h, M))
+            h = Y
+        self._saved = saved
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """The gradient of every parameter from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        L, g, B = len(self.W_0), self.g, self.n_slabs
+        G = dOut
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            d0 = self.dims[l]
+            h, M = self._saved[l]
+            gemm(G, h, transA=True, out=self.dW_0[l])
+            gemm(G, M, transA=True, out=self.dV[l])
+            last = l == 0 and not input_grad
+            if last and not self.C:
+                return None
+            dM = gemm(G, self.V[l], out=self._tmp(("dM", l), (g.n, B * d0)))
+            if self.C:
+                typed_coeff_grad(g.rowptr, g.colidx, self.etype, dM, h, self.n_relations, self.C[l], vals=self.vals,
+                                 type_order=g.type_order, out=self.dC[l])
+            if last:
+                return None
+            dh = gemm(G, self.W_0[l], out=self._tmp(("dh", l), (g.n, d0)))                       # through the vertex itself
+            spmm_typed_bwd(g.rowptr_t, g.colidx_t, self.etype_t, dM, self.n_relations, d0, coeff=self._coeff(l), vals_t=self.vals_t,
+                           out=dh, beta=1.0)                                                      # + through its neighbourhood
+            if l == 0:
+                return dh
+            G = relu_mask(h, dh, out=self._tmp(("G", l), (g.n, d0)))                             # h = relu output of the layer below
             colsum(G, out=self.db[l - 1])
         return G
 

@@ -1103,6 +1103,80 @@ int gnnx_spmm_csr_edge_bwd_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, i
 int gnnx_csr_entry_edges(int32_t n_rows, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_src, const int32_t *d_dst,
                          int64_t n_edges, int32_t *d_eidx, int32_t *d_missing, void *stream);
 
+/* ------------------------------------------------------------------ relation-typed aggregation --------------- */
+/*
+ * Aggregation over edges that carry a RELATION TYPE -- R-GCN (Schlichtkrull et al. 2018) and the knowledge-graph encoders built on it:
+ * one gather of every neighbour row feeding B output slabs, its backward to X and the per-entry dots of the coefficient gradient.  The
+ * reference has no typed edges; the contract is this comment, restated in NumPy by tests/typed_ref.py.
+ *
+ * Notation: t_p = etype[p] in [0, R), c_p = colidx[p], v_p = vals[p] (1 with d_vals == NULL), R = n_types, B = n_slabs, F = n_feat.
+ * etype is TRUSTED like colidx: a type outside [0, R) is the caller's error.
+ *
+ * Forward, gnnx_spmm_csr_typed_f32.  M: [n_rows, B * F] ld ldm, slab b in columns b F .. (b + 1) F - 1 (the following dense product
+ * reads it as one matrix).  M is written with beta = 0 semantics: it is never read, whatever it held is overwritten, columns beyond
+ * B * F are not touched.
+ *   Basis mode, d_C a float32 [R, B] table, row-major:
+ *     M[i, b F + f] = sum over the entries p of row i of (w_pb * X[c_p, f]),   w_pb = C[t_p, b] * v_p
+ *     -- w_pb is ONE rounding (C[t_p, b] itself, no multiply, with d_vals == NULL); the product w_pb * x is rounded before the add;
+ *     nothing is contracted.  A zero coefficient multiplies like any other: 0 * inf is NaN in that slab.
+ *   One-hot mode, d_C == NULL, which requires B == R:
+ *     entry p contributes v_p * X[c_p, f] (X[c_p, f] itself, no multiply, with d_vals == NULL) to slab t_p ONLY.  It does not touch the
+ *     other slabs -- there is no 0 * x -- so an inf or NaN among one relation's neighbours stays in that relation's slab.
+ *   ORDER of every sum, with S = 4096, exactly that of gnnx_spmm_csr_edge_f32: the row is cut into segments of S consecutive entries
+ *   (the last may be short); a segment is summed by ONE accumulator per output element starting from +0 and walking the segment from its
+ *   LAST entry to its FIRST; the row sum is ((seg_0 + seg_1) + seg_2) + ... in ascending segment order.  In one-hot mode the entries of
+ *   other types are simply absent from a slab's chain (a segment without an entry of the type contributes its +0).  An empty row, or a
+ *   slab that no entry reaches, is +0.  No atomics on any value: the bits are a function of the inputs alone, however rows, slabs,
+ *   segments and features map to lanes.
+ *
+ * Backward to X, gnnx_spmm_csr_typed_bwd_f32.  It runs on the pattern it is handed: the caller passes CSR(A^T) with etype and vals
+ * permuted through the transpose map (gnnx_csr_transpose_map).  dM: [n_cols_t, B * F] ld ldm; dX: [n_rows_t, F] ld lddx.
+ *     dX[j, f] = (beta ? dX[j, f] : nothing) + sum over the entries q of row j of u_q,        beta in {0, 1}
+ *   Basis mode:   u_q = w_q0 * dM[c_q, f];  then u_q = u_q + w_qb * dM[c_q, b F + f] for b = 1 .. B - 1 ascending -- each product
+ *                 rounded, then each add; w_qb as in the forward.
+ *   One-hot mode: u_q = v_q * dM[c_q, t_q F + f], the element itself with d_vals_t == NULL.
+ *   The entry order is the forward's (segments of S from the last entry to the first, segment sums ascending).
+ *
+ * Coefficient gradient, gnnx_typed_coeff_grad_f32 (basis mode only), on CSR(A) with i_p the row of entry p:
+ *     D[p, b] = v_p * dot(dM[i_p, b F .. (b + 1) F - 1], X[c_p, 0 .. F - 1]),        D: float32 [nnz, B], entry-major, dense
+ *   The dot has the order of the edge scores (gnnx_sddmm_csr_f32): Q = ceil(F / 4) chunks of four features, G = min(64, pow2 >= Q)
+ *   lanes, lane l adds the products of chunks l, l + G, ... in ascending f to ONE accumulator from +0, each product rounded before the
+ *   add, the G accumulators meet in an xor butterfly (s = 1, 2, .., G / 2).  v_p is applied last as one rounding, not at all with
+ *   d_vals == NULL.  dC[r, b] is the sum of D[p, b] over the entries of type r: a deterministic segment sum over a type-sorted entry
+ *   order (gnnx_gather_rows_f32, gnnx_segment_pool_f32), which the caller builds once per graph.
+ *
+ * All three calls are asynchronous on `stream` (a chain of launches on that one stream); they allocate nothing and synchronise nothing
+ * and TRUST the CSR and nnz (= rowptr[n_rows]); any CSR is taken, duplicate columns in a row included.  GNNX_ERR_INVALID_ARG before any
+ * device call: negative sizes, nnz >= 2^31, ldx < F, ldm < B * F, lddx < F, a beta other than 0 or 1, d_C == NULL with B != R, R <= 0 or
+ * B <= 0 with entries present, a null pointer (d_vals may be NULL, d_C in the two aggregations; the per-entry inputs may be NULL with
+ * nnz == 0).  GNNX_ERR_UNSUPPORTED: B * F >= 2^31, or a coefficient table that does not fit 64 KiB of LDS -- R * min(8, pow2 >= B)
+ * words in the forward, R * B words in the backward.  n_rows == 0 or a zero output width returns GNNX_OK and writes nothing; nnz == 0
+ * still writes the per-row outputs of the two aggregations.  The workspace is the neighbourhood reductions': NULL or fewer bytes than
+ * gnnx_spmm_csr_reduce_workspace(n_rows, nnz, width) is GNNX_ERR_WORKSPACE with nothing written, with width = B * F for the forward, F
+ * (and n_rows_t) for the backward and B for the coefficient gradient.  It holds nothing between calls and may sit at any address.
+ *
+ * Kernels (gnnx_typed.hip): rows of at most S entries take lane groups of 4 .. 64 lanes per row, one 16-byte piece per lane, feature
+ * tiles in the grid's y; a lane keeps a register tile of 1, 2, 4 or 8 slab accumulators, more than 8 slabs run as tiles of 8 in the
+ * grid's z.  A group fetches (c, t, v) of its entries with one coalesced load each, hands them out by shuffle and requests four X rows
+ * before the first multiply; the tile's columns of C are staged once per workgroup in LDS and read at a group-uniform address.  A
+ * one-hot pass gathers X only for the entries whose type falls in its tile.  n_feat % 4 != 0, or a pointer or leading dimension that
+ * is not 16-byte aligned, takes scalar lanes with the same bits.  Longer rows are listed in the workspace by the row kernel (a counter
+ * atomic reserves slots, never an atomic on a value), a fixed grid strides over their segments and a combine kernel adds the segment
+ * sums in ascending order.  The backward and the coefficient gradient take the slabs four at a time: the backward chains them per entry
+ * across the passes in registers, the coefficient gradient keeps a row's dM chunks of four slabs in registers (more slabs in the grid's
+ * y) and reduces the four partials by butterfly.
+ */
+int gnnx_spmm_csr_typed_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t nnz, int32_t n_types, int32_t n_slabs,
+                            const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_etype, const float *d_vals, const float *d_C,
+                            const float *d_X, int64_t ldx, float *d_M, int64_t ldm, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_spmm_csr_typed_bwd_f32(int32_t n_rows_t, int32_t n_cols_t, int32_t n_feat, int64_t nnz, int32_t n_types, int32_t n_slabs,
+                                const int32_t *d_rowptr_t, const int32_t *d_colidx_t, const int32_t *d_etype_t, const float *d_vals_t,
+                                const float *d_C, const float *d_dM, int64_t ldm, float beta, float *d_dX, int64_t lddx, void *d_workspace,
+                                size_t workspace_bytes, void *stream);
+int gnnx_typed_coeff_grad_f32(int32_t n_rows, int32_t n_cols, int32_t n_feat, int64_t nnz, int32_t n_types, int32_t n_slabs,
+                              const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_etype, const float *d_vals, const float *d_dM,
+                              int64_t ldm, const float *d_X, int64_t ldx, float *d_D, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ graph readout --------------- */
 /*
  * One row of output per GRAPH of a batch: the SUM, MEAN or MAX of each segment of consecutive rows of X, and the backward that hands a
