@@ -160,6 +160,12 @@ _SIGS = {
                                         _sz, _vp],
     "gnnx_edge_softmax_bwd_csr_heads_f32": [_i32, _i32, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp,
                                             _i64, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_gat_aggregate_csr_f32": [_i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, C.c_int, _vp, _i64, _vp,
+                                   _vp, _vp, _sz, _vp],
+    "gnnx_gat_aggregate_bwd_rows_csr_f32": [_i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _i64,
+                                            _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
+    "gnnx_gat_aggregate_bwd_cols_csr_f32": [_i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp,
+                                            _vp, _f32, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
     "gnnx_gatv2_scores_csr_f32": [_i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _vp, _i64, _vp],
     "gnnx_gatv2_scores_bwd_csr_f32": [_i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _f32, _vp, _i64,
                                       _vp, _i64, _vp],

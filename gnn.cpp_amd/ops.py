@@ -1246,6 +1246,111 @@ def edge_softmax_heads_bwd(rowptr, colidx, n_heads, alpha, dalpha, scores=None, 
     return dt, drow
 
 
+def _gat_fused_args(where, rowptr, colidx, n_heads, rowterm, colterm, n_cols, mats):
+    """What the three fused attention calls share: the sizes, the two terms as (pointer, stride) and the checked [rows, H*D] matrices.
+    mats: (name, tensor, rows) triples; the first one fixes H*D."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    if mats[0][1].dim() != 2:
+        raise capi.GnnxError(-2, where, f"{mats[0][0]} must be a 2-D matrix, got {tuple(mats[0][1].shape)}")
+    F = int(mats[0][1].shape[1])
+    D = _heads_of(mats[0][1], n_heads, where)
+    for name, t, rows in mats:
+        _gat_matrix(where, name, t, rows, F)
+    if rowterm is None or colterm is None:
+        raise capi.GnnxError(-1, where, "rowterm and colterm are both required")
+    # the column side gathers rowterm by entry: its rows are the pattern's columns
+    rt, rs = _edge_terms_heads(rowterm, n_cols if where == "gat_aggregate_bwd_cols" else n_rows, n_heads, "rowterm")
+    ct, cs = _edge_terms_heads(colterm, n_rows if where == "gat_aggregate_bwd_cols" else n_cols, n_heads, "colterm")
+    return n_rows, nnz, D, rt, rs, ct, cs
+
+
+def _gat_matrix(where, name, t, rows, F):
+    if t.dim() != 2 or tuple(t.shape) != (rows, F) or t.dtype != torch.float32 or t.stride(1) != 1 or not t.is_cuda:
+        raise capi.GnnxError(-2, where, f"{name} must be a row-major float32 [{rows}, {F}] matrix on the device, got {tuple(t.shape)} {t.dtype}")
+
+
+def _gat_stat(t, n, H, what, where):
+    if t.dtype != torch.float32 or tuple(t.shape) != (n, H) or not t.is_contiguous():
+        raise capi.GnnxError(-2, where, f"{what} must be a contiguous float32 [{n}, {H}] array, got {tuple(t.shape)} {t.dtype}")
+    return _ptr(t)
+
+
+def gat_aggregate(rowptr, colidx, X, n_heads, rowterm, colterm, negative_slope=0.2, bias=None, relu_out=False, out=None, want_stats=True,
+                  stats_out=None):
+    """gnnx_gat_aggregate_csr_f32: a GAT layer's softmax and aggregation in one gather, no [nnz, H] array --
+        Y[i, hD + j] = act( sum_p alpha_p X[c_p, hD + j] + bias ),  alpha = softmax over row i of leaky_relu(rowterm[i, h] + colterm[c_p, h]).
+    X: [n_cols, H*D]; rowterm [n_rows, H], colterm [n_cols, H] (the halves of one [n, 2H] matrix serve).  Returns (Y, rowmax, rowsum) with
+    the statistics as [n_rows, H] -- the backward calls need both; stats_out = (rowmax, rowsum) to write them into the caller's arrays -- or Y
+    alone with want_stats=False."""
+    n_cols = int(X.shape[0])
+    n_rows, nnz, D, rt, rs, ct, cs = _gat_fused_args("gat_aggregate", rowptr, colidx, n_heads, rowterm, colterm, n_cols, [("X", X, n_cols)])
+    dev = X.device
+    if out is None:
+        out = torch.empty((n_rows, n_heads * D), dtype=torch.float32, device=dev)
+    _gat_matrix("gat_aggregate", "out", out, n_rows, n_heads * D)
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (n_heads * D,) or not bias.is_contiguous()):
+        raise capi.GnnxError(-2, "gat_aggregate", f"bias must be a contiguous float32 [{n_heads * D}] vector, got {tuple(bias.shape)} {bias.dtype}")
+    rowmax, rowsum = stats_out if stats_out is not None else (None, None)
+    if want_stats and stats_out is None:
+        rowmax, rowsum = (torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) for _ in range(2))
+    if rowmax is not None:
+        _gat_stat(rowmax, n_rows, n_heads, "rowmax", "gat_aggregate"), _gat_stat(rowsum, n_rows, n_heads, "rowsum", "gat_aggregate")
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, n_heads * (D + 1), device=dev, tag="gat_fused")
+    capi.call("gnnx_gat_aggregate_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, n_heads, D, rt, rs, ct, cs,
+              float(negative_slope), _ptr(X), _ld(X), _ptr(bias), int(bool(relu_out)), _ptr(out), _ld(out), _ptr(rowmax), _ptr(rowsum),
+              _ptr(ws), ws.numel(), _stream())
+    return (out, rowmax, rowsum) if rowmax is not None else out
+
+
+def gat_aggregate_bwd_rows(rowptr, colidx, G, X, Y, n_heads, rowterm, colterm, rowmax, rowsum, negative_slope=0.2, bias=None,
+                           drowterm_out=None, dot_out=None):
+    """gnnx_gat_aggregate_bwd_rows_csr_f32, on the forward pattern: (drowterm [n_rows, H], dot [n_rows, H]) from G = dL/dY0 (ReLU mask
+    applied), X, the forward's Y, bias, terms and statistics.  drowterm_out: a float32 [n_rows, H] view with unit stride along the heads,
+    e.g. the left half of an [n, 2H] buffer.  dot goes to gat_aggregate_bwd_cols."""
+    where = "gat_aggregate_bwd_rows"
+    n_cols = int(X.shape[0])
+    n_rows = int(rowptr.numel() - 1)
+    n_rows, nnz, D, rt, rs, ct, cs = _gat_fused_args(where, rowptr, colidx, n_heads, rowterm, colterm, n_cols,
+                                                     [("G", G, n_rows), ("X", X, n_cols), ("Y", Y, n_rows)])
+    dev = X.device
+    drow = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if drowterm_out is None else drowterm_out
+    dp, drs = _edge_terms_heads(drow, n_rows, n_heads, "drowterm_out")
+    dot = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if dot_out is None else dot_out
+    _gat_stat(dot, n_rows, n_heads, "dot_out", where)
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, n_heads * (D + 1), device=dev, tag="gat_fused")
+    capi.call("gnnx_gat_aggregate_bwd_rows_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, n_heads, D, rt, rs, ct,
+              cs, float(negative_slope), _ptr(G), _ld(G), _ptr(X), _ld(X), _ptr(Y), _ld(Y), _ptr(bias),
+              _gat_stat(rowmax, n_rows, n_heads, "rowmax", where), _gat_stat(rowsum, n_rows, n_heads, "rowsum", where), dp, drs, _ptr(dot),
+              _ptr(ws), ws.numel(), _stream())
+    return drow, dot
+
+
+def gat_aggregate_bwd_cols(rowptr_t, colidx_t, G, X, n_heads, rowterm, colterm, rowmax, rowsum, dot, negative_slope=0.2, out=None, beta=0.0,
+                           dcolterm_out=None):
+    """gnnx_gat_aggregate_bwd_cols_csr_f32, on the TRANSPOSED pattern (row c, entries i): (dX [n_c, H*D], dcolterm [n_c, H]) with
+    dX[c] = beta*dX[c] + sum_i alpha_ic G[i].  G, rowterm, rowmax, rowsum and dot belong to the forward's rows (this pattern's columns), X
+    and colterm to its columns (this pattern's rows).  dcolterm_out: e.g. the right half of an [n, 2H] buffer."""
+    where = "gat_aggregate_bwd_cols"
+    n_cols = int(G.shape[0])
+    n_rows = int(rowptr_t.numel() - 1)
+    n_rows, nnz, D, rt, rs, ct, cs = _gat_fused_args(where, rowptr_t, colidx_t, n_heads, rowterm, colterm, n_cols,
+                                                     [("X", X, n_rows), ("G", G, n_cols)])
+    dev = X.device
+    if out is None:
+        if beta:
+            raise capi.GnnxError(-2, where, "beta = 1 adds onto `out`, which was not given")
+        out = torch.empty((n_rows, n_heads * D), dtype=torch.float32, device=dev)
+    _gat_matrix(where, "out", out, n_rows, n_heads * D)
+    dcol = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if dcolterm_out is None else dcolterm_out
+    dp, dcs = _edge_terms_heads(dcol, n_rows, n_heads, "dcolterm_out")
+    ws, _ = _scratch("gnnx_spmm_csr_reduce_workspace", n_rows, nnz, n_heads * (D + 1), device=dev, tag="gat_fused")
+    capi.call("gnnx_gat_aggregate_bwd_cols_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr_t), _ptr(colidx_t) if nnz else None, n_heads, D, rt, rs,
+              ct, cs, float(negative_slope), _ptr(G), _ld(G), _ptr(X), _ld(X), _gat_stat(rowmax, n_cols, n_heads, "rowmax", where),
+              _gat_stat(rowsum, n_cols, n_heads, "rowsum", where), _gat_stat(dot, n_cols, n_heads, "dot", where), float(beta), _ptr(out),
+              _ld(out), dp, dcs, _ptr(ws), ws.numel(), _stream())
+    return out, dcol
+
+
 REDUCE_OPS = {"max": 0, "min": 1}   # GNNX_REDUCE_MAX / GNNX_REDUCE_MIN
 
 
@@ -2435,9 +2540,11 @@ class _AttentionStack(_Stack):
             raise ValueError(f"layer {bad[0]}: {dims[bad[0] + 1]} features do not split into {heads[bad[0]]} heads")
         return [int(k) for k in heads]
 
+    fused = False   # GatStack(fused=True): no per-entry array, hence no transpose map
+
     def _bind(self, g):
         self.g = g
-        self.map_t = g.attention_map()
+        self.map_t = None if self.fused else g.attention_map()
         return self
 
     def _aggregate(self, l, X, vals, transposed=False, **epilogue):
@@ -2487,9 +2594,19 @@ class GatStack(_AttentionStack):
         rp, ci, _ = csr_from_coo_weighted(src, dst, w, n, DIAG_FILL)          # the values are discarded
         rp_t, ci_t, _ = csr_from_coo_weighted(dst, src, w, n, DIAG_FILL)
         g = CsrGraph(n, rp, ci, rp_t, ci_t)                                   # g.make_plans(...) for a power-law graph
-    A vertex without entries (only possible without the diagonal) has an empty softmax: its row is the bias alone."""
+    A vertex without entries (only possible without the diagonal) has an empty softmax: its row is the bias alone.
 
-    def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda", heads=None):
+    fused=True takes the three fused calls instead (gat_aggregate, gat_aggregate_bwd_rows, gat_aggregate_bwd_cols; include/gnnx.h "fused
+    graph attention"): a layer is linear_fwd -> ER -> gat_aggregate with the bias and the ReLU in its epilogue, and the backward recomputes
+    alpha from ER and the saved row statistics instead of carrying alpha, dalpha, dt and their transposed copies.  No [nnz, H] array
+    exists and g.attention_map() is never built, so this path also takes a RELABELLED graph and one whose map was never built (it still
+    needs the transposed CSR).  The sums run in the fused calls' order (ascending, segments of 4096), so logits and gradients agree with
+    fused=False to rounding, not bit for bit; without the keyword the stack runs exactly the path above."""
+
+    def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda", heads=None, fused=False):
+        self.fused = bool(fused)
+        if self.fused and (g.rowptr_t is None or g.colidx_t is None):
+            raise capi.GnnxError(-1, "GatStack", "the graph has no transposed CSR (from_coo(..., transpose=True))")
         self._bind(g)
         self.dims = list(dims)
         self.negative_slope = float(negative_slope)
@@ -2531,6 +2648,16 @@ class GatStack(_AttentionStack):
         saved, h = [], X
         for l in range(L):
             H = linear_fwd(h, self.W[l])
+            if self.fused:
+                Hh = self.heads[l]
+                ER = gemm(H, self.A[l], transB=True)
+                n = self.g.n   # the statistics wait for the backward in the stack's buffers, one pair per layer; Y is the layer's output
+                Y, rowmax, rowsum = gat_aggregate(self.g.rowptr, self.g.colidx, H, Hh, ER[:, :Hh], ER[:, Hh:], self.negative_slope,
+                                                  bias=self.b[l], relu_out=l + 1 < L,
+                                                  stats_out=(self._tmp(("rowmax", l), (n, Hh)), self._tmp(("rowsum", l), (n, Hh))))
+                saved.append((h, H, ER, rowmax, rowsum, Y))
+                h = Y
+                continue
             ER, alpha = self.attention(H, l)
             # the ReLU between layers rides in the aggregation's epilogue: only relu(Z) is stored (its sign is the mask)
             Y = self._aggregate(l, H, alpha, bias=self.b[l], relu_out=l + 1 < L)
@@ -2547,17 +2674,17 @@ class GatStack(_AttentionStack):
         if not have_last_bias_grad:
             colsum(G, out=self.db[L - 1])
         for l in reversed(range(L)):
-            h, H, ER, alpha, _ = self._saved[l]
             Hh = self.heads[l]
-            dalpha = self._vals_grad(l, G, H)
             dER = self._tmp(("dER", Hh), (n, 2 * Hh))                                     # left half: del, right half: der
-            dt, _ = edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, rowterm=ER[:, :Hh], colterm=ER[:, Hh:],
-                                           negative_slope=self.negative_slope, drowterm_out=dER[:, :Hh])
-            vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh))
-            self._to_transposed(dt, vals_t)
-            csr_rowsum_heads(g.rowptr_t, vals_t, out=dER[:, Hh:])                         # der: what flows back to a column's vertex
-            self._to_transposed(alpha, vals_t)
-            dH = self._aggregate(l, G, vals_t, transposed=True)                           # through the aggregated rows
+            if self.fused:
+                h, H, ER, rowmax, rowsum, Y = self._saved[l]
+                _, dot = gat_aggregate_bwd_rows(g.rowptr, g.colidx, G, H, Y, Hh, ER[:, :Hh], ER[:, Hh:], rowmax, rowsum, self.negative_slope,
+                                                bias=self.b[l], drowterm_out=dER[:, :Hh], dot_out=self._tmp(("dot", Hh), (n, Hh)))
+                dH, _ = gat_aggregate_bwd_cols(g.rowptr_t, g.colidx_t, G, H, Hh, ER[:, :Hh], ER[:, Hh:], rowmax, rowsum, dot,
+                                               self.negative_slope, out=self._tmp(("dH", l), tuple(H.shape)), dcolterm_out=dER[:, Hh:])
+            else:
+                dH = self._backward_entries(l, G, dER)
+            h, H = self._saved[l][0], self._saved[l][1]
             gemm(dER, self.A[l], out=dH, beta=1.0)                                        # + [del der] . A, through ER
             gemm(dER, H, transA=True, out=self.dA[l])
             if Hh > 1:   # the entries outside the blocks are not parameters (one head: the mask is all ones)
@@ -2568,6 +2695,21 @@ class GatStack(_AttentionStack):
             else:   # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue
                 G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
         return G
+
+    def _backward_entries(self, l, G, dER):
+        """The per-entry chain of one layer's attention backward: both halves of dER written in place; returns dH through the aggregated
+        rows."""
+        g = self.g
+        h, H, ER, alpha, _ = self._saved[l]
+        Hh = self.heads[l]
+        dalpha = self._vals_grad(l, G, H)
+        dt, _ = edge_softmax_heads_bwd(g.rowptr, g.colidx, Hh, alpha, dalpha, rowterm=ER[:, :Hh], colterm=ER[:, Hh:],
+                                       negative_slope=self.negative_slope, drowterm_out=dER[:, :Hh])
+        vals_t = self._tmp(("vals_t", Hh), (g.nnz, Hh))
+        self._to_transposed(dt, vals_t)
+        csr_rowsum_heads(g.rowptr_t, vals_t, out=dER[:, Hh:])                         # der: what flows back to a column's vertex
+        self._to_transposed(alpha, vals_t)
+        return self._aggregate(l, G, vals_t, transposed=True)                         # through the aggregated rows
 
 
 class Gatv2Stack(_AttentionStack):

@@ -852,6 +852,68 @@ int gnnx_edge_softmax_bwd_csr_heads_f32(int32_t n_rows, int32_t n_cols, int64_t 
                                         int64_t lda, const float *d_dalpha, int64_t ldd, float *d_dt, int64_t ldt, float *d_drowterm,
                                         int64_t drowterm_stride, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ fused graph attention -------- */
+/*
+ * A GATv1 layer's score, softmax and aggregation -- and their backward -- WITHOUT any per-entry array: the score of an entry is a
+ * function of two per-vertex scalars per head, so alpha is recomputed where it is needed from [n, H] arrays.  H = n_heads heads of
+ * width D = head_dim, F = H D; feature matrices are [rows, F], head h in columns h D .. h D + D - 1; rowterm / colterm are the edge
+ * softmax's terms, element h of row i at term[i * stride + h] (stride >= H: the halves of one [n, 2H] matrix serve).  Every operation
+ * below is ONE separately rounded fp32 operation (no fused multiply-add, no packed pair); expf is the device library's.
+ *
+ * gnnx_gat_aggregate_csr_f32 -- forward.  For row i, head h, entry p with column c:
+ *     t_p = rowterm[i, h] + colterm[c, h];  e_p = t_p > 0 ? t_p : t_p * slope;  m = max_p e_p;  x_p = expf(e_p - m)
+ *   (the edge softmax's definitions: m, and every x_p, carry the bits gnnx_edge_softmax_csr_heads_f32 gives);
+ *     z = sum_p x_p;  N[f] = sum_p (x_p * X[c, f]);  Y0[f] = N[f] / z  (one IEEE division per output element);
+ *     Y[i, f] = Y0[f] + bias[f], then where(Y > 0, Y, 0) with relu_out != 0.  bias: [F] or NULL.
+ *   d_rowmax / d_rowsum: [n_rows, H] contiguous, m and z, each may be NULL.  An empty row: -inf, +0 and Y = act(bias).
+ * gnnx_gat_aggregate_bwd_rows_csr_f32 -- backward, row side, on the FORWARD pattern.  G = dL/dY0 [n_rows, F] (the caller has applied
+ *   the ReLU mask), X, Y (the forward's output), bias (the forward's, or NULL), the two terms, rowmax, rowsum:
+ *     dot[i, h] = sum_{f in head h} G[i, f] * (Y[i, f] - bias[f])   ( = sum_p alpha_p dalpha_p; the subtraction rounded first )
+ *     alpha_p = x_p / z;  dalpha_p = <G[i, head h], X[c, head h]>;  de_p = alpha_p * (dalpha_p - dot);  dt_p = t_p > 0 ? de_p : de_p * slope
+ *     drowterm[i * drowterm_stride + h] = sum_p dt_p  (+0 for an empty row);  d_dot: [n_rows, H] contiguous, an output.
+ * gnnx_gat_aggregate_bwd_cols_csr_f32 -- backward, column side, on the TRANSPOSED pattern (n_rows = its rows c, entries = the forward's
+ *   rows i).  rowterm, rowmax, rowsum, dot and G are indexed by the ENTRY (i), colterm and X by the ROW (c); alpha_ic and dt_ic by the
+ *   formulas above:
+ *     dX[c, f] = beta * dX[c, f] + sum_i (alpha_ic * G[i, f])   (beta 0 or 1);   dcolterm[c * dcolterm_stride + h] = sum_i dt_ic.
+ *
+ * ORDER, a function of the row length and of D alone.  Every sum over a row's entries (z, N, drowterm, dX, dcolterm): ONE accumulator
+ * per output element, from +0, over the entries of a segment of S = 4096 consecutive entries in ASCENDING order; the segments' sums are
+ * added ascending starting from the first (a row of d <= S entries is one segment).  Every dot product over a head (dot, dalpha): the
+ * SDDMM lane-group order with F := D (gnnx_sddmm_csr_f32), left operand G.  How rows, heads and features map to lanes is not in the
+ * result: two runs give the same bits, and the 16-byte path and the scalar-load path (D % 4 != 0, or a pointer / leading dimension
+ * off 16 bytes) give the same bits.  No atomics on any value (two counter atomics per row longer than S); no per-entry array and no
+ * transpose map is read or written.  rowsum does NOT carry the bits of the edge softmax's rowsum (whose order is the 64-lane one).
+ *
+ * Statuses, all before any HIP call: negative sizes, nnz >= 2^31, n_heads < 1, head_dim < 1, a term stride < H, a leading dimension
+ * < F, a beta other than 0 or 1, a null rowptr / term / required operand or output are GNNX_ERR_INVALID_ARG; head_dim > 512 (a lane
+ * holds at most two 16-byte chunks of its head) and more than 65535 passes of heads (a pass holds max(1, 64 / max(1, pow2 >= D / 4))
+ * heads) are GNNX_ERR_UNSUPPORTED; a workspace that is NULL or smaller than that query's answer is GNNX_ERR_WORKSPACE.  A refused call
+ * writes nothing.  WORKSPACE: all three calls take the neighbourhood reductions' workspace,
+ * gnnx_spmm_csr_reduce_workspace(n_rows, nnz, n_heads * (head_dim + 1)) bytes with the n_rows of the pattern the call runs on (the hub
+ * list and one partial per segment slot, head and feature fit its layout; no query of their own); it holds nothing between calls.  Asynchronous on `stream`; nothing is allocated or synchronised.
+ * X, G and the outputs must not alias.  The CSR and its column indices are trusted as in gnnx_spmm_csr_f32.
+ *
+ * Accuracy (tests/test_gpu_gat_fused.py, float64 reference from expf on; bar c * 2^-24 * sum of the absolute terms, c = the rounded
+ * operations on the longest chain + 4 for expf): worst observed fraction of the bar on the test pattern (rows of up to 12 293 entries)
+ * over all tested (H, D): rowsum 0.20, Y 0.16, dot 0.25, drowterm 0.054, dX 0.26, dcolterm 0.13.
+ */
+int gnnx_gat_aggregate_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, int32_t n_heads,
+                               int32_t head_dim, const float *d_rowterm, int64_t rowterm_stride, const float *d_colterm, int64_t colterm_stride,
+                               float negative_slope, const float *d_X, int64_t ldx, const float *d_bias, int relu_out, float *d_Y, int64_t ldy,
+                               float *d_rowmax, float *d_rowsum, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_gat_aggregate_bwd_rows_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                        int32_t n_heads, int32_t head_dim, const float *d_rowterm, int64_t rowterm_stride,
+                                        const float *d_colterm, int64_t colterm_stride, float negative_slope, const float *d_G, int64_t ldg,
+                                        const float *d_X, int64_t ldx, const float *d_Y, int64_t ldy, const float *d_bias, const float *d_rowmax,
+                                        const float *d_rowsum, float *d_drowterm, int64_t drowterm_stride, float *d_dot, void *d_workspace,
+                                        size_t workspace_bytes, void *stream);
+int gnnx_gat_aggregate_bwd_cols_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                                        int32_t n_heads, int32_t head_dim, const float *d_rowterm, int64_t rowterm_stride,
+                                        const float *d_colterm, int64_t colterm_stride, float negative_slope, const float *d_G, int64_t ldg,
+                                        const float *d_X, int64_t ldx, const float *d_rowmax, const float *d_rowsum, const float *d_dot, float beta,
+                                        float *d_dX, int64_t lddx, float *d_dcolterm, int64_t dcolterm_stride, void *d_workspace,
+                                        size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ dynamic attention scores (GATv2) ---- */
 /*
  * The score of GATv2 (Brody, Alon, Yahav, ICLR 2022): e(i, c) = a^T leaky_relu(W_l h_i + W_r h_c), the non-linearity INSIDE the sum.  The
