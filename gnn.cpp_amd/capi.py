@@ -166,6 +166,13 @@ _SIGS = {
                                             _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "gnnx_gat_aggregate_bwd_cols_csr_f32": [_i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp,
                                             _vp, _f32, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_attn_workspace": [_i32, _i64, _i32, _i32, C.POINTER(_sz)],
+    "gnnx_attn_csr_f32": [_i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                          _vp, _sz, _vp],
+    "gnnx_attn_bwd_rows_csr_f32": [_i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                   _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp],
+    "gnnx_attn_bwd_cols_csr_f32": [_i32, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                   _vp, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _vp, _sz, _vp],
     "gnnx_gatv2_scores_csr_f32": [_i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _vp, _i64, _vp],
     "gnnx_gatv2_scores_bwd_csr_f32": [_i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _f32, _vp, _i64,
                                       _vp, _i64, _vp],

@@ -1351,6 +1351,98 @@ def gat_aggregate_bwd_cols(rowptr_t, colidx_t, G, X, n_heads, rowterm, colterm, 
     return out, dcol
 
 
+def _attn_args(where, rowptr, colidx, n_heads, mats, E, eidx, scale):
+    """What the three dot-product attention calls share: the sizes, the checked [rows, H*D] matrices (mats: (name, tensor, rows) triples,
+    the first one fixes H*D), the edge rows with their index as C arguments, and the scale (default D ** -0.5)."""
+    n_rows, nnz = int(rowptr.numel() - 1), int(colidx.numel())
+    if mats[0][1].dim() != 2:
+        raise capi.GnnxError(-2, where, f"{mats[0][0]} must be a 2-D matrix, got {tuple(mats[0][1].shape)}")
+    F = int(mats[0][1].shape[1])
+    D = _heads_of(mats[0][1], n_heads, where)
+    for name, t, rows in mats:
+        _gat_matrix(where, name, t, rows, F)
+    edge = (None, 0, None, 0)
+    if E is not None:
+        _gat_matrix(where, "E", E, int(E.shape[0]), F)
+        if eidx is not None and (eidx.dtype != torch.int32 or tuple(eidx.shape) != (nnz,) or not eidx.is_contiguous()):
+            raise capi.GnnxError(-2, where, f"eidx must be a contiguous int32 [{nnz}] array, got {tuple(eidx.shape)} {eidx.dtype}")
+        edge = (_ptr(eidx) if nnz else None, int(E.shape[0]), _ptr(E), _ld(E))
+    elif eidx is not None:
+        raise capi.GnnxError(-2, where, "eidx without E")
+    return n_rows, nnz, F, D, edge, float(D ** -0.5 if scale is None else scale)
+
+
+def _attn_out(where, name, t, rows, F, dev, zero=False):
+    if t is None:
+        return (torch.zeros if zero else torch.empty)((rows, F), dtype=torch.float32, device=dev)
+    _gat_matrix(where, name, t, rows, F)
+    return t
+
+
+def attn_aggregate(rowptr, colidx, Q, K, V, n_heads, E=None, eidx=None, scale=None, out=None, stats_out=None):
+    """gnnx_attn_csr_f32: transformer attention over the stored entries of each row in one gather, no [nnz, .] array --
+        Y[i] = sum_p alpha_p (V[c_p] + E[e_p]),  alpha = softmax over row i of scale * <Q[i], K[c_p] + E[e_p]> per head.
+    Q: [n_rows, H*D]; K, V: [n_cols, H*D]; E: [edge rows, H*D] or None (no edge term); eidx: int32 [nnz] or None (e_p = p); any of the
+    matrices may be a column slab of a wider one.  scale defaults to D ** -0.5.  Returns (Y, rowmax, rowsum), the statistics as
+    [n_rows, H] (stats_out = (rowmax, rowsum) to write them into the caller's arrays); the backward calls need all three."""
+    where = "attn_aggregate"
+    n_cols = int(K.shape[0])
+    n_rows, nnz, F, D, (ei, ne, Ep, lde), scale = _attn_args(where, rowptr, colidx, n_heads, [("Q", Q, int(rowptr.numel() - 1)), ("K", K, n_cols),
+                                                                                           ("V", V, n_cols)], E, eidx, scale)
+    dev = Q.device
+    out = _attn_out(where, "out", out, n_rows, F, dev)
+    rowmax, rowsum = stats_out if stats_out is not None else (torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) for _ in range(2))
+    ws, _ = _scratch("gnnx_attn_workspace", n_rows, nnz, n_heads, D, device=dev, tag="attn")
+    capi.call("gnnx_attn_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, ei, ne, n_heads, D, scale, _ptr(Q), _ld(Q),
+              _ptr(K), _ld(K), _ptr(V), _ld(V), Ep, lde, _ptr(out), _ld(out), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where),
+              _gat_stat(rowsum, n_rows, n_heads, "rowsum", where), _ptr(ws), ws.numel(), _stream())
+    return out, rowmax, rowsum
+
+
+def attn_aggregate_bwd_rows(rowptr, colidx, G, Q, K, V, Y, n_heads, rowmax, rowsum, E=None, eidx=None, scale=None, dq_out=None, dot_out=None,
+                            de_out=None):
+    """gnnx_attn_bwd_rows_csr_f32, on the forward pattern: (dQ [n_rows, H*D], dot [n_rows, H], dE [edge rows, H*D] or None) from
+    G = dL/dY, the forward's operands, its Y and its statistics.  dE rows that no entry names are not written: without de_out they are
+    the zeros the array is made of.  dot goes to attn_aggregate_bwd_cols."""
+    where = "attn_aggregate_bwd_rows"
+    n_cols = int(K.shape[0])
+    n_rows = int(rowptr.numel() - 1)
+    n_rows, nnz, F, D, (ei, ne, Ep, lde), scale = _attn_args(where, rowptr, colidx, n_heads, [("G", G, n_rows), ("Q", Q, n_rows), ("K", K, n_cols),
+                                                                                           ("V", V, n_cols), ("Y", Y, n_rows)], E, eidx, scale)
+    dev = Q.device
+    dQ = _attn_out(where, "dq_out", dq_out, n_rows, F, dev)
+    dE = None if E is None else _attn_out(where, "de_out", de_out, ne, F, dev, zero=True)
+    dot = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if dot_out is None else dot_out
+    ws, _ = _scratch("gnnx_attn_workspace", n_rows, nnz, n_heads, D, device=dev, tag="attn")
+    capi.call("gnnx_attn_bwd_rows_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr), _ptr(colidx) if nnz else None, ei, ne, n_heads, D, scale, _ptr(G),
+              _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K), _ptr(V), _ld(V), Ep, lde, _ptr(Y), _ld(Y), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where),
+              _gat_stat(rowsum, n_rows, n_heads, "rowsum", where), _ptr(dQ), _ld(dQ), _gat_stat(dot, n_rows, n_heads, "dot_out", where), _ptr(dE),
+              0 if dE is None else _ld(dE), _ptr(ws), ws.numel(), _stream())
+    return dQ, dot, dE
+
+
+def attn_aggregate_bwd_cols(rowptr_t, colidx_t, G, Q, K, V, n_heads, rowmax, rowsum, dot, E=None, eidx_t=None, scale=None, dk_out=None,
+                            dv_out=None, beta=0.0):
+    """gnnx_attn_bwd_cols_csr_f32, on the TRANSPOSED pattern (row c, entries i): (dK, dV), both [n_c, H*D], with
+    dV[c] = beta*dV[c] + sum_i alpha_ic G[i] and dK[c] = beta*dK[c] + scale * sum_i ds_ic Q[i].  G, Q, rowmax, rowsum and dot belong to the
+    forward's rows (this pattern's columns), K and V to its columns (this pattern's rows); eidx_t is the entry -> edge map of THIS pattern."""
+    where = "attn_aggregate_bwd_cols"
+    n_cols = int(G.shape[0])
+    n_rows = int(rowptr_t.numel() - 1)
+    n_rows, nnz, F, D, (ei, ne, Ep, lde), scale = _attn_args(where, rowptr_t, colidx_t, n_heads, [("K", K, n_rows), ("V", V, n_rows), ("G", G, n_cols),
+                                                                                               ("Q", Q, n_cols)], E, eidx_t, scale)
+    dev = Q.device
+    if beta and (dk_out is None or dv_out is None):
+        raise capi.GnnxError(-2, where, "beta = 1 adds onto dk_out and dv_out, which were not given")
+    dK, dV = _attn_out(where, "dk_out", dk_out, n_rows, F, dev), _attn_out(where, "dv_out", dv_out, n_rows, F, dev)
+    ws, _ = _scratch("gnnx_attn_workspace", n_rows, nnz, n_heads, D, device=dev, tag="attn")
+    capi.call("gnnx_attn_bwd_cols_csr_f32", n_rows, n_cols, nnz, _ptr(rowptr_t), _ptr(colidx_t) if nnz else None, ei, ne, n_heads, D, scale,
+              _ptr(G), _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K), _ptr(V), _ld(V), Ep, lde, _gat_stat(rowmax, n_cols, n_heads, "rowmax", where),
+              _gat_stat(rowsum, n_cols, n_heads, "rowsum", where), _gat_stat(dot, n_cols, n_heads, "dot", where), float(beta), _ptr(dK), _ld(dK),
+              _ptr(dV), _ld(dV), _ptr(ws), ws.numel(), _stream())
+    return dK, dV
+
+
 REDUCE_OPS = {"max": 0, "min": 1}   # GNNX_REDUCE_MAX / GNNX_REDUCE_MIN
 
 
@@ -3207,6 +3299,118 @@ class GineStack(_Stack):
             G = relu_mask(h, dh, out=self._tmp(("G", l), (n, d0)))               # h = relu output of the layer below
             colsum(G, out=self.db[l - 1])
         return G
+
+
+class TransformerStack(_Stack):
+    """L transformer-attention layers (TransformerConv; Shi et al. 2021) with the surface of GatStack, optionally reading the graph's
+    edge attributes (g.set_edge_attr).  Layer l has heads[l] heads of width D = dims[l+1] / heads[l], F = dims[l+1]; per head
+        q = h W_q^T,  k = h W_k^T,  v = h W_v^T,  E_l = edge_attr W_e^T  [edge rows, F]  (with edge_dim);
+        alpha_ic = softmax over the stored columns c of row i of D ** -0.5 * <q_i, k_c + E_l[edge of (i, c)]>;
+        h'_i = act( sum_c alpha_ic (v_c + E_l[edge of (i, c)]) + h_i W_s^T + b ),  ReLU between layers, none after the last,
+    and the layer's output is the concatenation of its heads.  ONE product h [W_q; W_k; W_v; W_s]^T gives an [n, 4F] matrix whose four
+    column slabs go to attn_aggregate by leading dimension; score, softmax and aggregation are that one call, which gathers every k, v
+    and edge row once: no [nnz, .] array exists.  Backward per layer: attn_aggregate_bwd_rows (dq, dE_l) and attn_aggregate_bwd_cols
+    (dk, dv, on CSR(A^T)) write three slabs of one [n, 4F] matrix whose fourth is dZ itself; one product with h gives the stacked weight
+    gradient, one with the stacked weight gives dh; dW_e = dE_l^T edge_attr, with the rows of dE_l that no entry names left zero.
+    The stack needs the transposed CSR.  Without edge_dim it never builds g.attention_map(), so it also takes a RELABELLED graph; with
+    edge_dim it raises GineStack's error on a graph without attributes and goes through g.entry_edge / g.entry_edge_t.  An empty row
+    attends to nothing: its output is h W_s^T + b.  Head averaging, the gated skip (beta=True of the paper's implementation) and
+    attention dropout are not implemented.  forward / backward / step / train_step / evaluate / grad_buffer / on_graph, the link_*
+    calls, and use under GraphClassifier.  Every operation is a C-ABI call; no atomics on any value; the same bits every run."""
+
+    def __init__(self, g, dims, heads=None, edge_dim=None, seed=0, device="cuda"):
+        self.dims, self.edge_dim = list(dims), None if edge_dim is None else int(edge_dim)
+        L = len(dims) - 1
+        self.heads = _AttentionStack._heads_per_layer(dims, heads)
+        self._bind(g)
+        self.W = [uniform_pm1(seed + 2 * l, (4 * dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.W_e = [] if edge_dim is None else [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], self.edge_dim), scale=self.edge_dim ** -0.5, device=device)
+                                                for l in range(L)]
+        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
+        self.dW, self.dW_e, self.db = ([torch.zeros_like(p) for p in ps] for ps in (self.W, self.W_e, self.b))
+        self._saved = None
+        self._buf = {}
+        self._opt = [None]
+
+    def _bind(self, g):
+        """What the stack holds of the graph itself: with edge_dim, the entry -> edge maps of both patterns."""
+        if g.rowptr_t is None or g.colidx_t is None:
+            raise capi.GnnxError(-1, "TransformerStack", "the graph has no transposed CSR (from_coo(..., transpose=True))")
+        self.entry_edge = self.entry_edge_t = None
+        if self.edge_dim is not None:
+            if getattr(g, "edge_attr", None) is None:
+                raise capi.GnnxError(-1, "TransformerStack", "the graph has no edge attributes (g.set_edge_attr(src, dst, attr))")
+            if int(g.edge_attr.shape[1]) != self.edge_dim:
+                raise ValueError(f"the graph's edge attributes have {int(g.edge_attr.shape[1])} columns, the stack was built for {self.edge_dim}")
+            self.entry_edge, self.entry_edge_t = g.entry_edge, g.entry_edge_t
+        self.g = g
+        return self
+
+    def params(self):
+        return self.W + self.W_e + self.b
+
+    def grads(self):
+        return self.dW + self.dW_e + self.db
+
+    def on_graph(self, g):
+        """This stack on another graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch buffers."""
+        if g.n != self.g.n:
+            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
+        return self._view(share_buf=True)._bind(g)
+
+    @staticmethod
+    def _slabs(P):
+        F = int(P.shape[1]) // 4
+        return [P[:, k * F:(k + 1) * F] for k in range(4)]
+
+    def forward(self, X):
+        L, g, n = len(self.W), self.g, self.g.n
+        saved, h = [], X
+        for l in range(L):
+            F, Hh = self.dims[l + 1], self.heads[l]
+            P = gemm(h, self.W[l], transB=True, out=self._tmp(("P", l), (n, 4 * F)))
+            Q, K, V, S = self._slabs(P)
+            El = None
+            if self.edge_dim is not None:
+                El = gemm(g.edge_attr, self.W_e[l], transB=True, out=self._tmp(("E", l), (int(g.edge_attr.shape[0]), F)))
+            Y, rowmax, rowsum = attn_aggregate(g.rowptr, g.colidx, Q, K, V, Hh, E=El, eidx=self.entry_edge, out=self._tmp(("Y", l), (n, F)),
+                                               stats_out=(self._tmp(("rowmax", l), (n, Hh)), self._tmp(("rowsum", l), (n, Hh))))
+            Z = bias_add(S, self.b[l], out=self._tmp(("Z", l), (n, F)))     # (skip + b) + Y; Y itself waits for the backward's <G, Y>
+            axpy(1.0, Y, Z)
+            if l + 1 < L:   # only relu(Z) is kept: its sign is the mask
+                bn_relu_fwd(Z, relu=True, out=Z)
+            saved.append((h, P, El, Y, rowmax, rowsum))
+            h = Z
+        self._saved = saved
+        return h
+
+    def backward(self, dOut, input_grad=True, have_last_bias_grad=False):
+        """The gradient of every parameter from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
+        have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
+        L, g, n = len(self.W), self.g, self.g.n
+        dP = [self._tmp(("dP", l), (n, 4 * self.dims[l + 1])) for l in range(L)]   # dq | dk | dv | dZ of every layer
+        G = self._slabs(dP[L - 1])[3]
+        capi.call("gnnx_memcpy2d_d2d", _ptr(G), 4 * _ld(G), _ptr(dOut), 4 * _ld(dOut), 4 * self.dims[L], n, _stream())
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[L - 1])
+        for l in reversed(range(L)):
+            F, Hh = self.dims[l + 1], self.heads[l]
+            h, P, El, Y, rowmax, rowsum = self._saved[l]
+            Q, K, V, _ = self._slabs(P)
+            dQ, dK, dV, G = self._slabs(dP[l])
+            # rows of dE that no entry names (duplicate edges, self loops) are never written: they stay the zeros they were made as
+            dE = None if El is None else self._tmp(("dE", l), tuple(El.shape), zero=True)
+            _, dot, _ = attn_aggregate_bwd_rows(g.rowptr, g.colidx, G, Q, K, V, Y, Hh, rowmax, rowsum, E=El, eidx=self.entry_edge, dq_out=dQ,
+                                                dot_out=self._tmp(("dot", l), (n, Hh)), de_out=dE)
+            attn_aggregate_bwd_cols(g.rowptr_t, g.colidx_t, G, Q, K, V, Hh, rowmax, rowsum, dot, E=El, eidx_t=self.entry_edge_t, dk_out=dK,
+                                    dv_out=dV)
+            if dE is not None:
+                gemm(dE, g.edge_attr, transA=True, out=self.dW_e[l])
+            gemm(dP[l], h, transA=True, out=self.dW[l])
+            if l == 0:
+                return gemm(dP[l], self.W[l]) if input_grad else None
+            # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue, straight into that layer's slab
+            gemm_relu_colsum(dP[l], self.W[l], h, out=self._slabs(dP[l - 1])[3], colsum_out=self.db[l - 1])
 
 
 class RgcnStack(_Stack):

@@ -914,6 +914,84 @@ int gnnx_gat_aggregate_bwd_cols_csr_f32(int32_t n_rows, int32_t n_cols, int64_t 
                                         float *d_dX, int64_t lddx, float *d_dcolterm, int64_t dcolterm_stride, void *d_workspace,
                                         size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ dot-product attention ------- */
+/*
+ * Transformer attention over the stored entries of each CSR row (TransformerConv; Shi et al. 2021), with an optional feature row per
+ * EDGE added to the gathered key and value -- score, softmax and aggregation, and their backward, WITHOUT any per-entry array.
+ * H = n_heads heads of width D = head_dim, F = H D; every matrix is [rows, F] with a leading dimension (the column slabs of one
+ * [n, 4F] product serve), head h in columns h D .. h D + D - 1.  "Own" is the row of the pattern the call runs on.  d_E and d_eidx are
+ * optional together: d_E == NULL means no edge term, k' = K[c] and v' = V[c] with their own bits (d_eidx must then be NULL too);
+ * d_eidx == NULL with d_E means e_p = p (n_edge_rows >= nnz is then validated).  eidx is TRUSTED like colidx.  Every operation below is
+ * ONE separately rounded fp32 operation (no fused multiply-add, no packed pair); expf is the device library's.
+ *
+ * gnnx_attn_csr_f32 -- forward.  For entry p of row i, head h, with c = colidx[p], e = eidx[p]:
+ *     k'_p = K[c] + E[e];   v'_p = V[c] + E[e];   s_p = scale * <Q[i], k'_p>_h;   m = max_p s_p;   x_p = expf(s_p - m);   z = sum_p x_p
+ *     Y[i] = (sum_p x_p v'_p) / z    (one IEEE division per element);   d_rowmax = m, d_rowsum = z: [n_rows, H] contiguous, each may be NULL.
+ *   An empty row gives Y = +0, m = -inf, z = +0.  No bias or activation epilogue: the backward needs <G, Y> of the plain output.
+ * gnnx_attn_bwd_rows_csr_f32 -- backward on the FORWARD pattern, from G = dL/dY, the forward's operands, Y, m and z:
+ *     dot[i, h] = <G_i, Y_i>_h;   alpha_p = expf(s_p - m) / z;   dalpha_p = <G_i, v'_p>_h;   ds_p = alpha_p * (dalpha_p - dot[i, h])
+ *     dQ[i] = scale * sum_p (ds_p * k'_p);     dE[e_p, f] = (alpha_p * G[i, f]) + ((scale * ds_p) * Q[i, f])    (with d_E only)
+ *   d_dot: [n_rows, H] contiguous, an output.  dE is ONE store per entry, no sum: rows of dE that no entry names are not touched, two
+ *   entries that name one edge row race (the contract of gnnx_spmm_csr_edge_bwd_f32; gnnx_csr_entry_edges never does either).
+ * gnnx_attn_bwd_cols_csr_f32 -- backward on the TRANSPOSED pattern: row c of CSR(A^T), its entries are the forward's rows i, d_eidx the
+ *   entry -> edge map of THAT pattern.  Own rows K[c], V[c]; gathered Q[i], G[i], E[e] and m, z, dot at [i, h]; alpha, ds as above:
+ *     dV[c] = beta * dV[c] + sum_i (alpha_ic * G_i);     dK[c] = beta * dK[c] + scale * sum_i (ds_ic * Q_i)     (beta 0 or 1; never read at 0).
+ *   No transpose map and no [nnz, .] array is read or written.
+ *
+ * ORDER, a function of the row length and of D alone.  A row is cut into segments of S = 4096 consecutive entries (a row of d <= S is
+ * one segment); a segment is walked ascending in BLOCKS of 4 consecutive entries, the last block holding the 1 .. 4 left.  Every dot
+ * product over a head is the SDDMM lane-group order with F := D (gnnx_sddmm_csr_f32; left operand Q for s, G for dot and dalpha); s then
+ * takes one multiply by scale.
+ *   Forward (an online softmax: every K, E and V row is gathered ONCE).  A segment starts from (m, z, N) = (-inf, +0, +0); per block
+ *     m' = max(m, s_u);  r = 1 if m == m', else expf(m - m');  z = z * r, then z = z + x_u for u ascending, x_u = expf(s_u - m');
+ *     N[f] = N[f] * r, then N[f] = N[f] + (x_u * v'_u[f]) for u ascending;  m = m'.        One expf per entry and one per block.
+ *   One segment: Y = N / z.  Several: m = max_s m_s;  w_s = 1 if m_s == m, else expf(m_s - m);  z = (z_0 * w_0) + (z_1 * w_1) + ... in
+ *   ascending segment order, N[f] likewise, Y = N / z.  (With scores that are all equal, r and w are exactly 1 and z is the row length.)
+ *   Backward.  m and z are operands, nothing is rescaled: ONE accumulator per output element from +0 over a segment's entries ascending,
+ *   each product rounded first; the segments' sums are added ascending starting from the first; dQ and dK then take one multiply by scale.
+ * How rows, heads and features map to lanes is not in the result: two runs give the same bits, and the 16-byte path and the
+ * scalar-load path (D % 4 != 0, or a pointer / leading dimension off 16 bytes) give the same bits.  No atomics on any value (two
+ * counter atomics per row longer than S).
+ *
+ * Statuses, all before any HIP call, as the fused graph attention's: negative sizes, nnz >= 2^31, n_heads < 1, head_dim < 1, a leading
+ * dimension < F, a beta other than 0 or 1, d_eidx without d_E, n_edge_rows < nnz with d_E and without d_eidx, a null rowptr / required
+ * operand or output are GNNX_ERR_INVALID_ARG; head_dim > 256 (a lane holds ONE 16-byte chunk of its head) and more than 65535 passes of
+ * heads (a pass holds max(1, 64 / max(1, pow2 >= D / 4)) heads) are GNNX_ERR_UNSUPPORTED; a workspace that is NULL or smaller than
+ * gnnx_attn_workspace(n_rows, nnz, n_heads, head_dim) -- n_rows of the pattern the call runs on -- is GNNX_ERR_WORKSPACE.  A refused
+ * call reads and writes nothing.  The workspace holds nothing between calls; with hubs = min(n_rows, nnz / (S + 1)) and
+ * segs = nnz / S + hubs (integer divisions) the query answers 256 + the next multiple of 256 of
+ * 4 * (16 + 2 * segs * F + 2 * segs * H + 2 * hubs + segs) bytes: 16 counter words, per segment slot two [F] partials and two [H]
+ * statistics, the hub list with each hub's first slot, the hub of each slot.  Asynchronous on `stream`; nothing is allocated or
+ * synchronised.  Inputs and outputs must not alias.  The CSR and its indices are trusted as in gnnx_spmm_csr_f32.
+ *
+ * Kernels (gnnx_attn.hip): a head is GH = min(64, pow2 >= ceil(D / 4)) lanes with one 16-byte chunk each (the kernels are instantiated
+ * on GH), a row max(4, min(64, pow2 >= GH H)) lanes, further heads are passes in grid.y; the own Q (and G) chunk stays in registers;
+ * a block's 12 chunk loads are requested before the first is consumed and its butterflies run interleaved.  Rows longer than S are
+ * listed by the row kernel; a fixed grid writes (m_s, z_s, N_s) per segment slot in ONE pass and a thread per element combines.
+ *
+ * Accuracy (tests/test_gpu_attn.py against float64 NumPy loops, tests/attn_ref.py; bar c * 2^-24 * sum of the absolute terms, c = the
+ * rounded operations on the longest chain, derived next to the reference; a term that holds a softmax weight carries the factor
+ * 1 + S_s + S_m of the score's and the maximum's absolute terms in its sum, because expf turns their absolute error into a relative
+ * one): worst observed fraction of the bar on the test pattern (rows of up to 12 293 entries) over all tested (H, D): rowmax 0.25,
+ * rowsum 0.030, Y 0.027, dot 0.27, dQ 0.048, dE 0.071, dK 0.061, dV 0.073.
+ */
+int gnnx_attn_workspace(int32_t n_rows, int64_t nnz, int32_t n_heads, int32_t head_dim, size_t *workspace_bytes);
+int gnnx_attn_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_eidx,
+                      int64_t n_edge_rows, int32_t n_heads, int32_t head_dim, float scale, const float *d_Q, int64_t ldq, const float *d_K,
+                      int64_t ldk, const float *d_V, int64_t ldv, const float *d_E, int64_t lde, float *d_Y, int64_t ldy, float *d_rowmax,
+                      float *d_rowsum, void *d_workspace, size_t workspace_bytes, void *stream);
+int gnnx_attn_bwd_rows_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                               const int32_t *d_eidx, int64_t n_edge_rows, int32_t n_heads, int32_t head_dim, float scale, const float *d_G,
+                               int64_t ldg, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+                               const float *d_E, int64_t lde, const float *d_Y, int64_t ldy, const float *d_rowmax, const float *d_rowsum,
+                               float *d_dQ, int64_t lddq, float *d_dot, float *d_dE, int64_t ldde, void *d_workspace, size_t workspace_bytes,
+                               void *stream);
+int gnnx_attn_bwd_cols_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colidx,
+                               const int32_t *d_eidx, int64_t n_edge_rows, int32_t n_heads, int32_t head_dim, float scale, const float *d_G,
+                               int64_t ldg, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+                               const float *d_E, int64_t lde, const float *d_rowmax, const float *d_rowsum, const float *d_dot, float beta,
+                               float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ dynamic attention scores (GATv2) ---- */
 /*
  * The score of GATv2 (Brody, Alon, Yahav, ICLR 2022): e(i, c) = a^T leaky_relu(W_l h_i + W_r h_c), the non-linearity INSIDE the sum.  The
