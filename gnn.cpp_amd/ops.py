@@ -1443,6 +1443,65 @@ def attn_aggregate_bwd_cols(rowptr_t, colidx_t, G, Q, K, V, n_heads, rowmax, row
     return dK, dV
 
 
+def _segment_attn_args(where, segptr, n_heads, mats, scale):
+    """What the three dense segment attention calls share: the checked segptr, the checked [n_rows, H*D] matrices (mats: (name, tensor)
+    pairs, the first one fixes the shape) and the scale (default D ** -0.5)."""
+    if segptr.dtype != torch.int32 or segptr.dim() != 1 or segptr.numel() < 1 or not segptr.is_contiguous():
+        raise capi.GnnxError(-2, where, f"segptr must be a contiguous int32 [n_seg + 1] array, got {tuple(segptr.shape)} {segptr.dtype}")
+    if mats[0][1].dim() != 2:
+        raise capi.GnnxError(-2, where, f"{mats[0][0]} must be a 2-D matrix, got {tuple(mats[0][1].shape)}")
+    n_rows, F = (int(v) for v in mats[0][1].shape)
+    D = _heads_of(mats[0][1], n_heads, where)
+    for name, t in mats:
+        _gat_matrix(where, name, t, n_rows, F)
+    return int(segptr.numel() - 1), n_rows, F, D, float(D ** -0.5 if scale is None else scale)
+
+
+def segment_attention(segptr, Q, K, V, n_heads, scale=None, out=None, stats_out=None):
+    """gnnx_segment_attn_f32: dense self-attention inside the segments of segptr (segment_pool's segptr; GraphBatch.graph_ptr) on the
+    matrix cores, no index array and no workspace --
+        Y[i] = sum_j alpha_ij V[j],  alpha = softmax over the rows j of i's segment of scale * <Q[i], K[j]> per head.
+    Q, K, V: [n_rows, H*D], each may be a column slab of a wider matrix; D <= 128.  scale defaults to D ** -0.5.  Returns (Y, rowmax,
+    rowsum), the statistics as [n_rows, H] (stats_out = (rowmax, rowsum) to write them into the caller's arrays)."""
+    where = "segment_attention"
+    n_seg, n_rows, F, D, scale = _segment_attn_args(where, segptr, n_heads, [("Q", Q), ("K", K), ("V", V)], scale)
+    dev = Q.device
+    out = _attn_out(where, "out", out, n_rows, F, dev)
+    rowmax, rowsum = stats_out if stats_out is not None else (torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) for _ in range(2))
+    capi.call("gnnx_segment_attn_f32", n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(Q), _ld(Q), _ptr(K), _ld(K), _ptr(V), _ld(V), _ptr(out),
+              _ld(out), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where), _gat_stat(rowsum, n_rows, n_heads, "rowsum", where), _stream())
+    return out, rowmax, rowsum
+
+
+def segment_attention_bwd_rows(segptr, G, Q, K, V, Y, n_heads, rowmax, rowsum, scale=None, dq_out=None, dot_out=None):
+    """gnnx_segment_attn_bwd_rows_f32: (dQ [n_rows, H*D], dot [n_rows, H]) from G = dL/dY, the forward's operands, its Y and its
+    statistics.  dot goes to segment_attention_bwd_cols."""
+    where = "segment_attention_bwd_rows"
+    n_seg, n_rows, F, D, scale = _segment_attn_args(where, segptr, n_heads, [("G", G), ("Q", Q), ("K", K), ("V", V), ("Y", Y)], scale)
+    dev = Q.device
+    dQ = _attn_out(where, "dq_out", dq_out, n_rows, F, dev)
+    dot = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if dot_out is None else dot_out
+    capi.call("gnnx_segment_attn_bwd_rows_f32", n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K),
+              _ptr(V), _ld(V), _ptr(Y), _ld(Y), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where),
+              _gat_stat(rowsum, n_rows, n_heads, "rowsum", where), _ptr(dQ), _ld(dQ), _gat_stat(dot, n_rows, n_heads, "dot_out", where), _stream())
+    return dQ, dot
+
+
+def segment_attention_bwd_cols(segptr, G, Q, K, V, n_heads, rowmax, rowsum, dot, scale=None, dk_out=None, dv_out=None, beta=0.0):
+    """gnnx_segment_attn_bwd_cols_f32: (dK, dV), both [n_rows, H*D], with dV[j] = beta*dV[j] + sum_i alpha_ij G[i] and
+    dK[j] = beta*dK[j] + scale * sum_i ds_ij Q[i] over the rows i of j's segment; dot is segment_attention_bwd_rows'."""
+    where = "segment_attention_bwd_cols"
+    n_seg, n_rows, F, D, scale = _segment_attn_args(where, segptr, n_heads, [("G", G), ("Q", Q), ("K", K), ("V", V)], scale)
+    dev = Q.device
+    if beta and (dk_out is None or dv_out is None):
+        raise capi.GnnxError(-2, where, "beta = 1 adds onto dk_out and dv_out, which were not given")
+    dK, dV = _attn_out(where, "dk_out", dk_out, n_rows, F, dev), _attn_out(where, "dv_out", dv_out, n_rows, F, dev)
+    capi.call("gnnx_segment_attn_bwd_cols_f32", n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K),
+              _ptr(V), _ld(V), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where), _gat_stat(rowsum, n_rows, n_heads, "rowsum", where),
+              _gat_stat(dot, n_rows, n_heads, "dot", where), float(beta), _ptr(dK), _ld(dK), _ptr(dV), _ld(dV), _stream())
+    return dK, dV
+
+
 REDUCE_OPS = {"max": 0, "min": 1}   # GNNX_REDUCE_MAX / GNNX_REDUCE_MIN
 
 
@@ -3315,15 +3374,20 @@ class TransformerStack(_Stack):
     The stack needs the transposed CSR.  Without edge_dim it never builds g.attention_map(), so it also takes a RELABELLED graph; with
     edge_dim it raises GineStack's error on a graph without attributes and goes through g.entry_edge / g.entry_edge_t.  An empty row
     attends to nothing: its output is h W_s^T + b.  Head averaging, the gated skip (beta=True of the paper's implementation) and
-    attention dropout are not implemented.  forward / backward / step / train_step / evaluate / grad_buffer / on_graph, the link_*
+    attention dropout are not implemented.
+    global_attention=True (g must be a GraphBatch, else TypeError) adds the graph transformers' GLOBAL branch: the product becomes
+    h [W_q; W_k; W_v; W_s; W_q'; W_k'; W_v']^T [n, 7F] and the layer act( local + segment_attention(g.graph_ptr, q', k', v') + skip + b ):
+    every vertex attends to every vertex of its own graph, on the matrix cores, with no index array.  Backward writes three more slabs of
+    an [n, 7F] dP with segment_attention_bwd_rows / _bwd_cols; the two products are unchanged in form.  forward / backward / step / train_step / evaluate / grad_buffer / on_graph, the link_*
     calls, and use under GraphClassifier.  Every operation is a C-ABI call; no atomics on any value; the same bits every run."""
 
-    def __init__(self, g, dims, heads=None, edge_dim=None, seed=0, device="cuda"):
+    def __init__(self, g, dims, heads=None, edge_dim=None, global_attention=False, seed=0, device="cuda"):
         self.dims, self.edge_dim = list(dims), None if edge_dim is None else int(edge_dim)
         L = len(dims) - 1
         self.heads = _AttentionStack._heads_per_layer(dims, heads)
+        self.n_slabs = 7 if global_attention else 4   # q | k | v | skip, then the global branch's q' | k' | v'
         self._bind(g)
-        self.W = [uniform_pm1(seed + 2 * l, (4 * dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.W = [uniform_pm1(seed + 2 * l, (self.n_slabs * dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
         self.W_e = [] if edge_dim is None else [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], self.edge_dim), scale=self.edge_dim ** -0.5, device=device)
                                                 for l in range(L)]
         self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
@@ -3336,6 +3400,8 @@ class TransformerStack(_Stack):
         """What the stack holds of the graph itself: with edge_dim, the entry -> edge maps of both patterns."""
         if g.rowptr_t is None or g.colidx_t is None:
             raise capi.GnnxError(-1, "TransformerStack", "the graph has no transposed CSR (from_coo(..., transpose=True))")
+        if self.n_slabs == 7 and not isinstance(g, GraphBatch):
+            raise TypeError("global_attention=True needs a GraphBatch: every vertex attends to the vertices of its own graph")
         self.entry_edge = self.entry_edge_t = None
         if self.edge_dim is not None:
             if getattr(g, "edge_attr", None) is None:
@@ -3359,17 +3425,17 @@ class TransformerStack(_Stack):
         return self._view(share_buf=True)._bind(g)
 
     @staticmethod
-    def _slabs(P):
-        F = int(P.shape[1]) // 4
-        return [P[:, k * F:(k + 1) * F] for k in range(4)]
+    def _slabs(P, count):
+        F = int(P.shape[1]) // count
+        return [P[:, k * F:(k + 1) * F] for k in range(count)]
 
     def forward(self, X):
         L, g, n = len(self.W), self.g, self.g.n
         saved, h = [], X
         for l in range(L):
             F, Hh = self.dims[l + 1], self.heads[l]
-            P = gemm(h, self.W[l], transB=True, out=self._tmp(("P", l), (n, 4 * F)))
-            Q, K, V, S = self._slabs(P)
+            P = gemm(h, self.W[l], transB=True, out=self._tmp(("P", l), (n, self.n_slabs * F)))
+            Q, K, V, S = self._slabs(P, self.n_slabs)[:4]
             El = None
             if self.edge_dim is not None:
                 El = gemm(g.edge_attr, self.W_e[l], transB=True, out=self._tmp(("E", l), (int(g.edge_attr.shape[0]), F)))
@@ -3377,9 +3443,15 @@ class TransformerStack(_Stack):
                                                stats_out=(self._tmp(("rowmax", l), (n, Hh)), self._tmp(("rowsum", l), (n, Hh))))
             Z = bias_add(S, self.b[l], out=self._tmp(("Z", l), (n, F)))     # (skip + b) + Y; Y itself waits for the backward's <G, Y>
             axpy(1.0, Y, Z)
+            glob = None
+            if self.n_slabs == 7:   # the global branch: dense attention inside each graph of the batch, on its own three slabs
+                Qg, Kg, Vg = self._slabs(P, 7)[4:]
+                glob = segment_attention(g.graph_ptr, Qg, Kg, Vg, Hh, out=self._tmp(("Yg", l), (n, F)),
+                                         stats_out=(self._tmp(("gmax", l), (n, Hh)), self._tmp(("gsum", l), (n, Hh))))
+                axpy(1.0, glob[0], Z)
             if l + 1 < L:   # only relu(Z) is kept: its sign is the mask
                 bn_relu_fwd(Z, relu=True, out=Z)
-            saved.append((h, P, El, Y, rowmax, rowsum))
+            saved.append((h, P, El, Y, rowmax, rowsum, glob))
             h = Z
         self._saved = saved
         return h
@@ -3388,29 +3460,36 @@ class TransformerStack(_Stack):
         """The gradient of every parameter from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         L, g, n = len(self.W), self.g, self.g.n
-        dP = [self._tmp(("dP", l), (n, 4 * self.dims[l + 1])) for l in range(L)]   # dq | dk | dv | dZ of every layer
-        G = self._slabs(dP[L - 1])[3]
+        ns = self.n_slabs
+        dP = [self._tmp(("dP", l), (n, ns * self.dims[l + 1])) for l in range(L)]   # dq | dk | dv | dZ (| dq' | dk' | dv') of every layer
+        G = self._slabs(dP[L - 1], ns)[3]
         capi.call("gnnx_memcpy2d_d2d", _ptr(G), 4 * _ld(G), _ptr(dOut), 4 * _ld(dOut), 4 * self.dims[L], n, _stream())
         if not have_last_bias_grad:
             colsum(G, out=self.db[L - 1])
         for l in reversed(range(L)):
             F, Hh = self.dims[l + 1], self.heads[l]
-            h, P, El, Y, rowmax, rowsum = self._saved[l]
-            Q, K, V, _ = self._slabs(P)
-            dQ, dK, dV, G = self._slabs(dP[l])
+            h, P, El, Y, rowmax, rowsum, glob = self._saved[l]
+            Q, K, V = self._slabs(P, ns)[:3]
+            dQ, dK, dV, G = self._slabs(dP[l], ns)[:4]
             # rows of dE that no entry names (duplicate edges, self loops) are never written: they stay the zeros they were made as
             dE = None if El is None else self._tmp(("dE", l), tuple(El.shape), zero=True)
             _, dot, _ = attn_aggregate_bwd_rows(g.rowptr, g.colidx, G, Q, K, V, Y, Hh, rowmax, rowsum, E=El, eidx=self.entry_edge, dq_out=dQ,
                                                 dot_out=self._tmp(("dot", l), (n, Hh)), de_out=dE)
             attn_aggregate_bwd_cols(g.rowptr_t, g.colidx_t, G, Q, K, V, Hh, rowmax, rowsum, dot, E=El, eidx_t=self.entry_edge_t, dk_out=dK,
                                     dv_out=dV)
+            if glob is not None:
+                Qg, Kg, Vg = self._slabs(P, ns)[4:]
+                dQg, dKg, dVg = self._slabs(dP[l], ns)[4:]
+                _, gdot = segment_attention_bwd_rows(g.graph_ptr, G, Qg, Kg, Vg, glob[0], Hh, glob[1], glob[2], dq_out=dQg,
+                                                     dot_out=self._tmp(("gdot", l), (n, Hh)))
+                segment_attention_bwd_cols(g.graph_ptr, G, Qg, Kg, Vg, Hh, glob[1], glob[2], gdot, dk_out=dKg, dv_out=dVg)
             if dE is not None:
                 gemm(dE, g.edge_attr, transA=True, out=self.dW_e[l])
             gemm(dP[l], h, transA=True, out=self.dW[l])
             if l == 0:
                 return gemm(dP[l], self.W[l]) if input_grad else None
             # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue, straight into that layer's slab
-            gemm_relu_colsum(dP[l], self.W[l], h, out=self._slabs(dP[l - 1])[3], colsum_out=self.db[l - 1])
+            gemm_relu_colsum(dP[l], self.W[l], h, out=self._slabs(dP[l - 1], ns)[3], colsum_out=self.db[l - 1])
 
 
 class RgcnStack(_Stack):

@@ -992,6 +992,63 @@ int gnnx_attn_bwd_cols_csr_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, cons
                                const float *d_E, int64_t lde, const float *d_rowmax, const float *d_rowsum, const float *d_dot, float beta,
                                float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ dense segment attention ----- */
+/*
+ * Dense self-attention INSIDE the segments of a batch -- graph transformers' global attention (GraphGPS, Graphormer, SAN): every vertex of
+ * a graph attends to every vertex of the same graph -- forward and backward on the matrix cores, with no index array and NO workspace.
+ * d_segptr: int32 [n_seg + 1], the contract of gnnx_segment_pool_f32's segptr (non-decreasing from 0 to n_rows; trusted; a segment may be
+ * empty and is skipped).  H = n_heads heads of width D = head_dim, F = H D; Q, K, V, G, Y, dQ, dK, dV are [n_rows, F] with a leading
+ * dimension (column slabs of a wider matrix serve), head h in columns h D .. h D + D - 1.  Row i belongs to segment g; per head
+ *     s_ij = scale * <Q_i, K_j>_h  for the rows j of g only;   m_i = max_j s_ij;   x_ij = expf(s_ij - m_i);   z_i = sum_j x_ij
+ * gnnx_segment_attn_f32 -- forward:  Y_i = (sum_j x_ij V_j) / z_i (one IEEE division per element), d_rowmax = m, d_rowsum = z, [n_rows, H]
+ *   contiguous.  A row that no segment holds (segptr[n_seg] < n_rows) gives Y = +0, m = -inf, z = +0.
+ * gnnx_segment_attn_bwd_rows_f32 -- from G = dL/dY, the forward's operands, Y, m and z:  dot[i, h] = <G_i, Y_i>_h ([n_rows, H] contiguous, an
+ *   output);  alpha_ij = expf(s_ij - m_i) / z_i;   ds_ij = alpha_ij * (<G_i, V_j>_h - dot[i, h]);   dQ_i = scale * sum_j ds_ij K_j.
+ * gnnx_segment_attn_bwd_cols_f32 -- with dot of the rows call:  dV_j = beta dV_j + sum_i alpha_ij G_i;   dK_j = beta dK_j + scale * sum_i ds_ij Q_i
+ *   (beta 0 or 1; with 0 the outputs are never read).  m and z are operands of both backward calls: nothing is rescaled.
+ *
+ * ORDER, as far as it is fixed.  A segment's rows are streamed in tiles of 32 from its first row.  The dot products and the sums over a
+ * tile's 32 rows run in v_mfma_f32_32x32x2_f32, whose internal order is the hardware's (fp32 operands and accumulation, no reduced
+ * precision).  Outside it every operation is ONE separately rounded fp32 operation:  s takes one multiply by scale;  per streamed tile
+ * m' = max(m, the tile's maximum),  r = 1 if m == m' else expf(m - m') -- exactly 1 when the maximum did not rise --,  x = expf(s - m'),
+ * the tile's sum = (16 terms ascending) + (the other 16 terms ascending),  z = z * r + that,  N = N * r before the tile's products are
+ * accumulated onto N;  Y = N / z.  Backward: alpha is one expf and one division, ds = alpha * (dP - dot), the accumulators start from +0,
+ * dQ and dK take one multiply by scale, beta = 1 is one add of the old value.  dot is the lane's D / 2 products ascending plus the
+ * other half's.  One accumulator per output element in one lane, no atomics: two runs give the same bits, and the 16-byte path and
+ * the scalar-load path (D % 4 != 0, or a pointer / leading dimension off 16 bytes) give the same bits.  A masked pair has weight
+ * exactly 0; a row of another segment that shares a tile is multiplied by that 0 (its values must be finite).
+ *
+ * Statuses, all before any HIP call: negative n_seg or n_rows, n_heads < 1, head_dim < 1, a leading dimension < F, a beta other than
+ * 0 or 1, n_seg == 0 with n_rows != 0, and -- once there is work -- a null segptr, operand or output are GNNX_ERR_INVALID_ARG;
+ * head_dim > 128 and n_heads > 65535 are GNNX_ERR_UNSUPPORTED.  n_rows == 0 (or n_seg == 0 with it) returns GNNX_OK and writes nothing.
+ * Asynchronous on `stream`; nothing is allocated or synchronised; offsets are 64-bit.  Inputs and outputs must not alias.
+ *
+ * Kernels (gnnx_segment_attn.hip): grid = (tiles of 32 consecutive rows of the whole batch) x heads, one wavefront per workgroup.  The
+ * wavefront finds the first segment of its tile by binary search in segptr and walks the segments that intersect the tile; rows of the
+ * tile outside the current segment and streamed rows past its end are masked and never loaded.  Forward and row side own 32 queries
+ * and stream keys, the column side owns 32 keys and streams queries.  The own tile goes through LDS into registers once (the B
+ * operand); streamed tiles are [32][DP + 4] floats in LDS, DP = D zero-padded to 16, 32, 64 or 128 (the instantiations), loaded with
+ * 16-byte loads where alignment allows and with scalar loads into the same layout otherwise.  The score tile is computed TRANSPOSED
+ * (S^T = K Q^T), so a lane owns one query and 16 of the 32 keys: maximum and sum are in-register plus one exchange with lane ^ 32, and
+ * the weights in those registers are already the B operand of O^T = V^T P^T -- they never go to LDS.  No kernel spills.
+ *
+ * Accuracy (tests/test_gpu_segment_attn.py against tests/attn_ref.py on the all-pairs entry list; bar c * 2^-24 * sum of the absolute
+ * terms, c derived in tests/segment_attn_ref.py counting a product or sum of length L in the matrix pipe as L roundings on one chain):
+ * worst observed fraction of the bar over all tested (H, D) and segments of 1 .. 200 rows: rowmax 0.28, rowsum 0.033, Y 0.011, dot 0.27,
+ * dQ 0.010, dK 0.0095, dV 0.021.
+ */
+int gnnx_segment_attn_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_heads, int32_t head_dim, float scale, const float *d_Q,
+                          int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv, float *d_Y, int64_t ldy, float *d_rowmax,
+                          float *d_rowsum, void *stream);
+int gnnx_segment_attn_bwd_rows_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_heads, int32_t head_dim, float scale,
+                                   const float *d_G, int64_t ldg, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V,
+                                   int64_t ldv, const float *d_Y, int64_t ldy, const float *d_rowmax, const float *d_rowsum, float *d_dQ,
+                                   int64_t lddq, float *d_dot, void *stream);
+int gnnx_segment_attn_bwd_cols_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_heads, int32_t head_dim, float scale,
+                                   const float *d_G, int64_t ldg, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V,
+                                   int64_t ldv, const float *d_rowmax, const float *d_rowsum, const float *d_dot, float beta, float *d_dK,
+                                   int64_t lddk, float *d_dV, int64_t lddv, void *stream);
+
 /* ------------------------------------------------------------------ dynamic attention scores (GATv2) ---- */
 /*
  * The score of GATv2 (Brody, Alon, Yahav, ICLR 2022): e(i, c) = a^T leaky_relu(W_l h_i + W_r h_c), the non-linearity INSIDE the sum.  The
