@@ -2331,14 +2331,44 @@ class Momentum(_TableOptimizer):
         return dict(buf=[] if self._bound is None else self._views(self._arenas[0]), t=self.t)
 
 
+def _uniform_layers(seed, stride, shapes, device, scales=None):
+    """One uniform_pm1 tensor per layer: layer l has the seed `seed + stride * l`, the shape shapes[l] and the scale scales[l] (default:
+    fan-in ** -0.5 with the shape's last extent as fan-in).  A tensor's bits depend on its own seed alone."""
+    scales = [s[-1] ** -0.5 for s in shapes] if scales is None else scales
+    return [uniform_pm1(seed + stride * l, shape, scale=scale, device=device) for l, (shape, scale) in enumerate(zip(shapes, scales))]
+
+
+def _zero_layers(like, device=None):
+    """One float32 zero tensor per entry of `like`: of that shape (a width or a tuple) on `device`, or like that tensor."""
+    return [torch.zeros_like(t) if torch.is_tensor(t) else torch.zeros(t, dtype=torch.float32, device=device) for t in like]
+
+
+def _need_transposed(g, who):
+    if g.rowptr_t is None or g.colidx_t is None:
+        raise capi.GnnxError(-1, who, "the graph has no transposed CSR (from_coo(..., transpose=True))")
+
+
+def _edge_maps(g, edge_dim, who):
+    """(entry_edge, entry_edge_t) of a graph that carries edge attributes of edge_dim columns: the entry -> edge maps of both patterns."""
+    if getattr(g, "edge_attr", None) is None:
+        raise capi.GnnxError(-1, who, "the graph has no edge attributes (g.set_edge_attr(src, dst, attr))")
+    if int(g.edge_attr.shape[1]) != edge_dim:
+        raise ValueError(f"the graph's edge attributes have {int(g.edge_attr.shape[1])} columns, the stack was built for {edge_dim}")
+    return g.entry_edge, g.entry_edge_t
+
+
 class _Model:
     """What the trainable models share: the table `_buf` of persistent scratch buffers, one step of the model's optimiser over the
     parallel lists params() / grads() (a subclass defines both: every parameter tensor, and its gradient at the same position), and
-    _view, the one way to make a second model on the same parameters.  A subclass creates `_buf = {}`, `_saved = None` and the
-    optimiser's slot `_opt = [None]` in its __init__: _view hands the slot itself on, so the optimiser set on a model is the
+    _view, the one way to make a second model on the same parameters.  A subclass's __init__ ends with _init_state(): `_buf = {}`,
+    `_saved = None` and the optimiser's slot `_opt = [None]`.  _view hands the slot itself on, so the optimiser set on a model is the
     optimiser of every view of it, made before or after set_optimizer."""
 
     gather_pitch = False   # only GcnStack asks its graph (GcnStack._bind)
+
+    def _init_state(self):
+        """What a new model starts with beside its parameters: no saved activations, an empty buffer table, the optimiser's slot."""
+        self._saved, self._buf, self._opt = None, {}, [None]
 
     def _tmp(self, key, shape, dtype=torch.float32, zero=False, gathered=False):
         """The persistent buffer `key`: the cached tensor while the shape matches, a new one otherwise (zero-filled with `zero`), on the
@@ -2355,7 +2385,7 @@ class _Model:
         return t
 
     def set_optimizer(self, opt):
-        """Every later step of this model and of every view of it (SageStack.on_graph, GraphClassifier.on_batch) is a step of `opt`
+        """Every later step of this model and of every view of it (_Stack.on_graph, GraphClassifier.on_batch) is a step of `opt`
         (ops.Adam, ops.Momentum), with ONE state and one step count; None: back to plain SGD.  The optimiser binds to params() /
         grads() at its first step.  Returns the model.  A GraphClassifier owns the optimiser of net.params() + [W_c, b_c]; one set on
         the stack it was built from drives that stack's own steps only."""
@@ -2389,11 +2419,17 @@ class _Model:
 
 
 class _Stack(_Model):
-    """What the three graph stacks share.  A subclass has forward(X) / backward(dOut, input_grad, have_last_bias_grad), the bias
-    gradients `db`, and _bind(g): the ONE method that derives everything the class takes from its graph (g itself included) and returns
-    self -- __init__ and every rebinding to another graph call it (SageStack.on_graph, GraphClassifier).  On those rest train_step /
-    evaluate and the link-prediction calls (link_scores, link_grad, link_train_step, link_evaluate: an inner-product decoder on the
-    stack's output), the same for every stack.
+    """What all graph stacks share.  A subclass has forward(X) / backward(dOut, input_grad, have_last_bias_grad), `dims`, the last
+    biases of its layers `b` with their gradients `db`, and _bind(g): the ONE method that derives everything the class takes from its
+    graph (g itself included) and returns self -- __init__ and every rebinding to another graph call it (on_graph, GraphClassifier).
+    On those rest on_graph, train_step / evaluate and the link-prediction calls (link_scores, link_grad, link_train_step,
+    link_evaluate: an inner-product decoder on the stack's output), the same for every stack.
+
+    The statements every layer loop repeats are written once, each on the buffer its caller hands it (so a stack's buffer keys and
+    shapes are its own): _top_grad (the head of backward: db[-1] unless the loss wrote it), _bias_act (a layer's epilogue: + b[l], ReLU
+    below the last layer), _relu_tail (a backward layer's end as two passes: ReLU mask of the layer below, db[l - 1]) and _fused_tail (the
+    same end in the epilogue of dH . W).  The per-layer parameter lists come from _uniform_layers / _zero_layers, what a class needs of
+    its graph from _need_transposed / _edge_maps.
 
     The top gradient's buffer carries a mark in `_buf`, next to it: the selection object (a row list, a LabelledSet) outside whose rows
     the buffer is known to be zero, which is what softmax_ce_rows needs of it.  masked_grad_buffer zeroes the buffer only when the mark
@@ -2401,6 +2437,47 @@ class _Stack(_Model):
     who may write every row (softmax_ce, GraphClassifier.backward, link_grad).  Models that share `_buf` share the mark."""
 
     _ZERO_OUTSIDE = "zero outside"   # the mark's key in _buf; the entry keeps the selection alive, so `is` cannot match a recycled id
+
+    def on_graph(self, g):
+        """This stack on another graph over the same vertices -- a sample of its neighbourhoods, say: a stack of the same class that
+        SHARES this one's parameters, gradients and scratch buffers (the same tensors and the same table, the gradient buffer's
+        zeroed-rows mark included: a step through either is a step of both) and has of its own what _bind derives from the graph
+        (SageStack: inv_deg / map_t; PnaStack: the scaler vectors of the new degrees under the delta it was built with; the edge
+        attributes, relation types or transpose map of the other classes).  The training surface of neighbour sampling:
+            net.on_graph(g.sample_neighbors(k, seed=epoch)).train_step(X, target, rows, lr)
+        while net.evaluate(...) keeps running on the full graph.  A GcnStack view keeps the gather pitch the shared buffers were made
+        with, whatever the new graph asks for: every kernel takes the leading dimension, so the bits are the same."""
+        if g.n != self.g.n:
+            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
+        return self._view(share_buf=True)._bind(g)
+
+    def _top_grad(self, G, have_last_bias_grad):
+        """The head of every backward: G = dL/dlogits, after db[-1] = colsum(G) unless the loss kernel already wrote it."""
+        if not have_last_bias_grad:
+            colsum(G, out=self.db[-1])
+        return G
+
+    def _bias_act(self, l, Z, out):
+        """A layer's epilogue: out = Z + b[l], then ReLU in place below the last layer -- only relu(Z + b) is kept: its sign is the mask."""
+        bias_add(Z, self.b[l], out=out)
+        if l + 1 < len(self.b):
+            bn_relu_fwd(out, relu=True, out=out)
+        return out
+
+    def _relu_tail(self, l, h, dh, buffered=True):
+        """The end of backward layer l > 0 as two passes: G = dh under the mask of h, the ReLU output of the layer below, into the
+        buffer ("G", l) (a fresh matrix without `buffered`), and db[l - 1] = colsum(G)."""
+        G = relu_mask(h, dh, out=self._tmp(("G", l), tuple(dh.shape)) if buffered else None)
+        colsum(G, out=self.db[l - 1])
+        return G
+
+    def _fused_tail(self, l, dH, W, h, input_grad, out=None):
+        """The same end in the epilogue of dH . W (gemm_relu_colsum, into `out` when given); layer 0 has no ReLU below it: the plain
+        product, or None without input_grad."""
+        if l == 0:
+            return gemm(dH, W) if input_grad else None
+        G, _ = gemm_relu_colsum(dH, W, h, out=out, colsum_out=self.db[l - 1])
+        return G
 
     def _grad(self, n=None):
         """The top gradient's buffer, [n (default g.n), dims[-1]], with the mark as it stands unless the buffer had to be reallocated."""
@@ -2511,17 +2588,15 @@ class GcnStack(_Stack):
             pad_streamed = g.n >= 100_000
         self.P = [-(-d // 128) * 128 if (pad_streamed and d % 128 and d >= 64) else d for d in dims]
         self.padded = self.P != self.dims
-        self.Wp = [torch.zeros((self.P[l + 1], self.P[l]), dtype=torch.float32, device=device) for l in range(L)]
-        self.dWp = [torch.zeros_like(w) for w in self.Wp]
+        self.Wp = _zero_layers(zip(self.P[1:], self.P[:-1]), device)
+        self.dWp = _zero_layers(self.Wp)
         self.W = [self.Wp[l][:dims[l + 1], :dims[l]] for l in range(L)]     # the logical matrices (views)
         self.dW = [self.dWp[l][:dims[l + 1], :dims[l]] for l in range(L)]
-        for l in range(L):
-            self.W[l].copy_(uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device))
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.db = [torch.zeros_like(b) for b in self.b]
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        for W, drawn in zip(self.W, _uniform_layers(seed, 2, list(zip(dims[1:], dims[:-1])), device)):
+            W.copy_(drawn)
+        self.b = _zero_layers(dims[1:], device)
+        self.db = _zero_layers(self.b)
+        self._init_state()
 
     def _bind(self, g):
         """The matrices the aggregations GATHER rows from -- H_l = h_l W_l^T forward, the gradients G_l backward -- sit on the padded
@@ -2594,11 +2669,9 @@ class GcnStack(_Stack):
         (softmax_ce(..., colsum_out=net.db[-1])).  labelled (CsrGraph.labelled): dOut is zero outside the labelled rows
         (softmax_ce_rows into a zeroed buffer); the LAST layer's backward aggregation runs on the column-restricted CSR(A^T) -- same
         bits; the dense products and the layers below are not pruned."""
-        G = dOut
+        G = self._top_grad(dOut, have_last_bias_grad)
         L = len(self.W)
         d, P = self.dims, self.P
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
         for l in reversed(range(L)):
             h, Y = self._saved[l]
             if self.padded:
@@ -2613,11 +2686,10 @@ class GcnStack(_Stack):
                 dH = aggregate_bwd(self.g, G, labelled=labelled if l + 1 == L else None)
                 Wl, hl = self.W[l], h
                 gemm(dH, h, transA=True, out=self.dW[l])          # dW_l = dH^T . h
-            if l == 0:
-                G = gemm(dH, Wl) if input_grad else None             # dX of the first layer: no ReLU below it
-            elif fused:
+            if fused or l == 0:
                 # h = Y_{l-1} = relu output of the layer below; G_{l-1} is gathered by that layer's backward aggregation
-                G, _ = gemm_relu_colsum(dH, Wl, hl, out=self._tmp(("G", l), (dH.shape[0], Wl.shape[1]), gathered=True), colsum_out=self.db[l - 1])
+                out = self._tmp(("G", l), (dH.shape[0], Wl.shape[1]), gathered=True) if l else None
+                G = self._fused_tail(l, dH, Wl, hl, input_grad, out=out)
             else:
                 G = gemm(dH, Wl)
                 G, _, _ = bn_relu_bwd(hl, hl, G, relu=True)
@@ -2756,14 +2828,13 @@ class GatStack(_AttentionStack):
 
     def __init__(self, g, dims, negative_slope=0.2, seed=0, device="cuda", heads=None, fused=False):
         self.fused = bool(fused)
-        if self.fused and (g.rowptr_t is None or g.colidx_t is None):
-            raise capi.GnnxError(-1, "GatStack", "the graph has no transposed CSR (from_coo(..., transpose=True))")
+        if self.fused:
+            _need_transposed(g, "GatStack")
         self._bind(g)
         self.dims = list(dims)
         self.negative_slope = float(negative_slope)
-        L = len(dims) - 1
         self.heads = self._heads_per_layer(dims, heads)
-        self.W = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
+        self.W = _uniform_layers(seed, 2, list(zip(dims[1:], dims[:-1])), device)
         self.A, self.A_mask = [], []
         for l, Hh in enumerate(self.heads):   # [a_l; a_r] drawn as one [2, dims[l+1]] matrix, laid out in the blocks of the [2 Hh, Hh D] one
             D = dims[l + 1] // Hh
@@ -2772,13 +2843,9 @@ class GatStack(_AttentionStack):
             draw = uniform_pm1(seed + 2 * l + 1, (2, dims[l + 1]), scale=D ** -0.5, device=device)
             self.A.append((torch.cat([draw[0:1].expand(Hh, -1), draw[1:2].expand(Hh, -1)]) * mask).contiguous())
             self.A_mask.append(mask)
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.dW = [torch.zeros_like(w) for w in self.W]
-        self.dA = [torch.zeros_like(a) for a in self.A]
-        self.db = [torch.zeros_like(b) for b in self.b]
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        self.b = _zero_layers(dims[1:], device)
+        self.dW, self.dA, self.db = _zero_layers(self.W), _zero_layers(self.A), _zero_layers(self.b)
+        self._init_state()
 
     def params(self):
         return self.W + self.A + self.b
@@ -2821,9 +2888,7 @@ class GatStack(_AttentionStack):
         """dW, dA (masked to its blocks) and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         g, L, n = self.g, len(self.W), self.g.n
-        G = dOut
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        G = self._top_grad(dOut, have_last_bias_grad)
         for l in reversed(range(L)):
             Hh = self.heads[l]
             dER = self._tmp(("dER", Hh), (n, 2 * Hh))                                     # left half: del, right half: der
@@ -2841,10 +2906,7 @@ class GatStack(_AttentionStack):
             if Hh > 1:   # the entries outside the blocks are not parameters (one head: the mask is all ones)
                 binary("mul", self.dA[l], self.A_mask[l], out=self.dA[l])
             gemm(dH, h, transA=True, out=self.dW[l])
-            if l == 0:
-                G = gemm(dH, self.W[l]) if input_grad else None
-            else:   # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue
-                G, _ = gemm_relu_colsum(dH, self.W[l], h, colsum_out=self.db[l - 1])
+            G = self._fused_tail(l, dH, self.W[l], h, input_grad)   # h = relu output of the layer below
         return G
 
     def _backward_entries(self, l, G, dER):
@@ -2885,18 +2947,14 @@ class Gatv2Stack(_AttentionStack):
         self.dims = list(dims)
         self.negative_slope = float(negative_slope)
         self.share_weights = bool(share_weights)
-        L = len(dims) - 1
         self.heads = self._heads_per_layer(dims, heads)
         k = 1 if self.share_weights else 2
-        self.W = [uniform_pm1(seed + 2 * l, (k * dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.a = [uniform_pm1(seed + 2 * l + 1, (dims[l + 1],), scale=(dims[l + 1] // self.heads[l]) ** -0.5, device=device) for l in range(L)]
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.dW = [torch.zeros_like(w) for w in self.W]
-        self.da = [torch.zeros_like(a) for a in self.a]
-        self.db = [torch.zeros_like(b) for b in self.b]
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        self.W = _uniform_layers(seed, 2, [(k * o, i) for o, i in zip(dims[1:], dims[:-1])], device)
+        head_width = [o // Hh for o, Hh in zip(dims[1:], self.heads)]
+        self.a = _uniform_layers(seed + 1, 2, [(o,) for o in dims[1:]], device, scales=[D ** -0.5 for D in head_width])
+        self.b = _zero_layers(dims[1:], device)
+        self.dW, self.da, self.db = _zero_layers(self.W), _zero_layers(self.a), _zero_layers(self.b)
+        self._init_state()
 
     def params(self):
         return self.W + self.a + self.b
@@ -2938,9 +2996,7 @@ class Gatv2Stack(_AttentionStack):
         """dW, da and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).  have_last_bias_grad: db[L-1]
         was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         g, L, n = self.g, len(self.W), self.g.n
-        G = dOut
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        G = self._top_grad(dOut, have_last_bias_grad)
         for l in reversed(range(L)):
             h, Hlr, e, alpha, _ = self._saved[l]
             Hl, Hr = self._halves(Hlr, l)
@@ -2959,10 +3015,7 @@ class Gatv2Stack(_AttentionStack):
                              beta=1.0 if self.share_weights else 0.0, T_out=self._tmp(("T", l), (n, out)))   # the row side, and T
             colsum(self._buf[("T", l)], out=self.da[l])
             gemm(dHlr, h, transA=True, out=self.dW[l])
-            if l == 0:
-                G = gemm(dHlr, self.W[l]) if input_grad else None
-            else:   # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue
-                G, _ = gemm_relu_colsum(dHlr, self.W[l], h, colsum_out=self.db[l - 1])
+            G = self._fused_tail(l, dHlr, self.W[l], h, input_grad)   # h = relu output of the layer below
         return G
 
 
@@ -2992,17 +3045,12 @@ class SageStack(_Stack):
         if aggr not in ("mean", "max"):
             raise ValueError(f"aggr must be 'mean' or 'max', got {aggr!r}")
         self.dims, self.aggr = list(dims), aggr
-        L = len(dims) - 1
         self._bind(g)
-        self.W_s = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.W_n = [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.dW_s = [torch.zeros_like(w) for w in self.W_s]
-        self.dW_n = [torch.zeros_like(w) for w in self.W_n]
-        self.db = [torch.zeros_like(b) for b in self.b]
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        shapes = list(zip(dims[1:], dims[:-1]))
+        self.W_s, self.W_n = _uniform_layers(seed, 2, shapes, device), _uniform_layers(seed + 1, 2, shapes, device)
+        self.b = _zero_layers(dims[1:], device)
+        self.dW_s, self.dW_n, self.db = _zero_layers(self.W_s), _zero_layers(self.W_n), _zero_layers(self.b)
+        self._init_state()
 
     def _bind(self, g):
         """What the stack holds of the graph itself: the transpose map (max) or 1 / deg (mean)."""
@@ -3019,16 +3067,6 @@ class SageStack(_Stack):
     def grads(self):
         return self.dW_s + self.dW_n + self.db
 
-    def on_graph(self, g):
-        """This stack on another graph over the same vertices -- a sample of its neighbourhoods: a SageStack that SHARES this one's
-        parameters, gradients and scratch buffers (the same tensors and the same table, the gradient buffer's zeroed-rows mark
-        included: a step through either is a step of both) and has its own inv_deg / map_t.  The training surface of neighbour sampling:
-            net.on_graph(g.sample_neighbors(k, seed=epoch)).train_step(X, target, rows, lr)
-        while net.evaluate(...) keeps running on the full graph."""
-        if g.n != self.g.n:
-            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
-        return self._view(share_buf=True)._bind(g)
-
     def _aggregate(self, l, h):
         """(M, arg) of layer l: the neighbourhood's mean (arg None) or its maximum with the winning entries."""
         g = self.g
@@ -3041,8 +3079,7 @@ class SageStack(_Stack):
         """out += the aggregation's gradient with respect to h."""
         g = self.g
         if self.aggr == "mean":
-            if g.rowptr_t is None:
-                raise capi.GnnxError(-1, "SageStack", "the graph has no transposed CSR (from_coo(..., transpose=True))")
+            _need_transposed(g, "SageStack")
             return spmm(g.rowptr_t, g.colidx_t, dM, out=out, colscale=self.inv_deg, beta=1.0, plan=g.plan_t)
         return spmm_reduce_bwd(g.rowptr_t, g.colidx_t, self.map_t, arg, dM, out=out, beta=1.0)
 
@@ -3053,10 +3090,7 @@ class SageStack(_Stack):
             M, arg = self._aggregate(l, h)
             Z = gemm(h, self.W_s[l], transB=True, out=self._tmp(("Z", l), (n, self.dims[l + 1])))
             gemm(M, self.W_n[l], transB=True, out=Z, beta=1.0)
-            Y = self._tmp(("Y", l), (n, self.dims[l + 1]))
-            bias_add(Z, self.b[l], out=Y)
-            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
-                bn_relu_fwd(Y, relu=True, out=Y)
+            Y = self._bias_act(l, Z, out=self._tmp(("Y", l), (n, self.dims[l + 1])))
             saved.append((h, M, arg, Y))
             h = Y
         self._saved = saved
@@ -3066,9 +3100,7 @@ class SageStack(_Stack):
         """dW_s, dW_n and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         L, n = len(self.W_s), self.g.n
-        G = dOut
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        G = self._top_grad(dOut, have_last_bias_grad)
         for l in reversed(range(L)):
             h, M, arg, _ = self._saved[l]
             gemm(G, h, transA=True, out=self.dW_s[l])
@@ -3080,8 +3112,7 @@ class SageStack(_Stack):
             self._aggregate_bwd(l, dM, arg, dh)                                        # + through its neighbourhood
             if l == 0:
                 return dh
-            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l])))           # h = relu output of the layer below
-            colsum(G, out=self.db[l - 1])
+            G = self._relu_tail(l, h, dh)                                              # h = relu output of the layer below
         return G
 
     # ---- mini-batch steps on a SampledField: compact matrices of their own, neither _saved nor _buf is touched ----
@@ -3107,9 +3138,7 @@ class SageStack(_Stack):
             Hs = gather_rows(h, field.self_pos[l + 1])
             Z = gemm(Hs, self.W_s[l], transB=True)
             gemm(M, self.W_n[l], transB=True, out=Z, beta=1.0)
-            Y = bias_add(Z, self.b[l], out=Z)
-            if l + 1 < L:
-                bn_relu_fwd(Y, relu=True, out=Y)
+            Y = self._bias_act(l, Z, out=Z)
             saved.append((h, Hs, M, arg, Y))
             h = Y
         return saved
@@ -3146,8 +3175,7 @@ class SageStack(_Stack):
                 spmm(rpt, cit, dM, out=dh, colscale=field.inv_deg[l + 1], beta=1.0)
             else:
                 spmm_reduce_bwd(rpt, cit, field.map_t(l + 1), arg, dM, out=dh, beta=1.0)
-            G = relu_mask(h, dh)                                                         # h = relu output of the layer below
-            colsum(G, out=self.db[l - 1])
+            G = self._relu_tail(l, h, dh, buffered=False)                                # h = relu output of the layer below
         self.step(lr, weight_decay)
         return loss
 
@@ -3171,18 +3199,13 @@ class EdgeConvStack(_Stack):
         if k is not None and not 1 <= int(k) <= KNN_MAX_K:
             raise ValueError(f"k must be None or 1 .. {KNN_MAX_K}, got {k!r}")
         self.dims, self.k = list(dims), None if k is None else int(k)
-        L = len(dims) - 1
         self.graphs = None
         self._bind(g)
-        self.W_s = [uniform_pm1(seed + 2 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.W_n = [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.dW_s = [torch.zeros_like(w) for w in self.W_s]
-        self.dW_n = [torch.zeros_like(w) for w in self.W_n]
-        self.db = [torch.zeros_like(b) for b in self.b]
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        shapes = list(zip(dims[1:], dims[:-1]))
+        self.W_s, self.W_n = _uniform_layers(seed, 2, shapes, device), _uniform_layers(seed + 1, 2, shapes, device)
+        self.b = _zero_layers(dims[1:], device)
+        self.dW_s, self.dW_n, self.db = _zero_layers(self.W_s), _zero_layers(self.W_n), _zero_layers(self.b)
+        self._init_state()
 
     def _bind(self, g):
         """What the stack holds of the graph itself: the transpose map of a fixed graph; of a dynamic one only the row ownership."""
@@ -3196,12 +3219,6 @@ class EdgeConvStack(_Stack):
 
     def grads(self):
         return self.dW_s + self.dW_n + self.db
-
-    def on_graph(self, g):
-        """This stack on another graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch buffers."""
-        if g.n != self.g.n:
-            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
-        return self._view(share_buf=True)._bind(g)
 
     def _layer_graph(self, h):
         if self.k is None:
@@ -3218,9 +3235,7 @@ class EdgeConvStack(_Stack):
                                  arg_out=self._tmp(("arg", l), (n, self.dims[l + 1]), torch.int32))
             Z = gemm(h, self.W_s[l], transB=True, out=self._tmp(("Z", l), (n, self.dims[l + 1])))
             axpy(1.0, M, Z)
-            Y = bias_add(Z, self.b[l], out=self._tmp(("Y", l), (n, self.dims[l + 1])))
-            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
-                bn_relu_fwd(Y, relu=True, out=Y)
+            Y = self._bias_act(l, Z, out=self._tmp(("Y", l), (n, self.dims[l + 1])))
             saved.append((h, M, arg, Y))
             graphs.append(gl)
             h = Y
@@ -3231,9 +3246,7 @@ class EdgeConvStack(_Stack):
         """dW_s, dW_n and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         L, n = len(self.W_s), self.g.n
-        G = dOut
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        G = self._top_grad(dOut, have_last_bias_grad)
         for l in reversed(range(L)):
             h, _, arg, _ = self._saved[l]
             gl = self.graphs[l]
@@ -3247,8 +3260,7 @@ class EdgeConvStack(_Stack):
             gemm(dT, self.W_n[l], out=dh, beta=1.0)                                    # + through its neighbourhood
             if l == 0:
                 return dh
-            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, self.dims[l])))           # h = relu output of the layer below
-            colsum(G, out=self.db[l - 1])
+            G = self._relu_tail(l, h, dh)                                              # h = relu output of the layer below
         return G
 
 
@@ -3265,33 +3277,20 @@ class GineStack(_Stack):
 
     def __init__(self, g, dims, edge_dim, seed=0, device="cuda"):
         self.dims, self.edge_dim = list(dims), int(edge_dim)
-        L = len(dims) - 1
         self._bind(g)
-
-        def weights(k, rows, cols):
-            return [uniform_pm1(seed + 3 * l + k, (rows(l), cols(l)), scale=cols(l) ** -0.5, device=device) for l in range(L)]
-
-        def zeros(width):
-            return [torch.zeros(width(l), dtype=torch.float32, device=device) for l in range(L)]
-
-        self.W_e = weights(0, lambda l: dims[l], lambda l: self.edge_dim)
-        self.W_1 = weights(1, lambda l: dims[l + 1], lambda l: dims[l])
-        self.W_2 = weights(2, lambda l: dims[l + 1], lambda l: dims[l + 1])
-        self.b_e, self.b_1, self.b = zeros(lambda l: dims[l]), zeros(lambda l: dims[l + 1]), zeros(lambda l: dims[l + 1])
-        self.dW_e, self.dW_1, self.dW_2 = ([torch.zeros_like(w) for w in ws] for ws in (self.W_e, self.W_1, self.W_2))
-        self.db_e, self.db_1, self.db = ([torch.zeros_like(b) for b in bs] for bs in (self.b_e, self.b_1, self.b))
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        d_in, d_out = dims[:-1], dims[1:]
+        self.W_e = _uniform_layers(seed, 3, [(i, self.edge_dim) for i in d_in], device)
+        self.W_1 = _uniform_layers(seed + 1, 3, list(zip(d_out, d_in)), device)
+        self.W_2 = _uniform_layers(seed + 2, 3, list(zip(d_out, d_out)), device)
+        self.b_e, self.b_1, self.b = _zero_layers(d_in, device), _zero_layers(d_out, device), _zero_layers(d_out, device)
+        self.dW_e, self.dW_1, self.dW_2 = _zero_layers(self.W_e), _zero_layers(self.W_1), _zero_layers(self.W_2)
+        self.db_e, self.db_1, self.db = _zero_layers(self.b_e), _zero_layers(self.b_1), _zero_layers(self.b)
+        self._init_state()
 
     def _bind(self, g):
         """What the stack holds of the graph itself: its edge attributes and the entry -> edge maps of both patterns."""
-        if getattr(g, "edge_attr", None) is None:
-            raise capi.GnnxError(-1, "GineStack", "the graph has no edge attributes (g.set_edge_attr(src, dst, attr))")
-        if int(g.edge_attr.shape[1]) != self.edge_dim:
-            raise ValueError(f"the graph's edge attributes have {int(g.edge_attr.shape[1])} columns, the stack was built for {self.edge_dim}")
+        self.entry_edge, self.entry_edge_t = _edge_maps(g, self.edge_dim, "GineStack")
         self.g = g
-        self.entry_edge, self.entry_edge_t = g.entry_edge, g.entry_edge_t
         return self
 
     def params(self):
@@ -3299,13 +3298,6 @@ class GineStack(_Stack):
 
     def grads(self):
         return self.dW_e + self.dW_1 + self.dW_2 + self.db_e + self.db_1 + self.db
-
-    def on_graph(self, g):
-        """This stack on another attributed graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch
-        buffers."""
-        if g.n != self.g.n:
-            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
-        return self._view(share_buf=True)._bind(g)
 
     def forward(self, X):
         L, g = len(self.W_1), self.g
@@ -3321,9 +3313,7 @@ class GineStack(_Stack):
             bias_add(A, self.b_1[l], out=A)
             bn_relu_fwd(A, relu=True, out=A)
             Y = gemm(A, self.W_2[l], transB=True, out=self._tmp(("Y", l), (n, d1)))
-            bias_add(Y, self.b[l], out=Y)
-            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
-                bn_relu_fwd(Y, relu=True, out=Y)
+            self._bias_act(l, Y, out=Y)
             saved.append((h, El, U, A))
             h = Y
         self._saved = saved
@@ -3334,9 +3324,7 @@ class GineStack(_Stack):
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         L, g = len(self.W_1), self.g
         n, ne = g.n, int(g.edge_attr.shape[0])
-        G = dOut
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        G = self._top_grad(dOut, have_last_bias_grad)
         for l in reversed(range(L)):
             d0, d1 = self.dims[l], self.dims[l + 1]
             h, El, U, A = self._saved[l]
@@ -3355,8 +3343,7 @@ class GineStack(_Stack):
             dh = spmm_edge(g.rowptr_t, g.colidx_t, None, dE, eidx=self.entry_edge_t, msg="add", out=dU, beta=1.0, n_cols=n)   # self + neighbours
             if l == 0:
                 return dh
-            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, d0)))               # h = relu output of the layer below
-            colsum(G, out=self.db[l - 1])
+            G = self._relu_tail(l, h, dh)                                        # h = relu output of the layer below
         return G
 
 
@@ -3383,32 +3370,21 @@ class TransformerStack(_Stack):
 
     def __init__(self, g, dims, heads=None, edge_dim=None, global_attention=False, seed=0, device="cuda"):
         self.dims, self.edge_dim = list(dims), None if edge_dim is None else int(edge_dim)
-        L = len(dims) - 1
         self.heads = _AttentionStack._heads_per_layer(dims, heads)
         self.n_slabs = 7 if global_attention else 4   # q | k | v | skip, then the global branch's q' | k' | v'
         self._bind(g)
-        self.W = [uniform_pm1(seed + 2 * l, (self.n_slabs * dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.W_e = [] if edge_dim is None else [uniform_pm1(seed + 2 * l + 1, (dims[l + 1], self.edge_dim), scale=self.edge_dim ** -0.5, device=device)
-                                                for l in range(L)]
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.dW, self.dW_e, self.db = ([torch.zeros_like(p) for p in ps] for ps in (self.W, self.W_e, self.b))
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        self.W = _uniform_layers(seed, 2, [(self.n_slabs * o, i) for o, i in zip(dims[1:], dims[:-1])], device)
+        self.W_e = [] if edge_dim is None else _uniform_layers(seed + 1, 2, [(o, self.edge_dim) for o in dims[1:]], device)
+        self.b = _zero_layers(dims[1:], device)
+        self.dW, self.dW_e, self.db = _zero_layers(self.W), _zero_layers(self.W_e), _zero_layers(self.b)
+        self._init_state()
 
     def _bind(self, g):
         """What the stack holds of the graph itself: with edge_dim, the entry -> edge maps of both patterns."""
-        if g.rowptr_t is None or g.colidx_t is None:
-            raise capi.GnnxError(-1, "TransformerStack", "the graph has no transposed CSR (from_coo(..., transpose=True))")
+        _need_transposed(g, "TransformerStack")
         if self.n_slabs == 7 and not isinstance(g, GraphBatch):
             raise TypeError("global_attention=True needs a GraphBatch: every vertex attends to the vertices of its own graph")
-        self.entry_edge = self.entry_edge_t = None
-        if self.edge_dim is not None:
-            if getattr(g, "edge_attr", None) is None:
-                raise capi.GnnxError(-1, "TransformerStack", "the graph has no edge attributes (g.set_edge_attr(src, dst, attr))")
-            if int(g.edge_attr.shape[1]) != self.edge_dim:
-                raise ValueError(f"the graph's edge attributes have {int(g.edge_attr.shape[1])} columns, the stack was built for {self.edge_dim}")
-            self.entry_edge, self.entry_edge_t = g.entry_edge, g.entry_edge_t
+        self.entry_edge, self.entry_edge_t = (None, None) if self.edge_dim is None else _edge_maps(g, self.edge_dim, "TransformerStack")
         self.g = g
         return self
 
@@ -3417,12 +3393,6 @@ class TransformerStack(_Stack):
 
     def grads(self):
         return self.dW + self.dW_e + self.db
-
-    def on_graph(self, g):
-        """This stack on another graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch buffers."""
-        if g.n != self.g.n:
-            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
-        return self._view(share_buf=True)._bind(g)
 
     @staticmethod
     def _slabs(P, count):
@@ -3464,8 +3434,7 @@ class TransformerStack(_Stack):
         dP = [self._tmp(("dP", l), (n, ns * self.dims[l + 1])) for l in range(L)]   # dq | dk | dv | dZ (| dq' | dk' | dv') of every layer
         G = self._slabs(dP[L - 1], ns)[3]
         capi.call("gnnx_memcpy2d_d2d", _ptr(G), 4 * _ld(G), _ptr(dOut), 4 * _ld(dOut), 4 * self.dims[L], n, _stream())
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        self._top_grad(G, have_last_bias_grad)
         for l in reversed(range(L)):
             F, Hh = self.dims[l + 1], self.heads[l]
             h, P, El, Y, rowmax, rowsum, glob = self._saved[l]
@@ -3486,10 +3455,9 @@ class TransformerStack(_Stack):
             if dE is not None:
                 gemm(dE, g.edge_attr, transA=True, out=self.dW_e[l])
             gemm(dP[l], h, transA=True, out=self.dW[l])
-            if l == 0:
-                return gemm(dP[l], self.W[l]) if input_grad else None
             # h = relu output of the layer below: its mask and the bias gradient in the product's epilogue, straight into that layer's slab
-            gemm_relu_colsum(dP[l], self.W[l], h, out=self._slabs(dP[l - 1], ns)[3], colsum_out=self.db[l - 1])
+            G = self._fused_tail(l, dP[l], self.W[l], h, input_grad, out=self._slabs(dP[l - 1], ns)[3] if l else None)
+        return G
 
 
 class RgcnStack(_Stack):
@@ -3515,15 +3483,12 @@ class RgcnStack(_Stack):
         self.n_slabs = B = self.n_relations if n_bases is None else self.n_bases
         L = len(dims) - 1
         self._bind(g)
-        self.W_0 = [uniform_pm1(seed + 3 * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        self.V = [uniform_pm1(seed + 3 * l + 1, (dims[l + 1], B * dims[l]), scale=(B * dims[l]) ** -0.5, device=device) for l in range(L)]
-        self.C = [] if n_bases is None else [uniform_pm1(seed + 3 * l + 2, (self.n_relations, B), device=device) for l in range(L)]
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.dW_0, self.dV, self.dC = ([torch.zeros_like(w) for w in ws] for ws in (self.W_0, self.V, self.C))
-        self.db = [torch.zeros_like(b) for b in self.b]
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        self.W_0 = _uniform_layers(seed, 3, list(zip(dims[1:], dims[:-1])), device)
+        self.V = _uniform_layers(seed + 1, 3, [(o, B * i) for o, i in zip(dims[1:], dims[:-1])], device)
+        self.C = [] if n_bases is None else _uniform_layers(seed + 2, 3, [(self.n_relations, B)] * L, device, scales=[1.0] * L)
+        self.b = _zero_layers(dims[1:], device)
+        self.dW_0, self.dV, self.dC, self.db = (_zero_layers(ps) for ps in (self.W_0, self.V, self.C, self.b))
+        self._init_state()
 
     def _bind(self, g):
         """What the stack holds of the graph itself: the entry types and weights of both patterns and the type-sorted entry order."""
@@ -3542,13 +3507,6 @@ class RgcnStack(_Stack):
     def grads(self):
         return self.dW_0 + self.dV + self.db + self.dC
 
-    def on_graph(self, g):
-        """This stack on another typed graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch
-        buffers."""
-        if g.n != self.g.n:
-            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
-        return self._view(share_buf=True)._bind(g)
-
     def _coeff(self, l):
         return self.C[l] if self.C else None
 
@@ -3561,10 +3519,7 @@ class RgcnStack(_Stack):
                            out=self._tmp(("M", l), (g.n, B * d0)))
             Z = gemm(h, self.W_0[l], transB=True, out=self._tmp(("Z", l), (g.n, d1)))
             gemm(M, self.V[l], transB=True, out=Z, beta=1.0)
-            Y = self._tmp(("Y", l), (g.n, d1))
-            bias_add(Z, self.b[l], out=Y)
-            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
-                bn_relu_fwd(Y, relu=True, out=Y)
+            Y = self._bias_act(l, Z, out=self._tmp(("Y", l), (g.n, d1)))
             saved.append((h, M))
             h = Y
         self._saved = saved
@@ -3574,9 +3529,7 @@ class RgcnStack(_Stack):
         """The gradient of every parameter from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         L, g, B = len(self.W_0), self.g, self.n_slabs
-        G = dOut
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        G = self._top_grad(dOut, have_last_bias_grad)
         for l in reversed(range(L)):
             d0 = self.dims[l]
             h, M = self._saved[l]
@@ -3596,8 +3549,7 @@ class RgcnStack(_Stack):
                            out=dh, beta=1.0)                                                      # + through its neighbourhood
             if l == 0:
                 return dh
-            G = relu_mask(h, dh, out=self._tmp(("G", l), (g.n, d0)))                             # h = relu output of the layer below
-            colsum(G, out=self.db[l - 1])
+            G = self._relu_tail(l, h, dh)                                                        # h = relu output of the layer below
         return G
 
 
@@ -3627,23 +3579,19 @@ class PnaStack(_Stack):
         if not scalers or any(k not in PNA_SCALERS for k in scalers) or len(set(scalers)) != len(scalers):
             raise ValueError(f"scalers must be distinct names out of {PNA_SCALERS}, got {scalers!r}")
         self.dims, self.scalers, self.eps = list(dims), scalers, float(eps)
-        L, K = len(dims) - 1, len(scalers)
+        K = len(scalers)
         logd = _log_degrees(g.rowptr)
         self.delta = float(logd.double().mean()) if g.n else 0.0
         if not self.delta > 0.0:     # a graph without entries: every scaler is the identity's
             self.delta = 1.0
         self._bind(g)
-        self.W_s = [uniform_pm1(seed + (K + 1) * l, (dims[l + 1], dims[l]), scale=dims[l] ** -0.5, device=device) for l in range(L)]
-        # W_n[l][k]: the weight of scaler k; the stack's parameter list holds them layer by layer
-        self.W_n = [[uniform_pm1(seed + (K + 1) * l + 1 + k, (dims[l + 1], 4 * dims[l]), scale=(4 * K * dims[l]) ** -0.5, device=device)
-                     for k in range(K)] for l in range(L)]
-        self.b = [torch.zeros(dims[l + 1], dtype=torch.float32, device=device) for l in range(L)]
-        self.dW_s = [torch.zeros_like(w) for w in self.W_s]
-        self.dW_n = [[torch.zeros_like(w) for w in ws] for ws in self.W_n]
-        self.db = [torch.zeros_like(b) for b in self.b]
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        self.W_s = _uniform_layers(seed, K + 1, list(zip(dims[1:], dims[:-1])), device)
+        # W_n[l][k]: the weight of scaler k, seed + (K + 1) l + 1 + k; the stack's parameter list holds them layer by layer
+        wide, scales = [(o, 4 * i) for o, i in zip(dims[1:], dims[:-1])], [(4 * K * i) ** -0.5 for i in dims[:-1]]
+        self.W_n = [list(ws) for ws in zip(*(_uniform_layers(seed + 1 + k, K + 1, wide, device, scales) for k in range(K)))]
+        self.b = _zero_layers(dims[1:], device)
+        self.dW_s, self.dW_n, self.db = _zero_layers(self.W_s), [_zero_layers(ws) for ws in self.W_n], _zero_layers(self.b)
+        self._init_state()
 
     def _bind(self, g):
         """What the stack holds of the graph itself: the transpose map and the scaler vectors of ITS degrees under the stack's delta."""
@@ -3662,13 +3610,6 @@ class PnaStack(_Stack):
     def grads(self):
         return self.dW_s + [w for ws in self.dW_n for w in ws] + self.db
 
-    def on_graph(self, g):
-        """This stack on another graph over the same vertices (SageStack.on_graph): shared parameters, gradients and scratch buffers;
-        delta stays, the scaler vectors follow the new graph's degrees."""
-        if g.n != self.g.n:
-            raise ValueError(f"the graph has {g.n} vertices, the stack was built for {self.g.n}")
-        return self._view(share_buf=True)._bind(g)
-
     def forward(self, X):
         L, g, n = len(self.W_s), self.g, self.g.n
         saved, h = [], X
@@ -3681,10 +3622,7 @@ class PnaStack(_Stack):
             for k, s in enumerate(self.scale):
                 Ms = M if s is None else rowscale(M, s, out=self._tmp(("Ms", l), (n, 4 * d0)))
                 gemm(Ms, self.W_n[l][k], transB=True, out=Z, beta=1.0)
-            Y = self._tmp(("Y", l), (n, d1))
-            bias_add(Z, self.b[l], out=Y)
-            if l + 1 < L:   # only relu(Z + b) is kept: its sign is the mask
-                bn_relu_fwd(Y, relu=True, out=Y)
+            Y = self._bias_act(l, Z, out=self._tmp(("Y", l), (n, d1)))
             saved.append((h, M, amin, amax))
             h = Y
         self._saved = saved
@@ -3694,9 +3632,7 @@ class PnaStack(_Stack):
         """dW_s, dW_n and db of every layer from dOut = dL/dlogits; returns dL/dX (None with input_grad=False).
         have_last_bias_grad: db[L-1] was already written by the loss kernel (softmax_ce_rows(..., colsum_out=net.db[-1]))."""
         L, g, n = len(self.W_s), self.g, self.g.n
-        G = dOut
-        if not have_last_bias_grad:
-            colsum(G, out=self.db[L - 1])
+        G = self._top_grad(dOut, have_last_bias_grad)
         for l in reversed(range(L)):
             d0, d1 = self.dims[l], self.dims[l + 1]
             h, M, amin, amax = self._saved[l]
@@ -3714,8 +3650,7 @@ class PnaStack(_Stack):
             spmm_pna_bwd(g.rowptr_t, g.colidx_t, self.map_t, g.rowptr, h, M, amin, amax, dM, out=dh, beta=1.0)   # + its neighbourhood
             if l == 0:
                 return dh
-            G = relu_mask(h, dh, out=self._tmp(("G", l), (n, d0)))                       # h = relu output of the layer below
-            colsum(G, out=self.db[l - 1])
+            G = self._relu_tail(l, h, dh)                                                # h = relu output of the layer below
         return G
 
 
@@ -3954,7 +3889,7 @@ class GraphBatch(CsrGraph):
 
 
 class GraphClassifier(_Model):
-    """One answer per GRAPH of a GraphBatch: a readout and a linear head over any of the three stacks,
+    """One answer per GRAPH of a GraphBatch: a readout and a linear head over any stack,
         Z = segment_pool(net.forward(X), pool) [B, dims[-1]];   logits = Z W_c^T + b_c   [B, n_classes],
     trained through the readout.  forward / backward / step / train_step / evaluate (no row selection: every graph of the batch counts),
     and on_batch for an epoch over mini-batches of any size.  Every operation is a C-ABI call: the stack's own, segment_pool, gemm,
@@ -3979,9 +3914,7 @@ class GraphClassifier(_Model):
         self.b_c = torch.zeros(self.n_classes, dtype=torch.float32, device=dev)
         self.dW_c = torch.zeros_like(self.W_c)
         self.db_c = torch.zeros_like(self.b_c)
-        self._saved = None
-        self._buf = {}
-        self._opt = [None]
+        self._init_state()
 
     def on_batch(self, batch):
         """This classifier on another GraphBatch, of ANY vertex and graph count: it shares W_c, b_c, their gradients and the stack's

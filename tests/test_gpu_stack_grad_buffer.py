@@ -8,7 +8,9 @@ when a selection object is first used and remembers that object.  Bars, all bit 
   (b) a step with a second selection object over other rows leaves the buffer zero outside THOSE rows and the parameters of the step
       composed by hand with a fresh zero buffer (GcnStack has this in test_gpu_masked.py);
   (c) a SageStack and its on_graph view share the buffer AND the mark: a step through the view, then one through the stack, with the same
-      row object, equal plain steps of stacks built on the two graphs; grad_buffer() of the view drops the mark for the stack too."""
+      row object, equal plain steps of stacks built on the two graphs; grad_buffer() of the view drops the mark for the stack too;
+  (d) on_graph is _Stack's one method: GcnStack and GatStack (heads [2, 1]; fused), which never had a copy, give through it the bits of
+      _view()._bind(g2) on the same parameter tensors, and refuse a graph of another vertex count (N = 12, dims [5, 6, 3])."""
 import importlib
 
 import numpy as np
@@ -155,3 +157,40 @@ def test_a_sage_view_shares_the_buffer_and_its_mark(env, task, kind):
     assert_same_params(env, net, on_g, "after a full-row write through the view")
     assert_zero_outside(env, net, mask, kind)
     assert view._buf is net._buf
+
+
+# ---- on_graph is _Stack's: the stacks that had no copy of their own inherit it (n = 12, dims [5, 6, 3]) -------------------------------
+SMALL_N, SMALL_DIMS = 12, [5, 6, 3]
+INHERITED = {"gcn": ("GcnStack", {}), "gat-heads": ("GatStack", dict(heads=HEADS)), "gat-fused": ("GatStack", dict(fused=True))}
+
+
+@pytest.fixture(scope="module")
+def small(env):
+    ops = env["ops"]
+    src, dst = synth.uniform_edges(47, SMALL_N, 40)
+    g = ops.CsrGraph.from_coo(dev(env, src), dev(env, dst), SMALL_N)
+    g2 = g.sample_neighbors(2, seed=5)                       # the same vertices, other neighbourhoods
+    assert g2.n == g.n and int(g2.nnz) < int(g.nnz)
+    src3, dst3 = synth.uniform_edges(48, SMALL_N + 1, 40)
+    g3 = ops.CsrGraph.from_coo(dev(env, src3), dev(env, dst3), SMALL_N + 1)
+    return dict(g=g, g2=g2, g3=g3, X=dev(env, synth.uniform_pm1(49, (SMALL_N, SMALL_DIMS[0]))))
+
+
+@pytest.mark.parametrize("kind", sorted(INHERITED))
+def test_the_inherited_on_graph_is_the_view_bound_to_the_graph(env, small, kind):
+    ops = env["ops"]
+    name, kwargs = INHERITED[kind]
+    cls = getattr(ops, name)
+    assert cls.on_graph is ops._Stack.on_graph
+    g, g2, X = small["g"], small["g2"], small["X"]
+    net = cls(g, SMALL_DIMS, seed=7, **kwargs)
+    on_g = net.forward(X).clone()
+    view = net.on_graph(g2)
+    assert type(view) is cls and view.g is g2 and net.g is g
+    assert view.W[0] is net.W[0] and view._buf is net._buf
+    got = view.forward(X).clone()
+    want = net._view()._bind(g2).forward(X)
+    assert tuple(got.shape) == (SMALL_N, SMALL_DIMS[-1]) and env["torch"].equal(got, want)
+    assert not env["torch"].equal(got, on_g)                 # the other graph's neighbourhoods were used
+    with pytest.raises(ValueError, match=f"the graph has {SMALL_N + 1} vertices, the stack was built for {SMALL_N}"):
+        net.on_graph(small["g3"])
