@@ -1502,6 +1502,76 @@ def segment_attention_bwd_cols(segptr, G, Q, K, V, n_heads, rowmax, rowsum, dot,
     return dK, dV
 
 
+def _segment_cross_attn_args(where, segptr, qsegptr, n_heads, qmats, kmats, scale):
+    """What the three cross segment attention calls share: both checked segment arrays (the same length), the checked [n_q, H*D] query-side
+    and [n_rows, H*D] key-side matrices ((name, tensor) pairs; the first of each fixes the row count) and the scale (default D ** -0.5)."""
+    for name, p in (("segptr", segptr), ("qsegptr", qsegptr)):
+        if p.dtype != torch.int32 or p.dim() != 1 or p.numel() < 1 or not p.is_contiguous():
+            raise capi.GnnxError(-2, where, f"{name} must be a contiguous int32 [n_seg + 1] array, got {tuple(p.shape)} {p.dtype}")
+    if qsegptr.numel() != segptr.numel():
+        raise capi.GnnxError(-2, where, f"qsegptr has {qsegptr.numel()} entries, segptr {segptr.numel()}")
+    for name, t in (qmats[0], kmats[0]):
+        if t.dim() != 2:
+            raise capi.GnnxError(-2, where, f"{name} must be a 2-D matrix, got {tuple(t.shape)}")
+    n_q, F = (int(v) for v in qmats[0][1].shape)
+    n_rows = int(kmats[0][1].shape[0])
+    D = _heads_of(qmats[0][1], n_heads, where)
+    for mats, rows in ((qmats, n_q), (kmats, n_rows)):
+        for name, t in mats:
+            _gat_matrix(where, name, t, rows, F)
+    return int(segptr.numel() - 1), n_rows, n_q, F, D, float(D ** -0.5 if scale is None else scale)
+
+
+def segment_cross_attention(segptr, qsegptr, Q, K, V, n_heads, scale=None, out=None, stats_out=None):
+    """gnnx_segment_cross_attn_f32: the queries of segment g (rows qsegptr[g] .. qsegptr[g+1] - 1 of Q) attend over the keys of segment g
+    (rows segptr[g] .. segptr[g+1] - 1 of K and V) on the matrix cores, a workgroup of four wavefronts per 32 queries: made for a few
+    queries per graph over many vertices --
+        Y[i] = sum_j alpha_ij V[j],  alpha = softmax over the keys j of i's segment of scale * <Q[i], K[j]> per head.
+    Q: [n_q, H*D]; K, V: [n_rows, H*D]; each may be a column slab of a wider matrix; D <= 128.  Returns (Y [n_q, H*D], rowmax, rowsum),
+    the statistics as [n_q, H] (stats_out = (rowmax, rowsum) to write them into the caller's arrays).  A query without keys gets Y = 0,
+    rowmax = -inf, rowsum = 0."""
+    where = "segment_cross_attention"
+    n_seg, n_rows, n_q, F, D, scale = _segment_cross_attn_args(where, segptr, qsegptr, n_heads, [("Q", Q)], [("K", K), ("V", V)], scale)
+    dev = Q.device
+    out = _attn_out(where, "out", out, n_q, F, dev)
+    rowmax, rowsum = stats_out if stats_out is not None else (torch.empty((n_q, n_heads), dtype=torch.float32, device=dev) for _ in range(2))
+    capi.call("gnnx_segment_cross_attn_f32", n_seg, n_rows, _ptr(segptr), n_q, _ptr(qsegptr), n_heads, D, scale, _ptr(Q), _ld(Q), _ptr(K), _ld(K),
+              _ptr(V), _ld(V), _ptr(out), _ld(out), _gat_stat(rowmax, n_q, n_heads, "rowmax", where), _gat_stat(rowsum, n_q, n_heads, "rowsum", where),
+              _stream())
+    return out, rowmax, rowsum
+
+
+def segment_cross_attention_bwd_rows(segptr, qsegptr, G, Q, K, V, Y, n_heads, rowmax, rowsum, scale=None, dq_out=None, dot_out=None):
+    """gnnx_segment_cross_attn_bwd_rows_f32: (dQ [n_q, H*D], dot [n_q, H]) from G = dL/dY, the forward's operands, its Y and its statistics.
+    dot goes to segment_cross_attention_bwd_cols."""
+    where = "segment_cross_attention_bwd_rows"
+    n_seg, n_rows, n_q, F, D, scale = _segment_cross_attn_args(where, segptr, qsegptr, n_heads, [("G", G), ("Q", Q), ("Y", Y)], [("K", K), ("V", V)],
+                                                               scale)
+    dev = Q.device
+    dQ = _attn_out(where, "dq_out", dq_out, n_q, F, dev)
+    dot = torch.empty((n_q, n_heads), dtype=torch.float32, device=dev) if dot_out is None else dot_out
+    capi.call("gnnx_segment_cross_attn_bwd_rows_f32", n_seg, n_rows, _ptr(segptr), n_q, _ptr(qsegptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q),
+              _ld(Q), _ptr(K), _ld(K), _ptr(V), _ld(V), _ptr(Y), _ld(Y), _gat_stat(rowmax, n_q, n_heads, "rowmax", where),
+              _gat_stat(rowsum, n_q, n_heads, "rowsum", where), _ptr(dQ), _ld(dQ), _gat_stat(dot, n_q, n_heads, "dot_out", where), _stream())
+    return dQ, dot
+
+
+def segment_cross_attention_bwd_cols(segptr, qsegptr, G, Q, K, V, n_heads, rowmax, rowsum, dot, scale=None, dk_out=None, dv_out=None, beta=0.0):
+    """gnnx_segment_cross_attn_bwd_cols_f32: (dK, dV), both [n_rows, H*D], with dV[j] = beta*dV[j] + sum_i alpha_ij G[i] and
+    dK[j] = beta*dK[j] + scale * sum_i ds_ij Q[i] over the queries i of j's segment; dot is segment_cross_attention_bwd_rows'."""
+    where = "segment_cross_attention_bwd_cols"
+    n_seg, n_rows, n_q, F, D, scale = _segment_cross_attn_args(where, segptr, qsegptr, n_heads, [("G", G), ("Q", Q)], [("K", K), ("V", V)], scale)
+    dev = Q.device
+    if beta and (dk_out is None or dv_out is None):
+        raise capi.GnnxError(-2, where, "beta = 1 adds onto dk_out and dv_out, which were not given")
+    dK, dV = _attn_out(where, "dk_out", dk_out, n_rows, F, dev), _attn_out(where, "dv_out", dv_out, n_rows, F, dev)
+    capi.call("gnnx_segment_cross_attn_bwd_cols_f32", n_seg, n_rows, _ptr(segptr), n_q, _ptr(qsegptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q),
+              _ld(Q), _ptr(K), _ld(K), _ptr(V), _ld(V), _gat_stat(rowmax, n_q, n_heads, "rowmax", where),
+              _gat_stat(rowsum, n_q, n_heads, "rowsum", where), _gat_stat(dot, n_q, n_heads, "dot", where), float(beta), _ptr(dK), _ld(dK), _ptr(dV),
+              _ld(dV), _stream())
+    return dK, dV
+
+
 REDUCE_OPS = {"max": 0, "min": 1}   # GNNX_REDUCE_MAX / GNNX_REDUCE_MIN
 
 
@@ -3888,6 +3958,20 @@ class GraphBatch(CsrGraph):
         return self._batch
 
 
+class AttentionReadout:
+    """A value of GraphClassifier's `pool` option: the learned attention readout (Set Transformer's PMA, GMT) -- n_seeds learned query
+    rows per graph attend over that graph's vertices with `heads` heads (ops.segment_cross_attention).  A descriptor: the parameters
+    live in the classifier."""
+
+    def __init__(self, heads=1, n_seeds=1):
+        self.heads, self.n_seeds = int(heads), int(n_seeds)
+        if self.heads < 1 or self.n_seeds < 1:
+            raise ValueError(f"heads and n_seeds must be at least 1, got {heads!r} and {n_seeds!r}")
+
+    def __repr__(self):
+        return f"AttentionReadout(heads={self.heads}, n_seeds={self.n_seeds})"
+
+
 class GraphClassifier(_Model):
     """One answer per GRAPH of a GraphBatch: a readout and a linear head over any stack,
         Z = segment_pool(net.forward(X), pool) [B, dims[-1]];   logits = Z W_c^T + b_c   [B, n_classes],
@@ -3896,60 +3980,117 @@ class GraphClassifier(_Model):
     bias_add, softmax_ce (db_c from the loss kernel), segment_pool_bwd into net.grad_buffer(), sgd_step.  No atomics on any value; the
     same bits every run.
 
+    pool=AttentionReadout(heads, n_seeds) is the learned readout, with F = dims[-1], S = n_seeds, seeds P [S, F], W_k, W_v [F, F], b_k, b_v:
+        K = H W_k^T + b_k;  V = H W_v^T + b_v;  Q = P repeated per graph [B S, F];  Y = segment_cross_attention(graph_ptr, S arange(B + 1), Q, K, V)
+        Z = Y viewed as [B, S F];   logits = Z W_c^T + b_c,  W_c [n_classes, S F],
+    trained through segment_cross_attention_bwd_rows / _bwd_cols (dP = the sum of dQ over the graphs).  The new parameters stand behind
+    W_c, b_c in params() / grads().  A graph without vertices reads out Z = 0.
+
     The stack is bound to the batch with net._view()._bind(batch), for any vertex count: a stack of the same class on the same parameter
     and gradient tensors, with what its _bind derives from the batch and scratch buffers of its own (they are shaped by the vertex count)."""
 
     def __init__(self, net, batch, n_classes, pool="mean", seed=0):
-        if pool not in POOL_OPS:
-            raise ValueError(f"pool must be 'sum', 'mean' or 'max', got {pool!r}")
+        att = pool if isinstance(pool, AttentionReadout) else None
+        if att is None and pool not in POOL_OPS:
+            raise ValueError(f"pool must be 'sum', 'mean', 'max' or an ops.AttentionReadout, got {pool!r}")
+        if att is not None and isinstance(net, _Stack) and (net.dims[-1] % att.heads or net.dims[-1] // att.heads > 128):
+            raise ValueError(f"{att!r} needs dims[-1] = {net.dims[-1]} to split into {att.heads} heads of at most 128 columns")
         if not isinstance(batch, GraphBatch):
             raise TypeError("batch must be a GraphBatch")
         if not isinstance(net, _Stack):
             raise TypeError(f"GcnStack, GatStack or SageStack expected, got {type(net).__name__}")
+        d = net.dims[-1]
         self.net = net if net.g is batch else net._view()._bind(batch)
         self.batch, self.pool, self.n_classes = batch, pool, int(n_classes)
-        d = self.net.dims[-1]
         dev = batch.graph_ptr.device
-        self.W_c = uniform_pm1(seed + 1000, (self.n_classes, d), scale=d ** -0.5, device=dev)
+        dz = d * (att.n_seeds if att is not None else 1)
+        self.W_c = uniform_pm1(seed + 1000, (self.n_classes, dz), scale=dz ** -0.5, device=dev)
         self.b_c = torch.zeros(self.n_classes, dtype=torch.float32, device=dev)
         self.dW_c = torch.zeros_like(self.W_c)
         self.db_c = torch.zeros_like(self.b_c)
+        self._att, self._datt = [], []
+        if att is not None:   # P, W_k, b_k, W_v, b_v and their gradients
+            self._att = _uniform_layers(seed + 1001, 1, [(att.n_seeds, d), (d, d), (d,), (d, d), (d,)], dev, scales=[1.0, d ** -0.5, 0.0, d ** -0.5, 0.0])
+            self._datt = _zero_layers(self._att)
+            self._bind_queries()
         self._init_state()
+
+    def _bind_queries(self):
+        """What the attention readout derives from its batch: the seed of every query row and the query segments, S per graph."""
+        B, S, dev = self.batch.n_graphs, self.pool.n_seeds, self.batch.graph_ptr.device
+        self._qidx = (torch.arange(B * S, dtype=torch.int32, device=dev) % S).contiguous()
+        self._qsegptr = torch.arange(B + 1, dtype=torch.int32, device=dev) * S
+        return self
 
     def on_batch(self, batch):
         """This classifier on another GraphBatch, of ANY vertex and graph count: it shares W_c, b_c, their gradients and the stack's
-        parameters and gradients (the same tensors), and binds the stack to the new graph:
+        parameters and gradients (the same tensors; the attention readout's too), and binds the stack to the new graph:
             for b in batches: clf.on_batch(b).train_step(X_b, target_b, lr)"""
         if not isinstance(batch, GraphBatch):
             raise TypeError("batch must be a GraphBatch")
-        return self._view(net=self.net._view()._bind(batch), batch=batch)
+        view = self._view(net=self.net._view()._bind(batch), batch=batch)
+        return view._bind_queries() if self._att else view
 
     def params(self):
-        return self.net.params() + [self.W_c, self.b_c]
+        return self.net.params() + [self.W_c, self.b_c] + self._att
 
     def grads(self):
-        return self.net.grads() + [self.dW_c, self.db_c]
+        return self.net.grads() + [self.dW_c, self.db_c] + self._datt
+
+    def _attend(self, H):
+        """The attention readout's Z [B, S F] from the stack's output H; Q, K, V, Y and the statistics are kept for backward."""
+        B, F, S, Hh, n = self.batch.n_graphs, self.net.dims[-1], self.pool.n_seeds, self.pool.heads, int(H.shape[0])
+        P, W_k, b_k, W_v, b_v = self._att
+        K = bias_add(gemm(H, W_k, transB=True, out=self._tmp("K", (n, F))), b_k, out=self._tmp("K", (n, F)))
+        V = bias_add(gemm(H, W_v, transB=True, out=self._tmp("V", (n, F))), b_v, out=self._tmp("V", (n, F)))
+        Q = gather_rows(P, self._qidx, out=self._tmp("Q", (B * S, F)))
+        Y, m, z = segment_cross_attention(self.batch.graph_ptr, self._qsegptr, Q, K, V, Hh, out=self._tmp("Y", (B * S, F)),
+                                          stats_out=(self._tmp("m", (B * S, Hh)), self._tmp("z", (B * S, Hh))))
+        return Y.view(B, S * F), (H, Q, K, V, Y, m, z)
+
+    def _attend_bwd(self, dZ, kept):
+        """dP, dW_k, db_k, dW_v, db_v from dZ [B, S F]; returns dH in the stack's gradient buffer."""
+        H, Q, K, V, Y, m, z = kept
+        B, F, S, Hh, n = self.batch.n_graphs, self.net.dims[-1], self.pool.n_seeds, self.pool.heads, int(H.shape[0])
+        (_, W_k, _, W_v, _), (dP, dW_k, db_k, dW_v, db_v) = self._att, self._datt
+        dY = dZ.view(B * S, F)
+        seg = (self.batch.graph_ptr, self._qsegptr)
+        dQ, dot = segment_cross_attention_bwd_rows(*seg, dY, Q, K, V, Y, Hh, m, z, dq_out=self._tmp("dQ", (B * S, F)),
+                                                   dot_out=self._tmp("dot", (B * S, Hh)))
+        dK, dV = segment_cross_attention_bwd_cols(*seg, dY, Q, K, V, Hh, m, z, dot, dk_out=self._tmp("dK", (n, F)), dv_out=self._tmp("dV", (n, F)))
+        colsum(dQ.view(B, S * F), out=dP.view(-1))   # the seeds are shared by the graphs
+        gemm(dK, H, transA=True, out=dW_k), colsum(dK, out=db_k)
+        gemm(dV, H, transA=True, out=dW_v), colsum(dV, out=db_v)
+        dH = gemm(dK, W_k, out=self.net.grad_buffer())
+        return gemm(dV, W_v, out=dH, beta=1.0)
 
     def forward(self, X):
-        """logits [B, n_classes]; the pooled Z [B, dims[-1]] is kept (self.Z) with the readout's arg for backward."""
+        """logits [B, n_classes]; the pooled Z [B, dims[-1]] ([B, n_seeds dims[-1]] of the attention readout) is kept (self.Z) with
+        what the readout's backward needs."""
         B, d = self.batch.n_graphs, self.net.dims[-1]
         H = self.net.forward(X)
-        Z, arg = segment_pool(self.batch.graph_ptr, H, self.pool, out=self._tmp("Z", (B, d)),
-                              arg_out=self._tmp("arg", (B, d), torch.int32) if self.pool == "max" else None)
+        if self._att:
+            Z, arg = self._attend(H)
+        else:
+            Z, arg = segment_pool(self.batch.graph_ptr, H, self.pool, out=self._tmp("Z", (B, d)),
+                                  arg_out=self._tmp("arg", (B, d), torch.int32) if self.pool == "max" else None)
         logits = bias_add(gemm(Z, self.W_c, transB=True, out=self._tmp("ZW", (B, self.n_classes))), self.b_c, out=self._tmp("logits", (B, self.n_classes)))
         self._saved = (Z, arg)
         self.Z = Z
         return logits
 
     def backward(self, dlogits, have_bias_grad=False):
-        """dW_c, db_c and every gradient of the stack from dlogits = dL/dlogits.  have_bias_grad: db_c was already written by the loss
-        kernel (softmax_ce(..., colsum_out=clf.db_c))."""
+        """dW_c, db_c, the attention readout's gradients and every gradient of the stack from dlogits = dL/dlogits.  have_bias_grad: db_c
+        was already written by the loss kernel (softmax_ce(..., colsum_out=clf.db_c))."""
         Z, arg = self._saved
         if not have_bias_grad:
             colsum(dlogits, out=self.db_c)
         gemm(dlogits, Z, transA=True, out=self.dW_c)
         dZ = gemm(dlogits, self.W_c, out=self._tmp("dZ", tuple(Z.shape)))
-        dH = segment_pool_bwd(self.batch.graph_ptr, dZ, self.pool, arg=arg, out=self.net.grad_buffer())
+        if self._att:
+            dH = self._attend_bwd(dZ, arg)
+        else:
+            dH = segment_pool_bwd(self.batch.graph_ptr, dZ, self.pool, arg=arg, out=self.net.grad_buffer())
         self.net.backward(dH, input_grad=False)
 
     def train_step(self, X, target, lr, weight_decay=0.0):

@@ -1049,6 +1049,69 @@ int gnnx_segment_attn_bwd_cols_f32(int32_t n_seg, int32_t n_rows, const int32_t 
                                    int64_t ldv, const float *d_rowmax, const float *d_rowsum, const float *d_dot, float beta, float *d_dK,
                                    int64_t lddk, float *d_dV, int64_t lddv, void *stream);
 
+/* ------------------------------------------------------------------ cross segment attention ----- */
+/*
+ * Dense attention BETWEEN two segment sets of a batch: the queries of segment g attend over the keys of segment g -- a few learned query
+ * rows per graph over that graph's vertices (the attention readout: Set Transformer's PMA, GMT, attentional aggregation with heads).  The
+ * arguments are those of the dense segment attention calls with (n_q, d_qsegptr) beside (n_rows, d_segptr): d_qsegptr, int32
+ * [n_seg + 1], cuts the n_q QUERY rows, d_segptr the n_rows KEY rows; both are trusted (non-decreasing from 0, ends at most n_q /
+ * n_rows), a segment of either may be empty.  Q, G, Y, dQ and the three [.., H] arrays have n_q rows; K, V, dK, dV have n_rows rows.  For
+ * query row i of query segment g and the key rows j of key segment g, per head
+ *     s_ij = scale * <Q_i, K_j>_h;   m_i = max_j s_ij;   x_ij = expf(s_ij - m_i);   z_i = sum_j x_ij
+ * gnnx_segment_cross_attn_f32 -- forward:  Y_i = (sum_j x_ij V_j) / z_i, d_rowmax = m, d_rowsum = z, [n_q, H] contiguous.  A query whose
+ *   key segment is empty, or that no segment holds, gives Y = +0, m = -inf, z = +0.
+ * gnnx_segment_cross_attn_bwd_rows_f32 -- dot[i, h] = <G_i, Y_i>_h (an output);  alpha_ij = expf(s_ij - m_i) / z_i;
+ *   ds_ij = alpha_ij * (<G_i, V_j>_h - dot[i, h]);   dQ_i = scale * sum_j ds_ij K_j;  a query without keys gets dQ = 0.
+ * gnnx_segment_cross_attn_bwd_cols_f32 -- dV_j = beta dV_j + sum_i alpha_ij G_i;   dK_j = beta dK_j + scale * sum_i ds_ij Q_i (beta 0 or 1;
+ *   with 0 the outputs are never read).  A key whose query segment is empty, or that no segment holds, gets beta * old; with n_q == 0 and
+ *   beta == 0 that is a matrix of zeros.
+ *
+ * ORDER, as far as it is fixed.  Forward and row side: a workgroup of FOUR wavefronts owns T consecutive query rows of the whole batch
+ * and one head; T is the largest of 32, 16, 8, 4, 2 with ceil(n_q / T) * n_heads >= 512 workgroups, or 1 -- a function of n_q and n_heads
+ * alone (few queries in all: more and smaller own tiles instead of an idle device).  It walks the segments that hold a query of its tile in ascending order and cuts each one's keys into tiles of 32 from the
+ * segment's first key; the (segment, key tile) pairs are numbered t = 0, 1, 2, ... as walked, over the whole own tile, and pair t goes
+ * to wavefront t mod 4.  Within a wavefront every operation is the dense segment attention's (one multiply by scale;  m' = max(m, tile
+ * maximum),  r = 1 if m == m' else expf(m - m'),  x = expf(s - m'),  tile sum = (16 terms ascending) + (the other 16),  z = z * r + that,
+ * N = N * r, the products accumulate in v_mfma_f32_32x32x2_f32) over the pairs it was dealt, from (m, z, N) = (-inf, +0, +0).  The four
+ * states are then MERGED in ascending wavefront order:
+ *     m* = max(max(max(m_0, m_1), m_2), m_3);   r_w = 1 if m_w == m* else expf(m_w - m*);
+ *     z = ((z_0 r_0 + z_1 r_1) + z_2 r_2) + z_3 r_3;   N the same, element by element;   Y = N / z, one IEEE division.
+ * A wavefront that was dealt no key of a row contributes exactly 0 (r = expf(-inf) = +0, or 1 with z = N = +0 when no wavefront saw a key;
+ * never a NaN).  Row side: alpha is one expf and one division from the operands m and z, ds = alpha * (dP - dot), each wavefront
+ * accumulates its own partial from +0, dQ = scale * (((p_0 + p_1) + p_2) + p_3).  dot is the dense call's.  Column side: one wavefront
+ * owns 32 consecutive keys and one head and streams the queries of its keys' segments in tiles of 32 from the segment's first query:
+ * one accumulator per output element from +0, dK takes one multiply by scale, beta = 1 is one add of the old value.  No atomics: two
+ * runs give the same bits, and the 16-byte and the scalar-load path give the same bits.  A query's bits depend on where its segment
+ * lies in its own tile of T (the deal), unlike the dense call's.
+ *
+ * Statuses, all before any HIP call: a negative n_seg, n_rows or n_q, n_heads < 1, head_dim < 1, a leading dimension < F, a beta other
+ * than 0 or 1, n_seg == 0 with n_rows + n_q != 0, and -- once there is work -- a null array that the work reads or writes are
+ * GNNX_ERR_INVALID_ARG; head_dim > 128 and n_heads > 65535 are GNNX_ERR_UNSUPPORTED.  n_q == 0 is a valid empty result of the forward
+ * and the row side; n_rows == 0 of the column side (the forward then writes the empty-segment values, and K, V may be null).
+ * Asynchronous on `stream`; no workspace; nothing is allocated or synchronised; offsets are 64-bit.  Inputs and outputs must not alias.
+ *
+ * Kernels (gnnx_segment_cross_attn.hip; the tile pieces are gnnx_segment_tiles.h's, shared with the dense unit).  Each wavefront stages
+ * its key tiles in an LDS region of its own -- two [32][DP + 4] tiles -- so the key loop has no workgroup barrier; the barriers stand
+ * around the own-tile load and the merge, which reuses the regions.  A workgroup takes 1024 (DP + 4) bytes of dynamic LDS (135 168 at
+ * DP = 128), opted in and checked against the device per kernel; a device that offers less is GNNX_ERR_UNSUPPORTED.
+ *
+ * Accuracy (tests/test_gpu_segment_cross_attn.py against the float64 loops of tests/segment_cross_attn_ref.py; bar c * 2^-24 * sum of the
+ * absolute terms, c the dense calls' counts plus the merge's): worst observed fraction of the bar over all tested cases: rowmax 0.43,
+ * rowsum 0.027, Y 0.013, dot 0.48, dQ 0.021, dK 0.058, dV 0.042.
+ */
+int gnnx_segment_cross_attn_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_q, const int32_t *d_qsegptr, int32_t n_heads,
+                                int32_t head_dim, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V,
+                                int64_t ldv, float *d_Y, int64_t ldy, float *d_rowmax, float *d_rowsum, void *stream);
+int gnnx_segment_cross_attn_bwd_rows_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_q, const int32_t *d_qsegptr,
+                                         int32_t n_heads, int32_t head_dim, float scale, const float *d_G, int64_t ldg, const float *d_Q,
+                                         int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv, const float *d_Y, int64_t ldy,
+                                         const float *d_rowmax, const float *d_rowsum, float *d_dQ, int64_t lddq, float *d_dot, void *stream);
+int gnnx_segment_cross_attn_bwd_cols_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_q, const int32_t *d_qsegptr,
+                                         int32_t n_heads, int32_t head_dim, float scale, const float *d_G, int64_t ldg, const float *d_Q,
+                                         int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv, const float *d_rowmax,
+                                         const float *d_rowsum, const float *d_dot, float beta, float *d_dK, int64_t lddk, float *d_dV,
+                                         int64_t lddv, void *stream);
+
 /* ------------------------------------------------------------------ dynamic attention scores (GATv2) ---- */
 /*
  * The score of GATv2 (Brody, Alon, Yahav, ICLR 2022): e(i, c) = a^T leaky_relu(W_l h_i + W_r h_c), the non-linearity INSIDE the sum.  The
