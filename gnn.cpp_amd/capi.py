@@ -178,6 +178,11 @@ _SIGS = {
                                        _vp, _vp],
     "gnnx_segment_attn_bwd_cols_f32": [_i32, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _f32, _vp, _i64,
                                        _vp, _i64, _vp],
+    "gnnx_segment_attn_bf16_f32": [_i32, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "gnnx_segment_attn_bwd_rows_bf16_f32": [_i32, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                            _i64, _vp, _vp],
+    "gnnx_segment_attn_bwd_cols_bf16_f32": [_i32, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _f32, _vp,
+                                            _i64, _vp, _i64, _vp],
     "gnnx_segment_cross_attn_f32": [_i32, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "gnnx_segment_cross_attn_bwd_rows_f32": [_i32, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                              _vp, _vp, _vp, _i64, _vp, _vp],

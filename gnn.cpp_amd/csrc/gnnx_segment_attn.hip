@@ -56,19 +56,6 @@ struct Args {
     int beta;
 };
 
-// body(lo, hi, active) for every non-empty segment [lo, hi) that intersects the tile [r0, r1); active: the lane's own row is in it
-template <class Body>
-__device__ __forceinline__ void for_segments(const Args &a, int64_t r0, int64_t r1, int64_t row, Body body)
-{
-    for (int32_t g = first_segment(a.segptr, a.n_seg, r0); g < a.n_seg; g++) {
-        int64_t lo = a.segptr[g], hi = a.segptr[g + 1];
-        if (lo >= r1) break;
-        lo = lo < 0 ? 0 : lo;
-        hi = hi > a.n_rows ? a.n_rows : hi;
-        if (hi > lo) body(lo, hi, row >= lo && row < hi);
-    }
-}
-
 // ---- forward -----------------------------------------------------------------------------------------------------------------------
 template <int DP, bool VEC>
 __global__ __launch_bounds__(kWave) void fwd_kernel(Args a)
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(kWave) void fwd_kernel(Args a)
         for (int r = 0; r < 16; r++) N[i][r] = 0.f;
     float m = -INFINITY, z = 0.f;
 
-    for_segments(a, r0, r1, row, [&](int64_t lo, int64_t hi, bool active) {
+    for_segments(a.segptr, a.n_seg, a.n_rows, r0, r1, row, [&](int64_t lo, int64_t hi, bool active) {
         for (int64_t kb = lo; kb < hi; kb += kTile) {
             copy_in<DP, VEC>(ks, a.K, a.ldk, c0, a.D, kb, hi, lane);
             copy_in<DP, VEC>(vs, a.V, a.ldv, c0, a.D, kb, hi, lane);
@@ -174,7 +161,7 @@ __global__ __launch_bounds__(kWave) void bwd_rows_kernel(Args a)
 #pragma unroll
         for (int r = 0; r < 16; r++) dq[i][r] = 0.f;
 
-    for_segments(a, r0, r1, row, [&](int64_t lo, int64_t hi, bool active) {
+    for_segments(a.segptr, a.n_seg, a.n_rows, r0, r1, row, [&](int64_t lo, int64_t hi, bool active) {
         for (int64_t kb = lo; kb < hi; kb += kTile) {
             copy_in<DP, VEC>(ks, a.K, a.ldk, c0, a.D, kb, hi, lane);
             copy_in<DP, VEC>(vs, a.V, a.ldv, c0, a.D, kb, hi, lane);
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(kWave) void bwd_cols_kernel(Args a)
 #pragma unroll
         for (int r = 0; r < 16; r++) dv[i][r] = 0.f, dk[i][r] = 0.f;
 
-    for_segments(a, r0, r1, row, [&](int64_t lo, int64_t hi, bool active) {
+    for_segments(a.segptr, a.n_seg, a.n_rows, r0, r1, row, [&](int64_t lo, int64_t hi, bool active) {
         for (int64_t qb = lo; qb < hi; qb += kTile) {
             copy_in<DP, VEC>(qs, a.Q, a.ldq, c0, a.D, qb, hi, lane);
             copy_in<DP, VEC>(gs, a.G, a.ldg, c0, a.D, qb, hi, lane);
@@ -260,17 +247,6 @@ __global__ __launch_bounds__(kWave) void bwd_cols_kernel(Args a)
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-// what all three calls check before any HIP call
-int check_common(int32_t n_seg, int32_t n_rows, int32_t H, int32_t D)
-{
-    GNNX_REQUIRE(n_seg >= 0 && n_rows >= 0, GNNX_ERR_INVALID_ARG, "negative size");
-    GNNX_REQUIRE(H >= 1 && D >= 1, GNNX_ERR_INVALID_ARG, "n_heads < 1 or head_dim < 1");
-    GNNX_REQUIRE(n_seg > 0 || n_rows == 0, GNNX_ERR_INVALID_ARG, "rows without a segment");
-    GNNX_REQUIRE(D <= kMaxDim, GNNX_ERR_UNSUPPORTED, "head_dim %d > %d", D, kMaxDim);
-    GNNX_REQUIRE(H <= 65535, GNNX_ERR_UNSUPPORTED, "%d heads are too many for one launch", H);
-    return GNNX_OK;
-}
-
 #define SEG_ATTN_ONE(kernel, DP)                                                                       \
     do {                                                                                               \
         if (vec) hipLaunchKernelGGL((kernel<DP, true>), grid, dim3(kWave), 0, st, a);                  \
@@ -292,7 +268,7 @@ GNNX_API int gnnx_segment_attn_f32(int32_t n_seg, int32_t n_rows, const int32_t 
                                    const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv, float *d_Y, int64_t ldy,
                                    float *d_rowmax, float *d_rowsum, void *stream)
 {
-    const int rc = check_common(n_seg, n_rows, n_heads, head_dim);
+    const int rc = check_self_attn(n_seg, n_rows, n_heads, head_dim);
     if (rc) return rc;
     const int64_t F = (int64_t)n_heads * head_dim;
     GNNX_REQUIRE(ldq >= F && ldk >= F && ldv >= F && ldy >= F, GNNX_ERR_INVALID_ARG, "ld < n_heads * head_dim");
@@ -311,7 +287,7 @@ GNNX_API int gnnx_segment_attn_bwd_rows_f32(int32_t n_seg, int32_t n_rows, const
                                             const float *d_V, int64_t ldv, const float *d_Y, int64_t ldy, const float *d_rowmax,
                                             const float *d_rowsum, float *d_dQ, int64_t lddq, float *d_dot, void *stream)
 {
-    const int rc = check_common(n_seg, n_rows, n_heads, head_dim);
+    const int rc = check_self_attn(n_seg, n_rows, n_heads, head_dim);
     if (rc) return rc;
     const int64_t F = (int64_t)n_heads * head_dim;
     GNNX_REQUIRE(ldg >= F && ldq >= F && ldk >= F && ldv >= F && ldy >= F && lddq >= F, GNNX_ERR_INVALID_ARG, "ld < n_heads * head_dim");
@@ -331,7 +307,7 @@ GNNX_API int gnnx_segment_attn_bwd_cols_f32(int32_t n_seg, int32_t n_rows, const
                                             const float *d_V, int64_t ldv, const float *d_rowmax, const float *d_rowsum, const float *d_dot,
                                             float beta, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
 {
-    const int rc = check_common(n_seg, n_rows, n_heads, head_dim);
+    const int rc = check_self_attn(n_seg, n_rows, n_heads, head_dim);
     if (rc) return rc;
     const int64_t F = (int64_t)n_heads * head_dim;
     GNNX_REQUIRE(ldg >= F && ldq >= F && ldk >= F && ldv >= F && lddk >= F && lddv >= F, GNNX_ERR_INVALID_ARG, "ld < n_heads * head_dim");

@@ -1,6 +1,8 @@
 // The tile pieces shared by the dense segment attention units (gnnx_segment_attn.hip, gnnx_segment_cross_attn.hip): a [32][DP + 4] LDS
 // tile, its copy from global memory, the MFMA operand readers, the accumulator's row map and the store of a lane's own row.  Every piece
 // is written for ONE wavefront: `lane` is the lane within it, and a tile belongs to the wavefront that copies and reads it.
+// gnnx_segment_attn_bf16.hip has bf16 images and readers of its own and takes the segment walk, the row map, the store and the status
+// checks from here.
 //
 // Streamed and own tiles are [32][DP + 4] floats, DP = the head width zero-padded to 16, 32, 64 or 128 (the instantiations,
 // GNNX_SEG_FOR_DP); each row is loaded from global memory with 16-byte loads where D % 4 == 0 and every pointer and pitch is 16-byte
@@ -138,9 +140,33 @@ __device__ __forceinline__ int32_t first_segment(const int32_t *segptr, int32_t 
     return lo;
 }
 
+// body(lo, hi, active) for every non-empty segment [lo, hi) that intersects the tile [r0, r1); active: the lane's own row is in it
+template <class Body>
+__device__ __forceinline__ void for_segments(const int32_t *segptr, int32_t n_seg, int32_t n_rows, int64_t r0, int64_t r1, int64_t row, Body body)
+{
+    for (int32_t g = first_segment(segptr, n_seg, r0); g < n_seg; g++) {
+        int64_t lo = segptr[g], hi = segptr[g + 1];
+        if (lo >= r1) break;
+        lo = lo < 0 ? 0 : lo;
+        hi = hi > n_rows ? n_rows : hi;
+        if (hi > lo) body(lo, hi, row >= lo && row < hi);
+    }
+}
+
 template <int DP> struct Lds { static constexpr int kFloats = kTile * (DP + 4); };
 
 inline bool vec4(int64_t ld, const void *p) { return ld % 4 == 0 && aligned16(p); }
+
+// what the dense segment attention calls of either operand type check before any HIP call
+inline int check_self_attn(int32_t n_seg, int32_t n_rows, int32_t H, int32_t D)
+{
+    GNNX_REQUIRE(n_seg >= 0 && n_rows >= 0, GNNX_ERR_INVALID_ARG, "negative size");
+    GNNX_REQUIRE(H >= 1 && D >= 1, GNNX_ERR_INVALID_ARG, "n_heads < 1 or head_dim < 1");
+    GNNX_REQUIRE(n_seg > 0 || n_rows == 0, GNNX_ERR_INVALID_ARG, "rows without a segment");
+    GNNX_REQUIRE(D <= kMaxDim, GNNX_ERR_UNSUPPORTED, "head_dim %d > %d", D, kMaxDim);
+    GNNX_REQUIRE(H <= 65535, GNNX_ERR_UNSUPPORTED, "%d heads are too many for one launch", H);
+    return GNNX_OK;
+}
 
 }  // namespace seg
 }  // namespace gnnx

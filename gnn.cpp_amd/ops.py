@@ -1264,9 +1264,10 @@ def _gat_fused_args(where, rowptr, colidx, n_heads, rowterm, colterm, n_cols, ma
     return n_rows, nnz, D, rt, rs, ct, cs
 
 
-def _gat_matrix(where, name, t, rows, F):
-    if t.dim() != 2 or tuple(t.shape) != (rows, F) or t.dtype != torch.float32 or t.stride(1) != 1 or not t.is_cuda:
-        raise capi.GnnxError(-2, where, f"{name} must be a row-major float32 [{rows}, {F}] matrix on the device, got {tuple(t.shape)} {t.dtype}")
+def _gat_matrix(where, name, t, rows, F, dtype=torch.float32):
+    if t.dim() != 2 or tuple(t.shape) != (rows, F) or t.dtype != dtype or t.stride(1) != 1 or not t.is_cuda:
+        kind = "float32" if dtype == torch.float32 else str(dtype)
+        raise capi.GnnxError(-2, where, f"{name} must be a row-major {kind} [{rows}, {F}] matrix on the device, got {tuple(t.shape)} {t.dtype}")
 
 
 def _gat_stat(t, n, H, what, where):
@@ -1445,7 +1446,13 @@ def attn_aggregate_bwd_cols(rowptr_t, colidx_t, G, Q, K, V, n_heads, rowmax, row
 
 def _segment_attn_args(where, segptr, n_heads, mats, scale):
     """What the three dense segment attention calls share: the checked segptr, the checked [n_rows, H*D] matrices (mats: (name, tensor)
-    pairs, the first one fixes the shape) and the scale (default D ** -0.5)."""
+    pairs, the first one fixes the shape), the scale (default D ** -0.5) and the calls' suffix: "_bf16_f32" when Q is torch.bfloat16 --
+    then G, K and V must be bfloat16 too and every other matrix float32, and a mixed call is refused naming the tensor --, else "_f32"."""
+    half = dict(mats)["Q"].dtype == torch.bfloat16
+    want = {name: torch.bfloat16 if half and name in ("G", "Q", "K", "V") else torch.float32 for name, _ in mats}
+    for name, t in mats:
+        if half and t.dtype != want[name]:
+            raise capi.GnnxError(-2, where, f"Q is bfloat16, so {name} must be {want[name]}, got {t.dtype}")
     if segptr.dtype != torch.int32 or segptr.dim() != 1 or segptr.numel() < 1 or not segptr.is_contiguous():
         raise capi.GnnxError(-2, where, f"segptr must be a contiguous int32 [n_seg + 1] array, got {tuple(segptr.shape)} {segptr.dtype}")
     if mats[0][1].dim() != 2:
@@ -1453,22 +1460,23 @@ def _segment_attn_args(where, segptr, n_heads, mats, scale):
     n_rows, F = (int(v) for v in mats[0][1].shape)
     D = _heads_of(mats[0][1], n_heads, where)
     for name, t in mats:
-        _gat_matrix(where, name, t, n_rows, F)
-    return int(segptr.numel() - 1), n_rows, F, D, float(D ** -0.5 if scale is None else scale)
+        _gat_matrix(where, name, t, n_rows, F, want[name])
+    return int(segptr.numel() - 1), n_rows, F, D, float(D ** -0.5 if scale is None else scale), "_bf16_f32" if half else "_f32"
 
 
 def segment_attention(segptr, Q, K, V, n_heads, scale=None, out=None, stats_out=None):
-    """gnnx_segment_attn_f32: dense self-attention inside the segments of segptr (segment_pool's segptr; GraphBatch.graph_ptr) on the
+    """gnnx_segment_attn_f32 (gnnx_segment_attn_bf16_f32 when Q, K and V are torch.bfloat16: bf16 matrix cores, f32 Y and statistics; the
+    backward calls dispatch likewise on Q, with G bfloat16 too): dense self-attention inside the segments of segptr (segment_pool's segptr; GraphBatch.graph_ptr) on the
     matrix cores, no index array and no workspace --
         Y[i] = sum_j alpha_ij V[j],  alpha = softmax over the rows j of i's segment of scale * <Q[i], K[j]> per head.
     Q, K, V: [n_rows, H*D], each may be a column slab of a wider matrix; D <= 128.  scale defaults to D ** -0.5.  Returns (Y, rowmax,
     rowsum), the statistics as [n_rows, H] (stats_out = (rowmax, rowsum) to write them into the caller's arrays)."""
     where = "segment_attention"
-    n_seg, n_rows, F, D, scale = _segment_attn_args(where, segptr, n_heads, [("Q", Q), ("K", K), ("V", V)], scale)
+    n_seg, n_rows, F, D, scale, kind = _segment_attn_args(where, segptr, n_heads, [("Q", Q), ("K", K), ("V", V)], scale)
     dev = Q.device
     out = _attn_out(where, "out", out, n_rows, F, dev)
     rowmax, rowsum = stats_out if stats_out is not None else (torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) for _ in range(2))
-    capi.call("gnnx_segment_attn_f32", n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(Q), _ld(Q), _ptr(K), _ld(K), _ptr(V), _ld(V), _ptr(out),
+    capi.call("gnnx_segment_attn" + kind, n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(Q), _ld(Q), _ptr(K), _ld(K), _ptr(V), _ld(V), _ptr(out),
               _ld(out), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where), _gat_stat(rowsum, n_rows, n_heads, "rowsum", where), _stream())
     return out, rowmax, rowsum
 
@@ -1477,11 +1485,11 @@ def segment_attention_bwd_rows(segptr, G, Q, K, V, Y, n_heads, rowmax, rowsum, s
     """gnnx_segment_attn_bwd_rows_f32: (dQ [n_rows, H*D], dot [n_rows, H]) from G = dL/dY, the forward's operands, its Y and its
     statistics.  dot goes to segment_attention_bwd_cols."""
     where = "segment_attention_bwd_rows"
-    n_seg, n_rows, F, D, scale = _segment_attn_args(where, segptr, n_heads, [("G", G), ("Q", Q), ("K", K), ("V", V), ("Y", Y)], scale)
+    n_seg, n_rows, F, D, scale, kind = _segment_attn_args(where, segptr, n_heads, [("G", G), ("Q", Q), ("K", K), ("V", V), ("Y", Y)], scale)
     dev = Q.device
     dQ = _attn_out(where, "dq_out", dq_out, n_rows, F, dev)
     dot = torch.empty((n_rows, n_heads), dtype=torch.float32, device=dev) if dot_out is None else dot_out
-    capi.call("gnnx_segment_attn_bwd_rows_f32", n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K),
+    capi.call("gnnx_segment_attn_bwd_rows" + kind, n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K),
               _ptr(V), _ld(V), _ptr(Y), _ld(Y), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where),
               _gat_stat(rowsum, n_rows, n_heads, "rowsum", where), _ptr(dQ), _ld(dQ), _gat_stat(dot, n_rows, n_heads, "dot_out", where), _stream())
     return dQ, dot
@@ -1491,12 +1499,12 @@ def segment_attention_bwd_cols(segptr, G, Q, K, V, n_heads, rowmax, rowsum, dot,
     """gnnx_segment_attn_bwd_cols_f32: (dK, dV), both [n_rows, H*D], with dV[j] = beta*dV[j] + sum_i alpha_ij G[i] and
     dK[j] = beta*dK[j] + scale * sum_i ds_ij Q[i] over the rows i of j's segment; dot is segment_attention_bwd_rows'."""
     where = "segment_attention_bwd_cols"
-    n_seg, n_rows, F, D, scale = _segment_attn_args(where, segptr, n_heads, [("G", G), ("Q", Q), ("K", K), ("V", V)], scale)
+    n_seg, n_rows, F, D, scale, kind = _segment_attn_args(where, segptr, n_heads, [("G", G), ("Q", Q), ("K", K), ("V", V)], scale)
     dev = Q.device
     if beta and (dk_out is None or dv_out is None):
         raise capi.GnnxError(-2, where, "beta = 1 adds onto dk_out and dv_out, which were not given")
     dK, dV = _attn_out(where, "dk_out", dk_out, n_rows, F, dev), _attn_out(where, "dv_out", dv_out, n_rows, F, dev)
-    capi.call("gnnx_segment_attn_bwd_cols_f32", n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K),
+    capi.call("gnnx_segment_attn_bwd_cols" + kind, n_seg, n_rows, _ptr(segptr), n_heads, D, scale, _ptr(G), _ld(G), _ptr(Q), _ld(Q), _ptr(K), _ld(K),
               _ptr(V), _ld(V), _gat_stat(rowmax, n_rows, n_heads, "rowmax", where), _gat_stat(rowsum, n_rows, n_heads, "rowsum", where),
               _gat_stat(dot, n_rows, n_heads, "dot", where), float(beta), _ptr(dK), _ld(dK), _ptr(dV), _ld(dV), _stream())
     return dK, dV

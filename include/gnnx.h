@@ -1049,6 +1049,47 @@ int gnnx_segment_attn_bwd_cols_f32(int32_t n_seg, int32_t n_rows, const int32_t 
                                    int64_t ldv, const float *d_rowmax, const float *d_rowsum, const float *d_dot, float beta, float *d_dK,
                                    int64_t lddk, float *d_dV, int64_t lddv, void *stream);
 
+/* ------------------------------------------------------------------ dense segment attention, bf16 operands ----- */
+/*
+ * The three dense segment attention calls on bf16 STORAGE (the naming of gnnx_spmm_csr_bf16_f32: bf16 in, f32 accumulation, f32 out):
+ * d_Q, d_K, d_V and d_G hold bf16 bit patterns (gnnx_f32_to_bf16's, the bf16 product epilogue's) with their leading dimensions in bf16
+ * elements; Y, rowmax, rowsum, dot, dQ, dK, dV, the row side's d_Y input and scale stay float.  Definitions, statuses, D <= 128,
+ * beta in {0, 1}, "no workspace, no atomics, every loop bounded" and the work split are the f32 calls'; every product runs on
+ * v_mfma_f32_32x32x16_bf16 (8 + 16 matrix instructions per 32 x 32 forward tile at D = 128 against 64 + 64).
+ *
+ * ORDER.  Products of two bf16 are exact in f32; the dot products and the sums over a tile's 32 rows accumulate in f32 in the matrix
+ * pipe's order.  Outside it every operation is one separately rounded fp32 operation in the f32 calls' order (one multiply by scale;
+ * m' = max(m, tile maximum), r = 1 if m == m' else expf(m - m'), x = expf(s - m'), the tile's sum = (16 terms ascending) + (the other
+ * 16), z = z * r + that, N = N * r, Y = N / z;  alpha = expf(scale * s - m) / z, ds = alpha * (dP - dot);  one multiply by scale on dQ
+ * and dK;  beta = 1 is one add).  rowmax is the maximum of scale * s and rowsum the f32 sum of the UNROUNDED x, so both backward calls
+ * recompute alpha from them.  EXACTLY three values are narrowed to bf16, as matrix operands:  x in the forward's numerator (z sums
+ * the f32 x),  alpha in dV,  ds in dQ and dK.  Each enters as TWO bf16 terms, hi = bf16(w) to nearest even and lo = bf16(w - hi) of the
+ * exact remainder, one matrix instruction each, hi first: the operand is w to 2^-16 relative.  (hi alone is w to 2^-8 -- half of
+ * bf16's spacing 2^-7 -- and cannot keep the accuracy bars below, which allow 2^-9.)  dot = <G, Y> is float(G) * Y in f32: the lane's
+ * products ascending from +0 plus the other half-wave's.  One accumulator per output element, the same bits every run; the 16-byte and
+ * the 2-byte copy paths (D % 8 != 0, or a bf16 pointer / leading dimension off 16 bytes) give the same bits.
+ *
+ * Kernels (gnnx_segment_attn_bf16.hip): a streamed tile has up to two bf16 images in LDS, a row image [32][DP + 8] for the score-like
+ * products and a transposed image [DP][40] with the streamed rows permuted (bits 2 and 3 of the row exchanged) for the output-like ones,
+ * so that the weights' accumulator registers, split and packed in place, are the B operands and every operand is one 16-byte LDS read.
+ * No kernel spills.
+ *
+ * Accuracy (tests/test_gpu_segment_attn_bf16.py; the operands are rounded to bf16 on the host and the float64 reference sees the same
+ * values; bars c * 2^-24 * S with c from tests/segment_attn_bf16_ref.py: a narrowed operand adds 2^15 to c of the outputs it feeds):
+ * worst observed fraction of the bar: rowmax 0.18, rowsum 0.038, Y 0.0013, dot 0.28, dQ 0.0008, dK 0.0009, dV 0.0020.
+ */
+int gnnx_segment_attn_bf16_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_heads, int32_t head_dim, float scale,
+                               const uint16_t *d_Q, int64_t ldq, const uint16_t *d_K, int64_t ldk, const uint16_t *d_V, int64_t ldv, float *d_Y,
+                               int64_t ldy, float *d_rowmax, float *d_rowsum, void *stream);
+int gnnx_segment_attn_bwd_rows_bf16_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_heads, int32_t head_dim, float scale,
+                                        const uint16_t *d_G, int64_t ldg, const uint16_t *d_Q, int64_t ldq, const uint16_t *d_K, int64_t ldk,
+                                        const uint16_t *d_V, int64_t ldv, const float *d_Y, int64_t ldy, const float *d_rowmax,
+                                        const float *d_rowsum, float *d_dQ, int64_t lddq, float *d_dot, void *stream);
+int gnnx_segment_attn_bwd_cols_bf16_f32(int32_t n_seg, int32_t n_rows, const int32_t *d_segptr, int32_t n_heads, int32_t head_dim, float scale,
+                                        const uint16_t *d_G, int64_t ldg, const uint16_t *d_Q, int64_t ldq, const uint16_t *d_K, int64_t ldk,
+                                        const uint16_t *d_V, int64_t ldv, const float *d_rowmax, const float *d_rowsum, const float *d_dot,
+                                        float beta, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream);
+
 /* ------------------------------------------------------------------ cross segment attention ----- */
 /*
  * Dense attention BETWEEN two segment sets of a batch: the queries of segment g attend over the keys of segment g -- a few learned query

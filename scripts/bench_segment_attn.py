@@ -10,7 +10,9 @@ on two batches -- "small": --graphs graphs of 16 .. 64 vertices (seeded uniform)
 (H, D) = (8, 16), (4, 32), (1, 128).  Every figure: --repeats single calls between two device events after --warmup calls; the median
 and the range.  extra_MiB: what each side holds beside Q, K, V, G and its outputs -- segptr on one side, rowptr + colidx + the
 workspace the CSR calls ask for on the other.  max_diff: the largest |segment - csr| of each output over the largest |csr|; the run fails at
-the end if one passes 1e-4.  One JSON line per cell."""
+the end if one passes 1e-4.  One JSON line per cell.
+
+--bf16 measures instead the bf16 calls against the f32 calls (bf16_leg) on the same two batches at (4, 32), (2, 64), (1, 128)."""
 import argparse
 import importlib
 import json
@@ -22,6 +24,45 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = ((8, 16), (4, 32), (1, 128))
+BF16_SHAPES = ((4, 32), (2, 64), (1, 128))
+
+
+def bf16_leg(args, torch, ops, dev, batches, timed):
+    """--bf16: gnnx_segment_attn*_bf16_f32 against gnnx_segment_attn*_f32 on the same batches, alternated call by call.  The f32 side gets
+    the bf16 operands widened to float32 (the same values), so max_diff is the kernels' own arithmetic alone; each side's backward
+    uses its own forward's Y and statistics.  to_bf16_ms: what a caller who holds float32 Q, K, V, G pays to convert them, on its own."""
+    for name, sizes in batches.items():
+        segptr = torch.cat([torch.zeros(1, dtype=torch.int64), sizes.cumsum(0)]).to(torch.int32).to(dev)
+        n = int(segptr[-1])
+        print(json.dumps({"batch": name, "graphs": int(sizes.numel()), "n": n}), flush=True)
+        for H, D in BF16_SHAPES:
+            F = H * D
+            P32 = ops.uniform_pm1(3, (n, 4 * F), device=dev)
+            Ph = torch.empty((n, 4 * F), dtype=torch.bfloat16, device=dev)
+            ops.to_bf16(P32, out=Ph)
+            Pf = Ph.float()
+            mats = {"bf16": [Ph[:, k * F:(k + 1) * F] for k in range(4)], "f32": [Pf[:, k * F:(k + 1) * F] for k in range(4)]}   # Q, K, V, G
+            out = {s: [torch.empty((n, F), device=dev) for _ in range(4)] for s in mats}   # Y, dQ, dK, dV
+            st = {}
+
+            def fwd(s):
+                Q, K, V, _ = mats[s]
+                st[s] = ops.segment_attention(segptr, Q, K, V, H, out=out[s][0])
+
+            def rows(s):
+                Q, K, V, G = mats[s]
+                Y, m, z = st[s]
+                st[s + "d"] = ops.segment_attention_bwd_rows(segptr, G, Q, K, V, Y, H, m, z, dq_out=out[s][1])[1]
+
+            def cols(s):
+                Q, K, V, G = mats[s]
+                ops.segment_attention_bwd_cols(segptr, G, Q, K, V, H, st[s][1], st[s][2], st[s + "d"], dk_out=out[s][2], dv_out=out[s][3])
+
+            both = lambda f: {s: (lambda s=s: f(s)) for s in ("bf16", "f32")}  # noqa: E731
+            row = {"batch": name, "H": H, "D": D, "forward_ms": timed(both(fwd)), "bwd_rows_ms": timed(both(rows)),
+                   "bwd_cols_ms": timed(both(cols)), "to_bf16_ms": timed({"QKVG": lambda: ops.to_bf16(P32, out=Ph)})["QKVG"]}
+            row["max_diff"] = {k: float((a - b).abs().max() / b.abs().max()) for k, a, b in zip(("Y", "dQ", "dK", "dV"), out["bf16"], out["f32"])}
+            print(json.dumps(row), flush=True)
 
 
 def main():
@@ -31,6 +72,7 @@ def main():
     ap.add_argument("--big-size", type=int, default=1024)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--bf16", action="store_true", help="the bf16 calls against the f32 calls on the same (bf16-valued) operands instead")
     args = ap.parse_args()
     import torch
     from __graft_entry__ import load_package
@@ -55,6 +97,8 @@ def main():
 
     gen = torch.Generator().manual_seed(11)
     batches = {"small": torch.randint(16, 65, (args.graphs,), generator=gen), "large": torch.full((args.big_graphs,), args.big_size)}
+    if args.bf16:
+        return bf16_leg(args, torch, ops, dev, batches, timed)
     worst = 0.0
     for name, sizes in batches.items():
         segptr = torch.cat([torch.zeros(1, dtype=torch.int64), sizes.cumsum(0)]).to(torch.int32).to(dev)
